@@ -13,7 +13,11 @@ A "step" is one full Pyro.single_step of the hot path: ghost fill (halo
 exchange), CFL time step (device reduction + driver dt policy), evolve.
 State is resident in HBM before the timed region starts.
 
-Rank 0 prints ONE JSON line.  At N=1 it also carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the --steps
+steps and prints the headline (metric, value, unit, higher_is_better, dtype,
+ms_per_step, config); --dump-outputs DIR also writes what the timed steps
+computed (dump_outputs).  Everything else is measured with --full only: the
+scale check of a decomposed run, the full record in a side file, and at N=1
   roofline      HBM roofline of the update kernels (HIP events, per launch),
                 with the FP64-VALU figures that actually bind this kernel
   cpu_baseline  the oracle (CPU port of the reference) on a bounded sample
@@ -89,7 +93,8 @@ def parse():
     ap.add_argument("--scale-check", action="store_true", default=None,
                     help="before timing: compressible Sedov 2048^2, 12 steps, on 1 rank vs the N ranks "
                          "of this run, must agree bit for bit (SURVEY 8(d).5); the result goes "
-                         "into config.scale_check, a mismatch is fatal.  On by default at --gpus > 1")
+                         "into config.scale_check, a mismatch is fatal.  On by default at --gpus > 1 "
+                         "with --full")
     ap.add_argument("--no-scale-check", dest="scale_check", action="store_false",
                     help="skip the bit-identity check of the decomposed run (--gpus > 1)")
     ap.add_argument("--slab-of", type=int, default=0,
@@ -106,6 +111,14 @@ def parse():
     ap.add_argument("--host-dt", action="store_true",
                     help="step from the host (one dt read-back per step) instead of "
                          "pyrohip_comp_evolve")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: roofline (an instrumented pass after the timed "
+                         "steps), cpu_baseline, the secondary legs (`also`), the scale check and the "
+                         "class-surface leg of a decomposed run, and the full record in a side file.  "
+                         "Without it a run sets up, warms up, times --steps steps and prints its line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed to DIR/<name>.npy (float64, "
+                         "< 64 MB in all; see dump_outputs())")
     return ap.parse_args()
 
 
@@ -282,10 +295,12 @@ def developed_tile(ctx, device, n=1024, tmax=0.1):
 
 
 def bench_sedov(args, dist, ctx, device, defaults, steps=None, warmup=None, tile=None, nx=None,
-                collect=False):
+                collect=False, profile=True, dump=None):
     """tile = None: the Sedov initial condition at t = 0 (BASELINE config);
     tile = (n, n, 4) array: that state repeated over the whole grid;
-    collect: also return this rank's final slab interior (scale check)"""
+    collect: also return this rank's final slab interior (scale check);
+    profile: the instrumented pass after the timed steps (per-kernel HIP events, roofline);
+    dump: called as dump(state, decomp, ng, dts) right after the timed steps"""
     from pyro2_amd.compressible.problems.sedov import sedov_state
     from pyro2_amd.decomp import DtPolicy, NoComm, RcclComm, SlabCompressible, SlabDecomp
     nx = ny = args.nx if nx is None else nx
@@ -326,19 +341,20 @@ def bench_sedov(args, dist, ctx, device, defaults, steps=None, warmup=None, tile
     device_dt = not args.host_dt and isinstance(comm, (NoComm, RcclComm))
 
     def run(n):
+        """n steps; returns their dts"""
         if n <= 0:
-            return
+            return []
         if device_dt:
-            assert len(slab.evolve(pol, 0.8, n)) == n
-        else:
-            for _ in range(n):
-                slab.step(pol, 0.8)
+            dts = slab.evolve(pol, 0.8, n)
+            assert len(dts) == n
+            return list(dts)
+        return [slab.step(pol, 0.8) for _ in range(n)]
     run(warmup)
     ctx.sync()
     dist.barrier()
     ctx.timer_start()
     t0 = time.perf_counter()
-    run(steps)
+    dts = run(steps)
     ctx.sync()
     t1 = time.perf_counter()
     ev_ms = ctx.timer_stop()
@@ -350,16 +366,20 @@ def bench_sedov(args, dist, ctx, device, defaults, steps=None, warmup=None, tile
         # single-domain one; found by running two ranks on one GPU)
         snap = {"interior": st.download()[ng:-ng, ng:-ng].copy(), "rows": (dec.i0, dec.nx_local),
                 "t": pol.t}
-    # the kernels' own durations: more steps with the library's HIP events around every
-    # launch, OUTSIDE the timed region (the events cost ~4 us per launch: nothing against the
-    # 9.5 ms kernel of the headline, 2-7 % of a 4096^2 step)
-    nprof = steps if r_short(elapsed, steps) else min(steps, 5)
-    ctx.prof_enable(True)
-    run(nprof)
-    ctx.sync()
-    prof = ctx.prof_report()
-    ctx.prof_enable(False)
-    dist.barrier()
+    if dump is not None:
+        dump(st, dec, ng, dts)
+    prof, nprof = {}, 0
+    if profile:
+        # the kernels' own durations: more steps with the library's HIP events around every
+        # launch, OUTSIDE the timed region (the events cost ~4 us per launch: nothing against the
+        # 9.5 ms kernel of the headline, 2-7 % of a 4096^2 step)
+        nprof = steps if r_short(elapsed, steps) else min(steps, 5)
+        ctx.prof_enable(True)
+        run(nprof)
+        ctx.sync()
+        prof = ctx.prof_report()
+        ctx.prof_enable(False)
+        dist.barrier()
     res = {"elapsed": elapsed, "cells": float(nx) * ny, "prof": prof, "event_ms": ev_ms,
            "t": pol.t, "dt": pol.dt_old, "local_cells": float(dec.nx_local) * ny, "steps": steps,
            "rows_local": dec.nx_local,
@@ -971,6 +991,61 @@ def cpu_baseline_sedov(sample_nx, max_seconds=12.0):
                       f"NumPy/numba (SURVEY 8(d))"}
 
 
+DUMP_SEED = 20261016
+DUMP_WINDOW = 768           # centre window: 768^2 cells x 4 doubles = 18.9 MB
+DUMP_ROWS, DUMP_COLS = 192, 4096    # seeded sample: 192 x 4096 cells x 4 doubles = 25.2 MB
+
+
+def dump_selection(nx, ny):
+    """the cells dump_outputs() writes: the interior rows and columns (0-based, sorted) of the
+    centre window and of the seeded sample; a function of the grid size alone"""
+    w = min(DUMP_WINDOW, nx), min(DUMP_WINDOW, ny)
+    rng = np.random.default_rng(DUMP_SEED)
+    rows = np.sort(rng.choice(nx, size=min(DUMP_ROWS, nx), replace=False))
+    cols = np.sort(rng.choice(ny, size=min(DUMP_COLS, ny), replace=False))
+    return (np.arange((nx - w[0]) // 2, (nx - w[0]) // 2 + w[0]),
+            np.arange((ny - w[1]) // 2, (ny - w[1]) // 2 + w[1]), rows, cols)
+
+
+def dump_outputs(path, dist, st, dec, ng, ny, dts):
+    """--dump-outputs: what the timed steps computed, as a caller of the stepping path gets it
+    (the conserved state after the last step and the dt of each step), to path/<name>.npy:
+      dt.npy            (steps,) float64: the time step of every timed step
+      state_center.npy  (w, w, 4) float64: density, energy, x-momentum, y-momentum of the
+                        interior window of up to 768^2 cells around the grid's centre (the blast)
+      state_sample.npy  (r, c, 4) float64: the same at the crossings of up to 192 rows and 4096
+                        columns of the interior, drawn with a fixed seed (dump_selection)
+    Under 64 MB in all at any grid size.  A decomposed run gathers its ranks' rows on rank 0:
+    the files are those of the single-domain run."""
+    wr, wc, sr, sc = dump_selection(dec.nx, ny)
+    mine = {}
+    for name, rows, cols in (("state_center", wr, wc), ("state_sample", sr, sc)):
+        own = rows[(rows >= dec.i0) & (rows < dec.i0 + dec.nx_local)]
+        part = np.empty((len(own), len(cols), st.nvar))
+        k = 0
+        while k < len(own):          # runs of consecutive rows, <= 64 rows on the host at a time
+            n = 1
+            while n < 64 and k + n < len(own) and own[k + n] == own[k] + n:
+                n += 1
+            got = st.download_rows(int(own[k]) - dec.i0 + ng, n)
+            part[k:k + n] = got[:, cols + ng, :]
+            k += n
+        mine[name] = (own, part)
+    parts = [mine]
+    if dist.td is not None:
+        parts = [None] * dist.world if dist.rank == 0 else None
+        dist.td.gather_object(mine, parts, dst=0)
+    if dist.rank != 0:
+        return
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "dt.npy"), np.asarray(dts, dtype=np.float64))
+    for name, rows in (("state_center", wr), ("state_sample", sr)):
+        own = np.concatenate([p[name][0] for p in parts])
+        a = np.concatenate([p[name][1] for p in parts])
+        assert np.array_equal(own, rows), name
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 LINE_LIMIT = 4096       # the driver keeps a bounded tail of stdout: the ONE line must fit it whole
 
 
@@ -1248,11 +1323,15 @@ def main():
         os.write(json_fd, (json.dumps(_rnd(o), separators=(",", ":")) + "\n").encode())
         return
 
-    # a decomposed run is checked against the single-domain one BEFORE anything is timed,
-    # unless the caller says --no-scale-check
-    do_check = world > 1 and args.scale_check is not False
+    # with --full, a decomposed run is checked against the single-domain one BEFORE anything is
+    # timed, unless the caller says --no-scale-check (--scale-check: also without --full)
+    do_check = world > 1 and (args.scale_check or (args.full and args.scale_check is not False))
     check = scale_check(args, dist, ctx, device, defaults) if do_check else None
-    r = bench_sedov(args, dist, ctx, device, defaults)
+    dump = None
+    if args.dump_outputs:
+        def dump(st, dec, ng, dts):
+            dump_outputs(args.dump_outputs, dist, st, dec, ng, args.nx, dts)
+    r = bench_sedov(args, dist, ctx, device, defaults, profile=args.full, dump=dump)
     value = r["cells"] * args.steps / r["elapsed"]
     out = {
         "metric": "cell-updates/s", "value": value, "unit": "cell-updates/s",
@@ -1283,6 +1362,12 @@ def main():
         out["config"]["scale_check"] = check
     if dist.oversubscribed:
         out["config"]["oversubscribed"] = "several ranks share one GPU (debug run, not a result)"
+    if not args.full:
+        # the headline alone: no side file, nothing measured after the timed steps
+        if dist.rank == 0:
+            os.write(json_fd, (compact_line(out) + "\n").encode())
+        dist.barrier()
+        return
     # every rank's own figures (kernel time, what the main stream waited for), gathered: a
     # first hardware scaling line must say WHERE the time of a step went
     geo = device.comp_wave_geometry(r["rows_local"], args.nx, 4, ctx.info().get("compute_units", 0))

@@ -4,8 +4,9 @@ path").  Pinned three ways:
     generator: oracle/gen_h5_fixture.py) and reproduces its content exactly;
   * write -> read round trip of pyro's output layout and the corner cases;
   * where an interpreter with h5py exists (this container: /opt/conda/bin/python3.9)
-    a file written by h5pure is read back with the real h5py, and pyro's own
-    shipped benchmark files are read by h5pure (where /root/reference exists).
+    a file written by h5pure is read back with the real h5py;
+  * two of pyro's own shipped benchmark files (tests/golden/smooth_0040.h5,
+    sod_x_0076.h5) are read by h5pure.
 """
 import json
 import os
@@ -20,7 +21,6 @@ from pyro2_amd.util import h5pure
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLD = os.path.join(HERE, "golden")
 CONDA = "/opt/conda/bin/python3.9"
-REF = "/root/reference/pyro"
 
 
 def _eq(a, b):
@@ -161,18 +161,18 @@ print(json.dumps(out))
         assert len(f["empty"]) == 20 and f["misc"].attrs["more"] == 5
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present")
 def test_reads_pyro_shipped_benchmarks():
-    """the regression benchmarks pyro ships (pyro/*/tests/*.h5) open through
+    """the regression benchmarks pyro ships (pyro/advection/tests/smooth_0040.h5 and
+    pyro/compressible/tests/sod_x_0076.h5, stored unchanged under tests/golden/) open through
     io_pyro.read without h5py, like `pyro_sim.py --compare_benchmark` does"""
     os.environ["PYRO_H5PURE"] = "1"
     try:
         from pyro2_amd.util import io_pyro
-        s = io_pyro.read(REF + "/advection/tests/smooth_0040")
+        s = io_pyro.read(GOLD + "/smooth_0040")
         assert s.n == 40 and s.cc_data.grid.nx == 32 and s.cc_data.names == ["density"]
         d = s.cc_data.get_var("density").v()
         assert d.shape == (32, 32) and 1.0 < d.max() < 2.0
-        s = io_pyro.read(REF + "/compressible/tests/sod_x_0076.h5")
+        s = io_pyro.read(GOLD + "/sod_x_0076.h5")
         assert s.n == 76 and s.cc_data.get_aux("gamma") == 1.4
         assert s.cc_data.BCs["y-momentum"].ylb == "reflect-odd"
     finally:

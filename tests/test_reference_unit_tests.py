@@ -47,7 +47,9 @@ def test_reference_unit_tests_pass_on_the_alias_package(tmp_path):
     files = [os.path.join(REF, f) for f, _ in REF_TESTS]
     for f in files:
         assert "pyro2_amd" not in open(f).read()          # the reference's files, untouched
-    env = dict(os.environ, PYTHONPATH=os.pathsep.join([str(tmp_path), ROOT]), MPLBACKEND="Agg")
+    # (no bytecode caches: the reference's test directories are not this suite's to write into)
+    env = dict(os.environ, PYTHONPATH=os.pathsep.join([str(tmp_path), ROOT]), MPLBACKEND="Agg",
+               PYTHONDONTWRITEBYTECODE="1")
     r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-p", "ref_unit_plugin", "-p",
                         "no:cacheprovider", f"--rootdir={tmp_path}"] + files, cwd=tmp_path, env=env,
                        capture_output=True, text=True, timeout=1500)

@@ -7,7 +7,7 @@
 # gpurun_out/profiles_<tag>/traffic.json:
 #   <tag>_provenance.json                commit, box (host, GPU id), date, ROCm -- every JSON below carries it too
 #   <tag>_pytest_gpu.txt                 pytest -m gpu summary line (TESTS=0 skips)
-#   <tag>_bench_line.json, <tag>_bench_default.json   python bench.py --gpus 1 --steps 20 --warmup 5 (the driver's command): its ONE stdout
+#   <tag>_bench_line.json, <tag>_bench_default.json   python bench.py --gpus 1 --steps 20 --warmup 5 --full: its ONE stdout
 #                                        line and the full record (ONLY=bench: just these, with <tag>_bench_default_provenance.json)
 #   <tag>_{swe4096,rk4096,sph2048}_{kernel_stats.csv,pmc.json}   the SURVEY 8(f4) one-launch kernels (tools/pmc_leg.sh)
 #   <tag>_xcdbar_probe.txt               barrier confined to one XCD vs chip-wide (tools/xcdbar_probe.hip, gridbar_probe.hip)
@@ -42,7 +42,7 @@ stats() {   # stats <name> <command...>: rocprofv3 kernel statistics of a comman
 if [ "${ONLY:-}" = "bench" ]; then
   # only the driver's command again, at a later commit than the rest of the set: its own stamp
   mv $P/${TAG}_provenance.json $P/${TAG}_bench_default_provenance.json
-  ( time timeout 600 python bench.py < /dev/null > $P/${TAG}_bench_line.json ) 2> $O/bench_${TAG}.err
+  ( time timeout 600 python bench.py --full < /dev/null > $P/${TAG}_bench_line.json ) 2> $O/bench_${TAG}.err
   cp $O/bench_full.json $P/${TAG}_bench_default.json
   head -c 300 $P/${TAG}_bench_line.json; echo; tail -3 $O/bench_${TAG}.err
   exit 0
@@ -53,7 +53,7 @@ if [ "${TESTS:-1}" = "1" ]; then
 fi
 # the driver's command: the ONE compact stdout line (<tag>_bench_line.json) and the full record it
 # points at (gpurun_out/bench_full.json -> <tag>_bench_default.json, the name of the earlier rounds)
-( time timeout 1500 python bench.py --gpus 1 --steps 20 --warmup 5 > $P/${TAG}_bench_line.json ) 2> $O/bench_${TAG}.err
+( time timeout 1500 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $P/${TAG}_bench_line.json ) 2> $O/bench_${TAG}.err
 cp $O/bench_full.json $P/${TAG}_bench_default.json
 wc -c $P/${TAG}_bench_line.json; head -c 400 $P/${TAG}_bench_line.json; echo; grep -E "^real" $O/bench_${TAG}.err
 B="python $R/bench.py --steps 10 --warmup 3 --no-also --no-cpu-baseline"
