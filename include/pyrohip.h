@@ -522,6 +522,30 @@ int pyrohip_comp_rk_evolve(pyrohip_state *y, const pyrohip_comp_params *p,
 int pyrohip_state_lincomb(pyrohip_state *dst, const pyrohip_state *src,
                           const pyrohip_state *k, const double *coef, int ncoef);
 
+/* ---- compressible_fv4 / compressible_sdc (4th order, McCorquodale & Colella 2011) ----
+   Simulation.substep (pyro/compressible_fv4/simulation.py:21-66) with fluxes.fluxes
+   (compressible_fv4/fluxes.py:46-223), mesh/fourth_order.states (:8-235) and riemann_prim
+   (compressible/riemann.py:314-574): k = -div F + <S> - sponge of the cell-average state y
+   (ghost cells filled, ng = 4, Cartesian; the density floor is applied to y in place) into
+   planes 4*slot .. 4*slot+3 of k.  S: gravity and the heating profile on the cell centres,
+   brought back to averages (:28-44).  p->riemann and p->limiter are ignored (the reference
+   calls the CGF solver on primitive states with its own limiter).  PYROHIP_ERR_STATE: the
+   averages or the masked centres fail cons_to_prim's assert (compressible/simulation.py:
+   68-71); k is left as it was.                                                             */
+int pyrohip_comp_fv4_rhs(pyrohip_state *y, const pyrohip_comp_params *p,
+                         pyrohip_state *k, int slot);
+/* FV2d.from_centers (pyro/mesh/fv.py:31-39) of variable var (-1: all, in order): the ghost
+   cells are filled (pyrohip_fill_bc), then the interior becomes a + dx^2 lap(a) / 24.     */
+int pyrohip_state_from_centers(pyrohip_state *s, int var, double dx, double dy);
+/* The node update of compressible_sdc.Simulation.evolve (pyro/compressible_sdc/
+   simulation.py:85-87 with sdc_integral :20-36): on the interior
+     dst = src + dt/2 (k[slot_new] - k[slot_old]) + dt/24 (cq[0] k[sq[0]] + cq[1] k[sq[1]] + cq[2] k[sq[2]])
+   in the reference's order (the integral first).  k holds slots of dst->nvar planes.  The
+   ghost cells of dst are not touched: fill them afterwards (:90).                          */
+int pyrohip_comp_sdc_update(pyrohip_state *dst, const pyrohip_state *src,
+                            const pyrohip_state *k, int slot_new, int slot_old,
+                            const int *slots_q, const double *cq, double dt);
+
 /* ---- shallow water (pyro/swe) -------------------------
    state: 4 variables height, x-momentum, y-momentum, fuel (ng >= 4).
    riemann: 0 Roe, 1 HLLC (swe/interface.py:216-554).

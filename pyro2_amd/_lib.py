@@ -115,6 +115,9 @@ _PROTOS = {
     "pyrohip_comp_rk_evolve": [_VP, C.POINTER(CompParams), _VP, C.c_int, _DP, _DP, C.c_double,
                                C.POINTER(DtPolicyC), C.c_int, C.POINTER(C.c_int), _DP],
     "pyrohip_state_lincomb": [_VP, _VP, _VP, _DP, C.c_int],
+    "pyrohip_comp_fv4_rhs": [_VP, C.POINTER(CompParams), _VP, C.c_int],
+    "pyrohip_state_from_centers": [_VP, C.c_int, C.c_double, C.c_double],
+    "pyrohip_comp_sdc_update": [_VP, _VP, _VP, C.c_int, C.c_int, C.POINTER(C.c_int), _DP, C.c_double],
     "pyrohip_swe_dt": [_VP, C.c_double, C.c_double, C.c_double, C.c_double, _DP],
     "pyrohip_swe_step": [_VP, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_double],
     "pyrohip_swe_step_ks": [_VP, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, C.c_int],

@@ -48,6 +48,9 @@ UNITS = [
     # (no -fno-honor-nans here: ghost faces of an oddly reflected density hold NaN roots that the
     # fmin / fmax floors of the CGF solver are there to absorb)
     ("comp_sph_wave.hip", "sphw_fast", ["-ffp-contract=fast", "-DPYRO_FAST=1"]),
+    # the 4th-order method-of-lines right-hand side (compressible_fv4 / compressible_sdc)
+    ("comp_fv4.hip", "fv4_exact", ["-ffp-contract=off", "-DPYRO_FAST=0"]),
+    ("comp_fv4.hip", "fv4_fast", ["-ffp-contract=fast", "-DPYRO_FAST=1"]),
     ("comp_api.hip", "comp_api", ["-ffp-contract=off"]),
     ("multigrid.hip", "multigrid", ["-ffp-contract=off"]),
     ("mg_march.hip", "mg_march", ["-ffp-contract=off", "-mllvm", "-pragma-unroll-threshold=200000"]),

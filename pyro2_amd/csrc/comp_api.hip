@@ -29,14 +29,19 @@ int comp_sponge(pyrohip_state *, const pyrohip_comp_params *, double);
 int comp_source_correct(pyrohip_state *, const pyrohip_comp_params *, double);
 int comp_rk_dt(pyrohip_state *, const pyrohip_comp_params *, double, double *);
 int comp_rk_rhs(pyrohip_state *, const pyrohip_comp_params *, pyrohip_state *, int);
+int comp_fv4_rhs(pyrohip_state *, const pyrohip_comp_params *, pyrohip_state *, int);
 int comp_rk_rhs_wave(pyrohip_state *, const pyrohip_comp_params *, pyrohip_state *, int);
 int comp_rk_step_wave(pyrohip_state *, const pyrohip_comp_params *, pyrohip_state *, int, const double *,
                       const double *, double, const StepScalars *, const double **);
 int comp_rk_cfl_min_device(pyrohip_state *, const pyrohip_comp_params *, const double **);
 int comp_wave_geometry(int, int, int, int, int, int *);
+int state_from_centers(pyrohip_state *, int, double, double, double *);
+int comp_sdc_update(pyrohip_state *, const pyrohip_state *, const pyrohip_state *, int, int, const int *,
+                    const double *, double);
 }
 namespace fastm {
 int comp_rk_rhs(pyrohip_state *, const pyrohip_comp_params *, pyrohip_state *, int);
+int comp_fv4_rhs(pyrohip_state *, const pyrohip_comp_params *, pyrohip_state *, int);
 int comp_rk_rhs_wave(pyrohip_state *, const pyrohip_comp_params *, pyrohip_state *, int);
 int comp_rk_step_wave(pyrohip_state *, const pyrohip_comp_params *, pyrohip_state *, int, const double *,
                       const double *, double, const StepScalars *, const double **);
@@ -927,6 +932,63 @@ int pyrohip_comp_rk_rhs(pyrohip_state *y, const pyrohip_comp_params *p, pyrohip_
     if (wave)
         return p->fast_math ? fastm::comp_rk_rhs_wave(y, p, k, slot) : exact::comp_rk_rhs_wave(y, p, k, slot);
     return p->fast_math ? fastm::comp_rk_rhs(y, p, k, slot) : exact::comp_rk_rhs(y, p, k, slot);
+}
+
+// compressible_fv4 (csrc/comp_fv4.hip): the 4th-order right-hand side of a ghost-filled state
+int pyrohip_comp_fv4_rhs(pyrohip_state *y, const pyrohip_comp_params *p, pyrohip_state *k, int slot)
+{
+    PYRO_TRY(check_comp(y, p));
+    PYRO_REQUIRE(y->g.ng == 4, "compressible_fv4 needs ng = 4 (the reference's grid)");
+    PYRO_REQUIRE(!y->sph, "compressible_fv4 has no SphericalPolar geometry terms");
+    PYRO_REQUIRE(k && k->ctx == y->ctx, "k state missing or on another context");
+    PYRO_REQUIRE(k->g.nx == y->g.nx && k->g.ny == y->g.ny && k->g.ng == y->g.ng,
+                 "k state must have the geometry of the stage state");
+    PYRO_REQUIRE(slot >= 0 && 4 * (slot + 1) <= k->nvar, "slot outside the k state");
+    if (p->do_sponge)
+        PYRO_REQUIRE(p->sponge_rho_begin > p->sponge_rho_full,
+                     "sponge_rho_begin must exceed sponge_rho_full (simulation.py:172)");
+    return p->fast_math ? fastm::comp_fv4_rhs(y, p, k, slot) : exact::comp_fv4_rhs(y, p, k, slot);
+}
+
+// fv.py:31-39 for variable `var` (-1: every variable, in order): fill its ghost cells, then
+// a + dx^2 lap(a) / 24 on the interior
+int pyrohip_state_from_centers(pyrohip_state *s, int var, double dx, double dy)
+{
+    PYRO_REQUIRE(s, "NULL state");
+    PYRO_REQUIRE(var >= -1 && var < s->nvar, "variable index out of range");
+    PYRO_REQUIRE(dx > 0 && dy > 0, "bad dx/dy");
+    PYRO_REQUIRE(s->g.ng >= 1, "from_centers needs ghost cells");
+    double *scratch = nullptr;
+    PYRO_CHECK_HIP(hipMalloc((void **)&scratch, s->g.plane * sizeof(double)));
+    int rc = 0;
+    for (int n = (var < 0 ? 0 : var); n < (var < 0 ? s->nvar : var + 1) && rc == 0; n++) {
+        rc = pyrohip_fill_bc(s, n);
+        if (rc == 0) rc = exact::state_from_centers(s, n, dx, dy, scratch);
+    }
+    if (rc == 0) PYRO_CHECK_HIP(hipStreamSynchronize(s->ctx->stream));
+    (void)hipFree(scratch);
+    s->next_cfl_min = -1.0;
+    s->ghost_by_rules = false;
+    return rc;
+}
+
+// compressible_sdc/simulation.py:85-87: dst <- src + dt/2 (k_new - k_old) + dt/24 sum_q cq[q] k_q
+int pyrohip_comp_sdc_update(pyrohip_state *dst, const pyrohip_state *src, const pyrohip_state *k,
+                            int slot_new, int slot_old, const int *slots_q, const double *cq, double dt)
+{
+    PYRO_REQUIRE(dst && src && k && slots_q && cq, "NULL argument");
+    PYRO_REQUIRE(dst->nvar == src->nvar && dst->g.plane == src->g.plane && dst->g.plane == k->g.plane &&
+                     dst->g.nx == k->g.nx && dst->g.ny == k->g.ny,
+                 "geometries differ");
+    PYRO_REQUIRE(dst->ctx == src->ctx && dst->ctx == k->ctx, "states live on different contexts");
+    const int nslots = k->nvar / dst->nvar;
+    PYRO_REQUIRE(slot_new >= 0 && slot_new < nslots && slot_old >= 0 && slot_old < nslots,
+                 "slot outside the k state");
+    for (int q = 0; q < 3; q++) PYRO_REQUIRE(slots_q[q] >= 0 && slots_q[q] < nslots, "slot outside the k state");
+    PYRO_TRY(exact::comp_sdc_update(dst, src, k, slot_new, slot_old, slots_q, cq, dt));
+    dst->next_cfl_min = -1.0;
+    dst->ghost_by_rules = false;
+    return 0;
 }
 
 int pyrohip_comp_stage_dump(pyrohip_state *s, int stage_id, double *out)

@@ -851,6 +851,86 @@ __device__ __forceinline__ ConsN hllc_lm_flux(const ConsN &Ul, const ConsN &Ur, 
     return cons_flux_n(Ul, gamma, normal_is_x);
 }
 
+// The Colella-Glaz-Ferguson solver's star region (riemann.py:60-99, riemann_prim
+// :402-439): Lagrangian and ordinary sound speeds, p*, u*, rho* on both sides.
+// ril / rir: 1 / rho of the side (fast build only).
+struct CgfStar { double c_l, c_r, pstar, ustar, rhostar_l, rhostar_r; };
+__device__ __forceinline__ CgfStar cgf_star(double rho_l, double un_l, double p_l, double rho_r,
+                                            double un_r, double p_r, double gamma, double ril,
+                                            double rir)
+{
+    const double smallc = 1.e-10, smallrho = 1.e-10, smallp = 1.e-10;
+    CgfStar s;
+    const double W_l = fmax(smallrho * smallc, psqrt(gamma * p_l * rho_l));
+    const double W_r = fmax(smallrho * smallc, psqrt(gamma * p_r * rho_r));
+    s.c_l = fmax(smallc, psqrt(pdivr(gamma * p_l, rho_l, ril)));
+    s.c_r = fmax(smallc, psqrt(pdivr(gamma * p_r, rho_r, rir)));
+    const double rW = PYRO_FAST ? prcp(W_l + W_r) : 0.0;
+    double pstar = pdivr(W_l * p_r + W_r * p_l + W_l * W_r * (un_l - un_r), W_l + W_r, rW);
+    s.pstar = fmax(pstar, smallp);
+    s.ustar = pdivr(W_l * un_l + W_r * un_r + (p_l - p_r), W_l + W_r, rW);
+    s.rhostar_l = rho_l + pdiv(s.pstar - p_l, s.c_l * s.c_l);
+    s.rhostar_r = rho_r + pdiv(s.pstar - p_r, s.c_r * s.c_r);
+    return s;
+}
+
+// ... and which state the face sees (riemann.py:113-245, riemann_prim :443-551): the wave
+// pattern both variants share.  CGF_FAN_*: a rarefaction spans the face, alpha is the weight
+// of the star state.
+enum { CGF_L = 0, CGF_STAR_L, CGF_FAN_L, CGF_R, CGF_STAR_R, CGF_FAN_R, CGF_ZERO };
+__device__ __forceinline__ int cgf_pick(const CgfStar &s, double un_l, double un_r, double p_l,
+                                        double p_r, double gamma, double &alpha)
+{
+    const double smallc = 1.e-10;
+    if (s.ustar > 0.0) {
+        const double cstar_l = fmax(smallc, psqrt(pdiv(gamma * s.pstar, s.rhostar_l)));
+        const double lambda_l = un_l - s.c_l, lambdastar_l = s.ustar - cstar_l;
+        if (s.pstar > p_l) {
+            const double sigma = (lambda_l + lambdastar_l) / 2.0;
+            return (sigma > 0.0) ? CGF_L : CGF_STAR_L;
+        }
+        if (lambda_l < 0.0 && lambdastar_l < 0.0) return CGF_STAR_L;
+        if (lambda_l > 0.0 && lambdastar_l > 0.0) return CGF_L;
+        alpha = pdiv(lambda_l, lambda_l - lambdastar_l);
+        return CGF_FAN_L;
+    }
+    if (s.ustar < 0) {
+        const double cstar_r = fmax(smallc, psqrt(pdiv(gamma * s.pstar, s.rhostar_r)));
+        const double lambda_r = un_r + s.c_r, lambdastar_r = s.ustar + cstar_r;
+        if (s.pstar > p_r) {
+            const double sigma = (lambda_r + lambdastar_r) / 2.0;
+            return (sigma > 0.0) ? CGF_STAR_R : CGF_R;
+        }
+        if (lambda_r < 0.0 && lambdastar_r < 0.0) return CGF_R;
+        if (lambda_r > 0.0 && lambdastar_r > 0.0) return CGF_STAR_R;
+        alpha = pdiv(lambda_r, lambda_r - lambdastar_r);
+        return CGF_FAN_R;
+    }
+    return CGF_ZERO;
+}
+
+// the state on the face from the pattern: x = (rho, un, e) with e the third variable of the
+// variant (rho e for conserved input, p for primitive input)
+struct CgfSel { double rho, un, e; };
+__device__ __forceinline__ CgfSel cgf_select(int w, double alpha, const CgfStar &s, double rho_l,
+                                             double un_l, double e_l, double estar_l, double rho_r,
+                                             double un_r, double e_r, double estar_r)
+{
+    switch (w) {
+    case CGF_L: return CgfSel{rho_l, un_l, e_l};
+    case CGF_STAR_L: return CgfSel{s.rhostar_l, s.ustar, estar_l};
+    case CGF_FAN_L:
+        return CgfSel{alpha * s.rhostar_l + (1.0 - alpha) * rho_l, alpha * s.ustar + (1.0 - alpha) * un_l,
+                      alpha * estar_l + (1.0 - alpha) * e_l};
+    case CGF_R: return CgfSel{rho_r, un_r, e_r};
+    case CGF_STAR_R: return CgfSel{s.rhostar_r, s.ustar, estar_r};
+    case CGF_FAN_R:
+        return CgfSel{alpha * s.rhostar_r + (1.0 - alpha) * rho_r, alpha * s.ustar + (1.0 - alpha) * un_r,
+                      alpha * estar_r + (1.0 - alpha) * e_r};
+    default: return CgfSel{0.5 * (s.rhostar_l + s.rhostar_r), s.ustar, 0.0};
+    }
+}
+
 // Two-shock Colella-Glaz-Ferguson solver on one face, riemann.py:8-310,
 // followed by consFlux of the resulting interface state (riemann_flux
 // :1083-1090), in the (normal, transverse) frame.  wall_zero: this is the
@@ -859,7 +939,7 @@ __device__ __forceinline__ ConsN hllc_lm_flux(const ConsN &Ul, const ConsN &Ur, 
 __device__ __forceinline__ ConsN cgf_state(const ConsN &Ul, const ConsN &Ur, double gamma,
                                            bool wall_zero)
 {
-    const double smallc = 1.e-10, smallrho = 1.e-10, smallp = 1.e-10;
+    const double smallp = 1.e-10;
     const double rho_l = Ul.d;
     const double ril = PYRO_FAST ? prcp(rho_l) : 0.0;
     const double un_l = pdivr(Ul.mn, rho_l, ril), ut_l = pdivr(Ul.mt, rho_l, ril);
@@ -870,63 +950,23 @@ __device__ __forceinline__ ConsN cgf_state(const ConsN &Ul, const ConsN &Ur, dou
     const double un_r = pdivr(Ur.mn, rho_r, rir), ut_r = pdivr(Ur.mt, rho_r, rir);
     const double rhoe_r = Ur.E - 0.5 * rho_r * (un_r * un_r + ut_r * ut_r);
     const double p_r = fmax(rhoe_r * (gamma - 1.0), smallp);
-    const double W_l = fmax(smallrho * smallc, psqrt(gamma * p_l * rho_l));
-    const double W_r = fmax(smallrho * smallc, psqrt(gamma * p_r * rho_r));
-    const double c_l = fmax(smallc, psqrt(pdivr(gamma * p_l, rho_l, ril)));
-    const double c_r = fmax(smallc, psqrt(pdivr(gamma * p_r, rho_r, rir)));
-    const double rW = PYRO_FAST ? prcp(W_l + W_r) : 0.0;
-    double pstar = pdivr(W_l * p_r + W_r * p_l + W_l * W_r * (un_l - un_r), W_l + W_r, rW);
-    pstar = fmax(pstar, smallp);
-    const double ustar = pdivr(W_l * un_l + W_r * un_r + (p_l - p_r), W_l + W_r, rW);
-    const double rhostar_l = rho_l + pdiv(pstar - p_l, c_l * c_l);
-    const double rhostar_r = rho_r + pdiv(pstar - p_r, c_r * c_r);
+    const CgfStar s = cgf_star(rho_l, un_l, p_l, rho_r, un_r, p_r, gamma, ril, rir);
     const double rhoestar_l =
-        rhoe_l + pdiv((pstar - p_l) * (pdivr(rhoe_l, rho_l, ril) + pdivr(p_l, rho_l, ril)), c_l * c_l);
+        rhoe_l + pdiv((s.pstar - p_l) * (pdivr(rhoe_l, rho_l, ril) + pdivr(p_l, rho_l, ril)), s.c_l * s.c_l);
     const double rhoestar_r =
-        rhoe_r + pdiv((pstar - p_r) * (pdivr(rhoe_r, rho_r, rir) + pdivr(p_r, rho_r, rir)), c_r * c_r);
-    double rho_s, un_s, ut_s, rhoe_s;
-    if (ustar > 0.0) {
-        ut_s = ut_l;
-        const double cstar_l = fmax(smallc, psqrt(pdiv(gamma * pstar, rhostar_l)));
-        const double lambda_l = un_l - c_l, lambdastar_l = ustar - cstar_l;
-        if (pstar > p_l) {
-            const double sigma = (lambda_l + lambdastar_l) / 2.0;
-            if (sigma > 0.0) { rho_s = rho_l; un_s = un_l; rhoe_s = rhoe_l; }
-            else { rho_s = rhostar_l; un_s = ustar; rhoe_s = rhoestar_l; }
-        } else if (lambda_l < 0.0 && lambdastar_l < 0.0) {
-            rho_s = rhostar_l; un_s = ustar; rhoe_s = rhoestar_l;
-        } else if (lambda_l > 0.0 && lambdastar_l > 0.0) {
-            rho_s = rho_l; un_s = un_l; rhoe_s = rhoe_l;
-        } else {
-            const double alpha = pdiv(lambda_l, lambda_l - lambdastar_l);
-            rho_s = alpha * rhostar_l + (1.0 - alpha) * rho_l;
-            un_s = alpha * ustar + (1.0 - alpha) * un_l;
-            rhoe_s = alpha * rhoestar_l + (1.0 - alpha) * rhoe_l;
-        }
-    } else if (ustar < 0) {
-        ut_s = ut_r;
-        const double cstar_r = fmax(smallc, psqrt(pdiv(gamma * pstar, rhostar_r)));
-        const double lambda_r = un_r + c_r, lambdastar_r = ustar + cstar_r;
-        if (pstar > p_r) {
-            const double sigma = (lambda_r + lambdastar_r) / 2.0;
-            if (sigma > 0.0) { rho_s = rhostar_r; un_s = ustar; rhoe_s = rhoestar_r; }
-            else { rho_s = rho_r; un_s = un_r; rhoe_s = rhoe_r; }
-        } else if (lambda_r < 0.0 && lambdastar_r < 0.0) {
-            rho_s = rho_r; un_s = un_r; rhoe_s = rhoe_r;
-        } else if (lambda_r > 0.0 && lambdastar_r > 0.0) {
-            rho_s = rhostar_r; un_s = ustar; rhoe_s = rhoestar_r;
-        } else {
-            const double alpha = pdiv(lambda_r, lambda_r - lambdastar_r);
-            rho_s = alpha * rhostar_r + (1.0 - alpha) * rho_r;
-            un_s = alpha * ustar + (1.0 - alpha) * un_r;
-            rhoe_s = alpha * rhoestar_r + (1.0 - alpha) * rhoe_r;
-        }
-    } else {   // ustar == 0
-        rho_s = 0.5 * (rhostar_l + rhostar_r);
-        un_s = ustar;
+        rhoe_r + pdiv((s.pstar - p_r) * (pdivr(rhoe_r, rho_r, rir) + pdivr(p_r, rho_r, rir)), s.c_r * s.c_r);
+    double alpha = 0.0;
+    const int w = cgf_pick(s, un_l, un_r, p_l, p_r, gamma, alpha);
+    CgfSel x = cgf_select(w, alpha, s, rho_l, un_l, rhoe_l, rhoestar_l, rho_r, un_r, rhoe_r, rhoestar_r);
+    double ut_s;
+    if (w == CGF_ZERO) {
         ut_s = 0.5 * (ut_l + ut_r);
-        rhoe_s = 0.5 * (rhoestar_l + rhoestar_r);
+        x.e = 0.5 * (rhoestar_l + rhoestar_r);
+    } else {
+        ut_s = (w < CGF_R) ? ut_l : ut_r;
     }
+    const double rho_s = x.rho, rhoe_s = x.e;
+    double un_s = x.un;
     if (wall_zero) un_s = 0.0;
     ConsN Uo;
     Uo.d = rho_s;
@@ -934,6 +974,33 @@ __device__ __forceinline__ ConsN cgf_state(const ConsN &Ul, const ConsN &Ur, dou
     Uo.mt = rho_s * ut_s;
     Uo.E = rhoe_s + 0.5 * rho_s * (un_s * un_s + ut_s * ut_s);
     return Uo;
+}
+
+// The same solver on PRIMITIVE face states, returning the primitive interface state
+// (riemann_prim, riemann.py:314-574; the 4th-order solver calls it with no solid walls).
+// (rho, un, ut, p) in the face's (normal, transverse) frame.
+struct PrimN { double r, un, ut, p; };
+__device__ __forceinline__ PrimN cgf_prim(const PrimN &ql, const PrimN &qr, double gamma)
+{
+    const double smallrho = 1.e-10, smallp = 1.e-10;
+    const double p_l = fmax(ql.p, smallp), p_r = fmax(qr.p, smallp);
+    const double rho_l = fmax(smallrho, ql.r), rho_r = fmax(smallrho, qr.r);
+    const double ril = PYRO_FAST ? prcp(rho_l) : 0.0, rir = PYRO_FAST ? prcp(rho_r) : 0.0;
+    const CgfStar s = cgf_star(rho_l, ql.un, p_l, rho_r, qr.un, p_r, gamma, ril, rir);
+    double alpha = 0.0;
+    const int w = cgf_pick(s, ql.un, qr.un, p_l, p_r, gamma, alpha);
+    CgfSel x = cgf_select(w, alpha, s, rho_l, ql.un, p_l, s.pstar, rho_r, qr.un, p_r, s.pstar);
+    PrimN o;
+    if (w == CGF_ZERO) {
+        o.ut = 0.5 * (ql.ut + qr.ut);
+        x.e = s.pstar;
+    } else {
+        o.ut = (w < CGF_R) ? ql.ut : qr.ut;
+    }
+    o.r = x.rho;
+    o.un = x.un;
+    o.p = x.e;
+    return o;
 }
 __device__ __forceinline__ ConsN cgf_flux(const ConsN &Ul, const ConsN &Ur, double gamma,
                                           bool normal_is_x, bool wall_zero)

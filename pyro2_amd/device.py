@@ -238,6 +238,26 @@ class DeviceState:
             check(self._l.pyrohip_comp_rk_dt(self.h, C.byref(params), float(cfl), C.byref(out)))
         return out.value
 
+    # ---- compressible_fv4 / compressible_sdc ---------------------------------------
+    def comp_fv4_rhs(self, params, kstate, slot):
+        """the 4th-order k = -div F + <S> of this (ghost-filled, cell-average) state into
+        slot `slot` of kstate (pyrohip_comp_fv4_rhs)"""
+        with self.ctx.lock:
+            check(self._l.pyrohip_comp_fv4_rhs(self.h, C.byref(params), kstate.h, int(slot)))
+
+    def from_centers(self, n, dx, dy):
+        """ghost fill of variable n (-1: all), then interior a + dx^2 lap(a) / 24"""
+        with self.ctx.lock:
+            check(self._l.pyrohip_state_from_centers(self.h, int(n), float(dx), float(dy)))
+
+    def comp_sdc_update(self, src, kstate, slot_new, slot_old, slots_q, cq, dt):
+        """interior: self = src + dt/2 (k_new - k_old) + dt/24 sum_q cq[q] k_q"""
+        sq = (C.c_int * 3)(*[int(x) for x in slots_q])
+        c = np.ascontiguousarray(cq, dtype=np.float64)
+        with self.ctx.lock:
+            check(self._l.pyrohip_comp_sdc_update(self.h, src.h, kstate.h, int(slot_new), int(slot_old),
+                                                  sq, dptr(c), float(dt)))
+
     def lincomb(self, src, kstate, coefs):
         """self <- src (whole array); interior += coefs[s] * k_s in order"""
         c = np.ascontiguousarray(coefs, dtype=np.float64)
