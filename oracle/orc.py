@@ -448,6 +448,24 @@ def comp_rk_rhs(U, P, fluxes=False):
     return (rc, k, Fx, Fy) if fluxes else (rc, k)
 
 
+# ---- compressible_fv4 -------------------------------------------------------
+def fv4_rhs(U, P, fluxes=False, counts=False):
+    """the 4th-order k = -div F + <S> of the ghost-filled state U (qx,qy,4)
+    (compressible_fv4 Simulation.substep); U's interior density is floored in
+    place.  P: comp_params (dx, dy, gamma, use_flattening, z0/z1/delta,
+    small_dens, grav, sponge, heating).  Returns (rc, k[, Fx, Fy][, counts]),
+    counts = (to_centers mask fallbacks, q_avg positivity fallbacks)."""
+    _ck(U)
+    k = np.zeros_like(U)
+    Fx = np.zeros_like(U) if fluxes else None
+    Fy = np.zeros_like(U) if fluxes else None
+    cnt = (C.c_int * 2)()
+    rc = lib().orc_fv4_rhs(_p(U), C.byref(P), _p(k), None if Fx is None else _p(Fx),
+                           None if Fy is None else _p(Fy), cnt)
+    out = (rc, k) + ((Fx, Fy) if fluxes else ())
+    return out + ((cnt[0], cnt[1]),) if counts else out
+
+
 def comp_rk_dt(U, nx, ny, ng, dx, dy, gamma, cfl):
     f = lib().orc_comp_rk_dt
     f.restype = C.c_double

@@ -2900,3 +2900,401 @@ void orc_swe_step(double *U, const orc_swe_params *P, double dt, orc_swe_stages 
     free(Uxl); free(Uxr); free(Uyl); free(Uyr); free(Fx); free(Fy);
 }
 #undef SQ
+
+/* ================================================================== */
+/* compressible_fv4 right-hand side (McCorquodale & Colella 2011)      */
+/*   pyro/compressible_fv4/simulation.py:21-66  Simulation.substep     */
+/*   pyro/compressible_fv4/fluxes.py:12-38      flux_cons              */
+/*   pyro/compressible_fv4/fluxes.py:46-223     fluxes                 */
+/*   pyro/mesh/fourth_order.py:8-235            states                 */
+/*   pyro/compressible/riemann.py:314-574       riemann_prim (CGF)     */
+/*   pyro/mesh/fv.py:18-29                      to_centers             */
+/* Whole arrays, zero outside the region the reference writes.  U is   */
+/* the ghost-filled stage state; clean_state floors its interior       */
+/* density in place (compressible/simulation.py:452-456: U.v() only).   */
+/* k: interior written, zero elsewhere.  o_Fx / o_Fy (optional): the    */
+/* fluxes F_x, F_y of fluxes() (zero outside buf = 1).                 */
+/* use_flattening = 0 blends with xi = 1 (the reference fails there:   */
+/* xi is the float 1.0 and fluxes.py:137 calls xi.v()).                */
+/* counts (optional, [2]): cells where the to_centers mask fell back   */
+/* to the averages (fluxes.py:60-66), and q_avg values where the       */
+/* positivity fallback took q_cc (fluxes.py:89-96).                    */
+/* Returns 1 where the cons_to_prim asserts of fluxes.py:80-81 fire.   */
+/* Scalar `x**2` (CPython float, dx**2) is libm pow; inside the njit    */
+/* riemann_prim it follows orc_set_scalar_pow (c_l**2).                */
+/* ================================================================== */
+static volatile double g_two_fv4 = 2.0;
+static inline double pypow2(double x) { return pow(x, g_two_fv4); }
+static inline double npmin(double a, double b) { return (a != a) ? a : (b != b) ? b : (a < b ? a : b); }
+
+/* fourth_order.states, one component a (qx,qy) -> al, ar (zeroed here) */
+static void fv4_states(const double *a, int qx, int qy, int ng, int idir, double *al, double *ar,
+                       double *wk /* 6 * qx * qy */)
+{
+    const size_t N = (size_t)qx * qy;
+    const int nx = qx - 2 * ng, ny = qy - 2 * ng;
+    const int ilo = ng, ihi = ng + nx, jlo = ng, jhi = ng + ny; /* njit-local */
+    const double C2 = 1.25, C3 = 0.1;
+    double *a_int = wk, *dafm = wk + N, *dafp = wk + 2 * N, *d2af = wk + 3 * N, *d2ac = wk + 4 * N,
+           *d3a = wk + 5 * N;
+    memset(wk, 0, 6 * N * 8);
+    memset(al, 0, N * 8);
+    memset(ar, 0, N * 8);
+#define A(i, j) a[(size_t)(i) * qy + (j)]
+#define W(p, i, j) p[(size_t)(i) * qy + (j)]
+    /* (di, dj): the sweep's unit step; the cell loops run over the same ranges with the
+       roles of i and j swapped between the two directions */
+    const int di = (idir == 1), dj = (idir == 2);
+    int i0, i1, j0, j1;
+    /* a_int, al, ar: fourth_order.py:61-70 / :150-159 */
+    if (idir == 1) { i0 = ilo - 2; i1 = ihi + 3; j0 = jlo - 1; j1 = jhi + 1; }
+    else           { i0 = ilo - 1; i1 = ihi + 1; j0 = jlo - 2; j1 = jhi + 3; }
+    for (int i = i0; i < i1; i++)
+        for (int j = j0; j < j1; j++) {
+            W(a_int, i, j) = (7.0 / 12.0) * (A(i - di, j - dj) + A(i, j)) -
+                             (1.0 / 12.0) * (A(i - 2 * di, j - 2 * dj) + A(i + di, j + dj));
+            W(al, i, j) = W(a_int, i, j);
+            W(ar, i, j) = W(a_int, i, j);
+        }
+    /* dafm, dafp, d2af: :72-80 / :161-169 (same ranges) */
+    for (int i = i0; i < i1; i++)
+        for (int j = j0; j < j1; j++) {
+            W(dafm, i, j) = A(i, j) - W(a_int, i, j);
+            W(dafp, i, j) = W(a_int, i + di, j + dj) - A(i, j);
+            W(d2af, i, j) = 6.0 * (W(a_int, i, j) - 2.0 * A(i, j) + W(a_int, i + di, j + dj));
+        }
+    /* d2ac: :82-84 / :171-173 */
+    if (idir == 1) { i0 = ilo - 3; i1 = ihi + 3; j0 = jlo - 1; j1 = jhi + 1; }
+    else           { i0 = ilo - 1; i1 = ihi + 1; j0 = jlo - 3; j1 = jhi + 3; }
+    for (int i = i0; i < i1; i++)
+        for (int j = j0; j < j1; j++)
+            W(d2ac, i, j) = A(i - di, j - dj) - 2.0 * A(i, j) + A(i + di, j + dj);
+    /* d3a: :86-89 / :175-178 -- the y sweep stops at jhi + 1 (njit-local jhi = ng + ny),
+       so d3a[i, ng + ny + 2] stays 0 where the limiter of the last cell reads it */
+    if (idir == 1) { i0 = ilo - 2; i1 = ihi + 3; j0 = jlo - 1; j1 = jhi + 1; }
+    else           { i0 = ilo - 1; i1 = ihi + 1; j0 = jlo - 2; j1 = jhi + 2; }
+    for (int i = i0; i < i1; i++)
+        for (int j = j0; j < j1; j++)
+            W(d3a, i, j) = W(d2ac, i, j) - W(d2ac, i - di, j - dj);
+    /* the limiter, :93-144 / :182-233, over cells ilo-1 .. ihi, jlo-1 .. jhi (njit-local) */
+    for (int i = ilo - 1; i < ihi + 1; i++)
+        for (int j = jlo - 1; j < jhi + 1; j++) {
+            const double ac = A(i, j), fm = W(dafm, i, j), fp = W(dafp, i, j), f2 = W(d2af, i, j);
+            const double cm = W(d2ac, i - di, j - dj), c0 = W(d2ac, i, j), cp = W(d2ac, i + di, j + dj);
+            double *arc = &W(ar, i, j), *alp = &W(al, i + di, j + dj);
+            if (fm * fp <= 0.0 ||
+                (ac - A(i - 2 * di, j - 2 * dj)) * (A(i + 2 * di, j + 2 * dj) - ac) <= 0.0) {
+                const double s = copysign(1.0, c0);
+                double d2a_lim, rho;
+                if (s == copysign(1.0, cm) && s == copysign(1.0, cp) && s == copysign(1.0, f2)) {
+                    /* Python min(): the first of equal values, NaN never replaces */
+                    double m = fabs(f2);
+                    if (C2 * fabs(cm) < m) m = C2 * fabs(cm);
+                    if (C2 * fabs(c0) < m) m = C2 * fabs(c0);
+                    if (C2 * fabs(cp) < m) m = C2 * fabs(cp);
+                    d2a_lim = s * m;
+                } else {
+                    d2a_lim = 0.0;
+                }
+                double amax = fabs(A(i - 2 * di, j - 2 * dj));
+                for (int m = -1; m <= 2; m++) {
+                    const double v = fabs(A(i + m * di, j + m * dj));
+                    if (v > amax) amax = v;
+                }
+                if (fabs(f2) <= 1.e-12 * amax) rho = 0.0;
+                else rho = d2a_lim / f2;
+                if (rho < 1.0 - 1.e-12) {
+                    double d3[4];
+                    for (int m = 0; m < 4; m++) d3[m] = W(d3a, i + (m - 1) * di, j + (m - 1) * dj);
+                    double d3a_min = d3[0], d3a_max = d3[0];
+                    for (int m = 1; m < 4; m++) {
+                        if (d3[m] < d3a_min) d3a_min = d3[m];
+                        if (d3[m] > d3a_max) d3a_max = d3[m];
+                    }
+                    const double big = fabs(d3a_max) > fabs(d3a_min) ? fabs(d3a_max) : fabs(d3a_min);
+                    if (C3 * big <= (d3a_max - d3a_min)) {
+                        if (fm * fp < 0.0) {
+                            *arc = ac - rho * fm;
+                            *alp = ac + rho * fp;
+                        } else if (fabs(fm) >= 2.0 * fabs(fp)) {
+                            *arc = ac - 2.0 * (1.0 - rho) * fp - rho * fm;
+                        } else if (fabs(fp) >= 2.0 * fabs(fm)) {
+                            *alp = ac + 2.0 * (1.0 - rho) * fm + rho * fp;
+                        }
+                    }
+                }
+            } else {
+                if (fabs(fm) >= 2.0 * fabs(fp)) *arc = ac - 2.0 * fp;
+                if (fabs(fp) >= 2.0 * fabs(fm)) *alp = ac + 2.0 * fm;
+            }
+        }
+#undef A
+#undef W
+}
+
+/* riemann_prim without solid walls (the 4th-order solver passes 0, 0), riemann.py:314-574 */
+static void fv4_riemann_prim(int idir, int qx, int qy, int ng, double gamma, const double *q_l,
+                             const double *q_r, double *q_int)
+{
+    const int nx = qx - 2 * ng, ny = qy - 2 * ng;
+    const int ilo = ng, ihi = ng + nx, jlo = ng, jhi = ng + ny; /* njit-local */
+    const double smallc = 1.e-10, smallrho = 1.e-10, smallp = 1.e-10;
+    memset(q_int, 0, (size_t)qx * qy * 32);
+    for (int i = ilo - 1; i < ihi + 1; i++)
+        for (int j = jlo - 1; j < jhi + 1; j++) {
+            const double *ql = q_l + ((size_t)i * qy + j) * 4, *qr = q_r + ((size_t)i * qy + j) * 4;
+            double rho_l = ql[IRHO], un_l, ut_l, rho_r = qr[IRHO], un_r, ut_r;
+            if (idir == 1) { un_l = ql[IU]; ut_l = ql[IV]; un_r = qr[IU]; ut_r = qr[IV]; }
+            else           { un_l = ql[IV]; ut_l = ql[IU]; un_r = qr[IV]; ut_r = qr[IU]; }
+            double p_l = pymax(ql[IP], smallp), p_r = pymax(qr[IP], smallp);
+            rho_l = pymax(smallrho, rho_l);
+            rho_r = pymax(smallrho, rho_r);
+            const double W_l = pymax(smallrho * smallc, sqrt(gamma * p_l * rho_l));
+            const double W_r = pymax(smallrho * smallc, sqrt(gamma * p_r * rho_r));
+            const double c_l = pymax(smallc, sqrt(gamma * p_l / rho_l));
+            const double c_r = pymax(smallc, sqrt(gamma * p_r / rho_r));
+            double pstar = (W_l * p_r + W_r * p_l + W_l * W_r * (un_l - un_r)) / (W_l + W_r);
+            pstar = pymax(pstar, smallp);
+            const double ustar = (W_l * un_l + W_r * un_r + (p_l - p_r)) / (W_l + W_r);
+            const double rhostar_l = rho_l + (pstar - p_l) / sq_ref(c_l);
+            const double rhostar_r = rho_r + (pstar - p_r) / sq_ref(c_r);
+            const double cstar_l = pymax(smallc, sqrt(gamma * pstar / rhostar_l));
+            const double cstar_r = pymax(smallc, sqrt(gamma * pstar / rhostar_r));
+            double rho_s, un_s, ut_s, p_s;
+            if (ustar > 0.0) {
+                ut_s = ut_l;
+                const double lambda_l = un_l - c_l, lambdastar_l = ustar - cstar_l;
+                if (pstar > p_l) {
+                    const double sigma = (lambda_l + lambdastar_l) / 2.0;
+                    if (sigma > 0.0) { rho_s = rho_l; un_s = un_l; p_s = p_l; }
+                    else { rho_s = rhostar_l; un_s = ustar; p_s = pstar; }
+                } else if (lambda_l < 0.0 && lambdastar_l < 0.0) {
+                    rho_s = rhostar_l; un_s = ustar; p_s = pstar;
+                } else if (lambda_l > 0.0 && lambdastar_l > 0.0) {
+                    rho_s = rho_l; un_s = un_l; p_s = p_l;
+                } else {
+                    const double alpha = lambda_l / (lambda_l - lambdastar_l);
+                    rho_s = alpha * rhostar_l + (1.0 - alpha) * rho_l;
+                    un_s = alpha * ustar + (1.0 - alpha) * un_l;
+                    p_s = alpha * pstar + (1.0 - alpha) * p_l;
+                }
+            } else if (ustar < 0) {
+                ut_s = ut_r;
+                const double lambda_r = un_r + c_r, lambdastar_r = ustar + cstar_r;
+                if (pstar > p_r) {
+                    const double sigma = (lambda_r + lambdastar_r) / 2.0;
+                    if (sigma > 0.0) { rho_s = rhostar_r; un_s = ustar; p_s = pstar; }
+                    else { rho_s = rho_r; un_s = un_r; p_s = p_r; }
+                } else if (lambda_r < 0.0 && lambdastar_r < 0.0) {
+                    rho_s = rho_r; un_s = un_r; p_s = p_r;
+                } else if (lambda_r > 0.0 && lambdastar_r > 0.0) {
+                    rho_s = rhostar_r; un_s = ustar; p_s = pstar;
+                } else {
+                    const double alpha = lambda_r / (lambda_r - lambdastar_r);
+                    rho_s = alpha * rhostar_r + (1.0 - alpha) * rho_r;
+                    un_s = alpha * ustar + (1.0 - alpha) * un_r;
+                    p_s = alpha * pstar + (1.0 - alpha) * p_r;
+                }
+            } else {
+                rho_s = 0.5 * (rhostar_l + rhostar_r);
+                un_s = ustar;
+                ut_s = 0.5 * (ut_l + ut_r);
+                p_s = pstar;
+            }
+            double *o = q_int + ((size_t)i * qy + j) * 4;
+            o[IRHO] = rho_s;
+            if (idir == 1) { o[IU] = un_s; o[IV] = ut_s; }
+            else           { o[IU] = ut_s; o[IV] = un_s; }
+            o[IP] = p_s;
+        }
+}
+
+/* fluxes.py:12-38 over the whole array */
+static void fv4_flux_cons(int idir, double gamma, const double *q, size_t N, double *F)
+{
+    for (size_t k = 0; k < N; k++) {
+        const double *c = q + k * 4;
+        double *f = F + k * 4;
+        const double un = (idir == 1) ? c[IU] : c[IV];
+        f[IDENS] = c[IRHO] * un;
+        if (idir == 1) {
+            f[IXMOM] = c[IRHO] * (c[IU] * c[IU]) + c[IP];
+            f[IYMOM] = c[IRHO] * c[IV] * c[IU];
+        } else {
+            f[IXMOM] = c[IRHO] * c[IU] * c[IV];
+            f[IYMOM] = c[IRHO] * (c[IV] * c[IV]) + c[IP];
+        }
+        f[IENER] = (c[IP] / (gamma - 1.0) + 0.5 * c[IRHO] * (c[IU] * c[IU] + c[IV] * c[IV]) + c[IP]) * un;
+    }
+}
+
+/* FV2d.to_centers of every variable, fv.py:18-29: the copy, then the buf = ng-1 ring */
+static void fv4_to_centers(const double *U, int qx, int qy, double dx, double dy, double *c)
+{
+    const double dx2 = pypow2(dx), dy2 = pypow2(dy);
+    memcpy(c, U, (size_t)qx * qy * 32);
+    for (int i = 1; i < qx - 1; i++)
+        for (int j = 1; j < qy - 1; j++)
+            for (int n = 0; n < 4; n++) {
+#define UU(i, j) U[((size_t)(i) * qy + (j)) * 4 + n]
+                const double lap = (UU(i - 1, j) - 2 * UU(i, j) + UU(i + 1, j)) / dx2 +
+                                   (UU(i, j - 1) - 2 * UU(i, j) + UU(i, j + 1)) / dy2;
+                c[((size_t)i * qy + j) * 4 + n] = UU(i, j) - dx2 * lap / 24.0;
+#undef UU
+            }
+}
+
+int orc_fv4_rhs(double *U, const orc_comp_params *P, double *kout, double *o_Fx, double *o_Fy,
+                int *counts)
+{
+    const int nx = P->nx, ny = P->ny, ng = P->ng;
+    const int qx = nx + 2 * ng, qy = ny + 2 * ng;
+    const int ilo = ng, ihi = ng + nx - 1, jlo = ng, jhi = ng + ny - 1;
+    const size_t N = (size_t)qx * qy;
+    const double gamma = P->gamma, dx = P->dx, dy = P->dy;
+    const double dx2 = pypow2(dx), dy2 = pypow2(dy);
+    const double alpha = 0.3, beta = 0.3;
+    int rc = 0, n_mask = 0, n_pos = 0;
+#define U4(a, i, j, n) a[((size_t)(i) * qy + (j)) * 4 + (n)]
+#define I2(i, j) ((size_t)(i) * qy + (j))
+    for (int i = ilo; i <= ihi; i++)            /* clean_state: the interior only */
+        for (int j = jlo; j <= jhi; j++)
+            U4(U, i, j, IDENS) = pymax(U4(U, i, j, IDENS), P->small_dens);
+
+    /* substep, simulation.py:32-46: sources on the unmasked centres, back to averages */
+    double *Ucc = zalloc(N * 4), *S = zalloc(N * 4), *Sa = zalloc(N * 4);
+    fv4_to_centers(U, qx, qy, dx, dy, Ucc);
+    ext_sources_h(Ucc, NULL, N, P->grav, 0.0, S, P->heat_rate, P->heat_prof);
+    memcpy(Sa, S, N * 32);
+    for (int i = ilo; i <= ihi; i++)
+        for (int j = jlo; j <= jhi; j++)
+            for (int n = 0; n < 4; n++) {
+                const double lap = (U4(S, i - 1, j, n) - 2 * U4(S, i, j, n) + U4(S, i + 1, j, n)) / dx2 +
+                                   (U4(S, i, j - 1, n) - 2 * U4(S, i, j, n) + U4(S, i, j + 1, n)) / dy2;
+                U4(Sa, i, j, n) = U4(S, i, j, n) - dx2 * lap / 24.0;
+            }
+
+    /* fluxes.py:55-69: masked centres */
+    for (size_t k = 0; k < N; k++) {
+        double *c = Ucc + k * 4;
+        const double rhoe = c[IENER] - 0.5 * (c[IXMOM] * c[IXMOM] + c[IYMOM] * c[IYMOM]) / c[IDENS];
+        if (c[IDENS] < 0 || rhoe < 0) {
+            memcpy(c, U + k * 4, 32);
+            n_mask++;
+        }
+    }
+    double *qbar = zalloc(N * 4), *qcc = zalloc(N * 4), *qavg = zalloc(N * 4);
+    rc |= orc_cons_to_prim(U, nx, ny, ng, gamma, qbar);        /* fluxes.py:80-81 */
+    rc |= orc_cons_to_prim(Ucc, nx, ny, ng, gamma, qcc);
+    for (int i = ilo - 3; i <= ihi + 3; i++)                   /* fluxes.py:84-96 */
+        for (int j = jlo - 3; j <= jhi + 3; j++)
+            for (int n = 0; n < 4; n++) {
+                const double lap =
+                    (U4(qbar, i - 1, j, n) - 2 * U4(qbar, i, j, n) + U4(qbar, i + 1, j, n)) / dx2 +
+                    (U4(qbar, i, j - 1, n) - 2 * U4(qbar, i, j, n) + U4(qbar, i, j + 1, n)) / dy2;
+                double v = U4(qcc, i, j, n) + dx2 / 24.0 * lap;
+                if ((n == IRHO || n == IP) && !(v > 0)) {
+                    v = U4(qcc, i, j, n);
+                    n_pos++;
+                }
+                U4(qavg, i, j, n) = v;
+            }
+    double *xi = zalloc(N);                                     /* fluxes.py:99-107 */
+    if (P->use_flattening)
+        orc_flatten_multid(qbar, nx, ny, ng, P->z0, P->z1, P->delta, xi);
+    else
+        for (size_t k = 0; k < N; k++) xi[k] = 1.0;
+
+    double *a = zalloc(N), *al = zalloc(N), *ar = zalloc(N), *wk = zalloc(6 * N);
+    double *q_l = zalloc(N * 4), *q_r = zalloc(N * 4), *qint = zalloc(N * 4), *qfc = zalloc(N * 4);
+    double *Ffc = zalloc(N * 4), *Favg = zalloc(N * 4), *lam = zalloc(N), *test = zalloc(N);
+    double *Fx = zalloc(N * 4), *Fy = zalloc(N * 4);
+    for (int idir = 1; idir <= 2; idir++) {
+        const int di = (idir == 1), dj = (idir == 2);
+        double *F = (idir == 1) ? Fx : Fy;
+        for (int n = 0; n < 4; n++) {                           /* fluxes.py:132-133 */
+            for (size_t k = 0; k < N; k++) a[k] = qavg[k * 4 + n];
+            fv4_states(a, qx, qy, ng, idir, al, ar, wk);
+            for (size_t k = 0; k < N; k++) { q_l[k * 4 + n] = al[k]; q_r[k * 4 + n] = ar[k]; }
+        }
+        for (int n = 0; n < 4; n++)                             /* fluxes.py:136-148 */
+            for (int i = ilo - 2; i <= ihi + 2; i++)
+                for (int j = jlo - 2; j <= jhi + 2; j++) {
+                    const double x = xi[I2(i, j)], qa = U4(qavg, i, j, n);
+                    U4(q_l, i + di, j + dj, n) = x * U4(q_l, i + di, j + dj, n) + (1.0 - x) * qa;
+                    U4(q_r, i, j, n) = x * U4(q_r, i, j, n) + (1.0 - x) * qa;
+                }
+        fv4_riemann_prim(idir, qx, qy, ng, gamma, q_l, q_r, qint);   /* fluxes.py:151-156 */
+        memset(qfc, 0, N * 32);                                 /* fluxes.py:159-172 */
+        for (int i = 1; i < qx - 1; i++)
+            for (int j = 1; j < qy - 1; j++)
+                for (int n = 0; n < 4; n++)
+                    U4(qfc, i, j, n) = U4(qint, i, j, n) -
+                                       1.0 / 24.0 * (U4(qint, i + dj, j + di, n) - 2 * U4(qint, i, j, n) +
+                                                     U4(qint, i - dj, j - di, n));
+        fv4_flux_cons(idir, gamma, qfc, N, Ffc);                /* fluxes.py:176-177 */
+        fv4_flux_cons(idir, gamma, qint, N, Favg);
+        memset(F, 0, N * 32);                                   /* fluxes.py:179-192 */
+        for (int i = ilo - 1; i <= ihi + 1; i++)
+            for (int j = jlo - 1; j <= jhi + 1; j++)
+                for (int n = 0; n < 4; n++)
+                    U4(F, i, j, n) = U4(Ffc, i, j, n) +
+                                     1.0 / 24.0 * (U4(Favg, i + dj, j + di, n) - 2 * U4(Favg, i, j, n) +
+                                                   U4(Favg, i - dj, j - di, n));
+        memset(lam, 0, N * 8);                                  /* fluxes.py:194-211 */
+        memset(test, 0, N * 8);
+        for (int i = ilo - 1; i <= ihi + 1; i++)
+            for (int j = jlo - 1; j <= jhi + 1; j++) {
+                if (idir == 1)
+                    lam[I2(i, j)] = (U4(qbar, i, j, IU) - U4(qbar, i - 1, j, IU)) / dx +
+                                    0.25 * (U4(qbar, i, j + 1, IV) - U4(qbar, i, j - 1, IV) +
+                                            U4(qbar, i - 1, j + 1, IV) - U4(qbar, i - 1, j - 1, IV)) / dy;
+                else
+                    lam[I2(i, j)] = (U4(qbar, i, j, IV) - U4(qbar, i, j - 1, IV)) / dy +
+                                    0.25 * (U4(qbar, i + 1, j, IU) - U4(qbar, i - 1, j, IU) +
+                                            U4(qbar, i + 1, j - 1, IU) - U4(qbar, i - 1, j - 1, IU)) / dx;
+                const double dl = dx * lam[I2(i, j)];         /* fluxes.py:213-215 */
+                test[I2(i, j)] = dl * dl / (beta * gamma * U4(qbar, i, j, IP) / U4(qbar, i, j, IRHO));
+            }
+        for (int i = ilo - 1; i <= ihi + 1; i++)                /* fluxes.py:217-225 */
+            for (int j = jlo - 1; j <= jhi + 1; j++) {
+                double nu = dx * lam[I2(i, j)] * npmin(test[I2(i, j)], 1.0);
+                if (lam[I2(i, j)] >= 0.0) nu = 0.0;
+                for (int n = 0; n < 4; n++)
+                    U4(F, i, j, n) += alpha * nu * (U4(U, i, j, n) - U4(U, i - di, j - dj, n));
+            }
+    }
+    if (o_Fx) memcpy(o_Fx, Fx, N * 32);
+    if (o_Fy) memcpy(o_Fy, Fy, N * 32);
+
+    memset(kout, 0, N * 32);                                    /* simulation.py:50-54 */
+    for (int i = ilo; i <= ihi; i++)
+        for (int j = jlo; j <= jhi; j++)
+            for (int n = 0; n < 4; n++)
+                U4(kout, i, j, n) = (U4(Fx, i, j, n) - U4(Fx, i + 1, j, n)) / dx +
+                                    (U4(Fy, i, j, n) - U4(Fy, i, j + 1, n)) / dy + U4(Sa, i, j, n);
+    if (P->do_sponge) {                                         /* simulation.py:57-64 */
+        const double PI = 3.14159265358979323846;
+        for (int i = ilo; i <= ihi; i++)
+            for (int j = jlo; j <= jhi; j++) {
+                const double rho = U4(U, i, j, IDENS);
+                double f;
+                if (rho > P->sponge_rho_begin) f = 0.0;
+                else if (rho < P->sponge_rho_full) f = 1.0;
+                else f = 0.5 * (1.0 - cos(PI * (rho - P->sponge_rho_begin) /
+                                          (P->sponge_rho_full - P->sponge_rho_begin)));
+                const double kap = f / P->sponge_timescale;
+                const double mx = U4(U, i, j, IXMOM), my = U4(U, i, j, IYMOM);
+                U4(kout, i, j, IXMOM) -= kap * mx;
+                U4(kout, i, j, IYMOM) -= kap * my;
+                U4(kout, i, j, IENER) -= kap * (mx * mx / rho + my * my / rho);
+            }
+    }
+    if (counts) { counts[0] = n_mask; counts[1] = n_pos; }
+    free(Ucc); free(S); free(Sa); free(qbar); free(qcc); free(qavg); free(xi);
+    free(a); free(al); free(ar); free(wk); free(q_l); free(q_r); free(qint); free(qfc);
+    free(Ffc); free(Favg); free(lam); free(test); free(Fx); free(Fy);
+#undef U4
+#undef I2
+    return rc;
+}

@@ -941,6 +941,9 @@ int pyrohip_comp_fv4_rhs(pyrohip_state *y, const pyrohip_comp_params *p, pyrohip
     PYRO_REQUIRE(y->g.ng == 4, "compressible_fv4 needs ng = 4 (the reference's grid)");
     PYRO_REQUIRE(!y->sph, "compressible_fv4 has no SphericalPolar geometry terms");
     PYRO_REQUIRE(k && k->ctx == y->ctx, "k state missing or on another context");
+    PYRO_REQUIRE(k != y && k->d != y->d,
+                 "k must not be the stage state: a tile would read cells that other tiles have "
+                 "already overwritten");
     PYRO_REQUIRE(k->g.nx == y->g.nx && k->g.ny == y->g.ny && k->g.ng == y->g.ng,
                  "k state must have the geometry of the stage state");
     PYRO_REQUIRE(slot >= 0 && 4 * (slot + 1) <= k->nvar, "slot outside the k state");

@@ -13,12 +13,13 @@
 // radius of the scheme is 5 cells (face states read q_avg at -4 .. +3, q_avg reads the
 // averages at +-1), so a tile loads the state on a (TI + 10) x (TJ + 10) window and works
 // inward:
-//   load (floored U, q_bar)  ->  U_cc, q_cc, q_avg; S at centres; xi_x, xi_y  ->  xi
+//   load (U, interior density floored; q_bar)  ->  U_cc, q_cc, q_avg; S at centres; xi_x, xi_y
+//   ->  xi
 //   ->  x faces: limited states, flattening, CGF  ->  F_x (face-centred + transverse
 //       Laplacian + artificial viscosity)  ->  the same for y  ->  k = -div F + <S> - sponge
 // The state is read once (plus the halo) and k written once.  k_fv4_prep runs in front of
-// it: the density floor (written back, like clean_state) and the two cons_to_prim asserts,
-// so that an invalid state leaves k untouched.
+// it: the density floor of the interior (written back, like clean_state) and the two
+// cons_to_prim asserts, so that an invalid state leaves k untouched.
 //
 // This file is compiled twice: PYRO_FAST=0 (-ffp-contract=off, the bit-faithful build) and
 // PYRO_FAST=1 (-ffp-contract=fast); pyrohip_comp_fv4_rhs dispatches on fast_math.
@@ -136,7 +137,7 @@ __device__ __forceinline__ void flux_cons_n(const PrimN &q, double gamma, double
 enum { QR = 0, QU = 1, QV = 2, QP = 3 };
 
 struct Lds {
-    double U[4][B5::N];      // floored averages
+    double U[4][B5::N];      // averages, the interior density floored
     double Qb[4][B5::N];     // q_bar
     double Qa[4][B4::N];     // q_avg (0 in the outermost ghost ring, as the reference's buf = 3)
     double S[2][B1::N];      // S[E], S[ymom] at cell centres
@@ -151,8 +152,10 @@ struct Lds {
 
 }  // namespace
 
-// density floor (written back: clean_state modifies the stage state, fv4/simulation.py:24) and
-// the two cons_to_prim asserts of fluxes.py:80-81 (U_avg and the masked U_cc, interior only).
+// density floor of the interior (written back: clean_state modifies the stage state,
+// fv4/simulation.py:24, through U.v() -- compressible/simulation.py:452-456 -- so the ghost cells
+// keep their density) and the two cons_to_prim asserts of fluxes.py:80-81 (U_avg and the masked
+// U_cc, interior only).
 // flag |= 1 on an invalid state.
 __global__ __launch_bounds__(256) void k_fv4_prep(double *__restrict__ U, Geom g, FP P,
                                                   int *__restrict__ flag)
@@ -160,12 +163,12 @@ __global__ __launch_bounds__(256) void k_fv4_prep(double *__restrict__ U, Geom g
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     const int i = blockIdx.y;
     if (j >= g.qy) return;
+    if (i < g.ilo || i > g.ihi || j < g.jlo || j > g.jhi) return;   // ghosts keep their density
     const size_t pl = g.plane;
     const size_t k = (size_t)i * g.pitch + j;
     const double d0 = U[k];
     const double d = floor_dens(d0, P.small_dens);
     if (d != d0) U[k] = d;
-    if (i < g.ilo || i > g.ihi || j < g.jlo || j > g.jhi) return;
     bool ok_avg, ok_cc;
     const Cons Ua{d, U[pl + k], U[2 * pl + k], U[3 * pl + k]};
     (void)cons_to_prim(Ua, P.gamma, &ok_avg);
@@ -176,9 +179,12 @@ __global__ __launch_bounds__(256) void k_fv4_prep(double *__restrict__ U, Geom g
     for (int n = 0; n < 4; n++) {
         const double *a = U + n * pl;
         double v = a[k], im = a[k - g.pitch], ip = a[k + g.pitch], jm = a[k - 1], jp = a[k + 1];
-        if (n == 0) {
-            v = d; im = floor_dens(im, P.small_dens); ip = floor_dens(ip, P.small_dens);
-            jm = floor_dens(jm, P.small_dens); jp = floor_dens(jp, P.small_dens);
+        if (n == 0) {   // the floored density of the interior neighbours (written by their threads)
+            v = d;
+            if (i > g.ilo) im = floor_dens(im, P.small_dens);
+            if (i < g.ihi) ip = floor_dens(ip, P.small_dens);
+            if (j > g.jlo) jm = floor_dens(jm, P.small_dens);
+            if (j < g.jhi) jp = floor_dens(jp, P.small_dens);
         }
         const double lap = (im - 2 * v + ip) / dx2 + (jm - 2 * v + jp) / dy2;
         c[n] = v - dx2 * lap / 24.0;
@@ -199,14 +205,17 @@ __global__ __launch_bounds__(NT) void k_fv4_rhs(const double *__restrict__ Ug, d
     const size_t pl = g.plane;
     const double dx2 = P.dx * P.dx, dy2 = P.dy * P.dy;
 
-    // ---- 1. floored averages and q_bar on the 5-cell apron (zero beyond the array) ----------
+    // ---- 1. averages (density floored on the interior) and q_bar on the 5-cell apron (zero
+    //         beyond the array) -----------------------------------------------------------------
     for (int e = t; e < B5::N; e += NT) {
         const int a = e / B5::NJ - 5, b = e % B5::NJ - 5;
         const int i = i0 + a, j = j0 + b;
         Cons u{0.0, 0.0, 0.0, 0.0};
         if (i >= 0 && i < g.qx && j >= 0 && j < g.qy) {
             const size_t k = (size_t)i * g.pitch + j;
-            u = Cons{floor_dens(Ug[k], P.small_dens), Ug[pl + k], Ug[2 * pl + k], Ug[3 * pl + k]};
+            const bool inner = i >= g.ilo && i <= g.ihi && j >= g.jlo && j <= g.jhi;
+            u = Cons{inner ? floor_dens(Ug[k], P.small_dens) : Ug[k], Ug[pl + k], Ug[2 * pl + k],
+                     Ug[3 * pl + k]};
         }
         L.U[0][e] = u.d; L.U[1][e] = u.E; L.U[2][e] = u.mx; L.U[3][e] = u.my;
         const Prim q = cons_to_prim(u, P.gamma);
@@ -464,6 +473,7 @@ int comp_fv4_rhs(pyrohip_state *s, const pyrohip_comp_params *p, pyrohip_state *
     PYRO_CHECK_HIP(hipMemsetAsync(s->d_flag, 0, sizeof(int), c->stream));
     PYRO_LAUNCH(c, "k_fv4_prep", k_fv4_prep, dim3((g.qy + 255) / 256, g.qx), dim3(256), 0, s->d, g, P,
                 s->d_flag);
+    PYRO_CHECK_HIP(hipGetLastError());   // (a refused prep launch must not be lost behind the next)
     const dim3 grid((g.nx + TI - 1) / TI, (g.ny + TJ - 1) / TJ);
     PYRO_LAUNCH(c, "k_fv4_rhs", k_fv4_rhs, grid, dim3(NT), 0, (const double *)s->d,
                 kst->d + (size_t)(4 * slot) * g.plane, g, P, (const int *)s->d_flag);

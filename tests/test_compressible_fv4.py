@@ -22,33 +22,67 @@ def _rel(a, b):
             for n in range(a.shape[-1])]
 
 
-def _rhs(ctx, U, bcs, meta, fast, slot=0):
+def _rhs(ctx, U, bcs, meta, fast, slot=0, small_dens=-1.e200, heat=None, state=False):
+    """k of U into slot `slot` of a k state pre-filled with 7.0; heat = (rate, profile);
+    state=True also returns the stage state after the call"""
     from pyro2_amd import device
     qx, qy = U.shape[:2]
     nx, ny = qx - 8, qy - 8
     dx, dy, gamma, grav, flat, sponge, rb, rf, tau = meta
     P = device.make_comp_params(dx, dy, gamma=gamma, grav=grav, use_flattening=int(flat),
-                                fast_math=fast, riemann="CGF",
-                                sponge=(rb, rf, tau) if sponge else None)
+                                fast_math=fast, riemann="CGF", small_dens=small_dens,
+                                sponge=(rb, rf, tau) if sponge else None,
+                                heat_rate=heat[0] if heat is not None else 0.0)
     s = device.DeviceState(ctx, nx, ny, 4, [[str(b) for b in r] for r in bcs])
     s.upload(np.ascontiguousarray(U))
+    if heat is not None:
+        s.set_heating(heat[1])
     k = device.DeviceState(ctx, nx, ny, 4, [["outflow"] * 4] * (4 * (slot + 1)))
     k.upload(np.full((qx, qy, 4 * (slot + 1)), 7.0))
     s.comp_fv4_rhs(P, k, slot)
-    return k.download()[..., 4 * slot:4 * slot + 4]
+    got = k.download()[..., 4 * slot:4 * slot + 4]
+    return (got, s.download()) if state else got
+
+
+def _rhs_cases(golden):
+    """(file, case) of every reference right-hand side: the three of comp_fv4_rhs and the
+    ragged / sub-tile / dx != dy / heating / quad / density-floor cases of comp_fv4_edges"""
+    return [(name, str(c)) for name in ("comp_fv4_rhs", "comp_fv4_edges") for c in golden(name)["cases"]]
+
+
+def _case_args(g, case):
+    """small_dens and (heat_rate, profile) of a fixture case (defaults where absent)"""
+    sd = float(g[f"{case}_small_dens"]) if f"{case}_small_dens" in g else -1.e200
+    heat = (float(g[f"{case}_heat_rate"]), g[f"{case}_heat"]) if f"{case}_heat" in g else None
+    return sd, heat
+
+
+# Variables whose k is zero analytically in a case: sod.x is uniform in y with reflecting y
+# walls, so k of the y-momentum is round-off (max |k| 1.6e-10 against 11.4 for the x-momentum).
+# Its error is measured against the momentum's scale, max |k| of both components.
+ZERO_K = {("comp_fv4_edges", "sodx"): 3}
 
 
 @pytest.mark.parametrize("fast,tol", [(0, 1e-14), (1, 1e-10)])
 def test_fv4_rhs_vs_reference(dev, golden, fast, tol):
-    """Simulation.substep of the reference on the acoustic pulse (32^2), a shocked sod state
-    (32 x 48) and an rt state with gravity and the sponge (24 x 40: ragged tiles)"""
-    g = golden("comp_fv4_rhs")
-    for case in g["cases"]:
+    """Simulation.substep of the reference: the acoustic pulse (32^2), a shocked sod state
+    (32 x 48), rt with gravity and the sponge (24 x 40), and comp_fv4_edges: sod.x 21 x 13
+    with a density floor above the outflow ghosts' density, rt 13 x 70 (hse), heating 18^2
+    (a strong source), quad 20^2 and the pulse with dy = 1.5 dx.  Where the fixture holds the state after the
+    call, the stage state must match it bit for bit (clean_state floors the interior only)."""
+    for name, case in _rhs_cases(golden):
+        g = golden(name)
         U, k, bcs, meta = g[f"{case}_U"], g[f"{case}_k"], g[f"{case}_bcs"], g[f"{case}_meta"]
-        got = _rhs(dev, U, bcs, meta, fast, slot=1)
+        sd, heat = _case_args(g, case)
+        got, Uout = _rhs(dev, U, bcs, meta, fast, slot=1, small_dens=sd, heat=heat, state=True)
         err = _rel(got[4:-4, 4:-4], k[4:-4, 4:-4])
-        print(case, "fast" if fast else "exact", err)
+        if (name, case) in ZERO_K:
+            n, K = ZERO_K[(name, case)], k[4:-4, 4:-4]
+            err[n] = float(np.abs(got[4:-4, 4:-4, n] - K[..., n]).max() / np.abs(K[..., 2:4]).max())
+        print(name, case, "fast" if fast else "exact", err)
         assert max(err) <= tol, (case, err)
+        if f"{case}_Uout" in g:
+            assert np.array_equal(Uout, g[f"{case}_Uout"]), case
 
 
 def test_fv4_from_to_centers(api):
@@ -105,6 +139,33 @@ def test_fv4_sdc_runs_vs_reference(api, golden, solver, steps, fast, tol):
     U = np.array(p.sim.cc_data.data)
     err = _rel(U[4:-4, 4:-4], g[solver + "_U"][4:-4, 4:-4])
     print(solver, fast, err)
+    assert max(err) <= tol
+
+
+@pytest.mark.parametrize("fast,tol", [(0, 1e-12), (1, 1e-10)])
+@pytest.mark.parametrize("solver,steps", [("compressible_fv4", 4), ("compressible_sdc", 3)])
+@pytest.mark.parametrize("grid", ["sodx", "rt"])
+def test_fv4_sdc_edge_runs_vs_reference(api, golden, grid, solver, steps, fast, tol):
+    """the same on ragged, non-periodic grids: sod.x at 44 x 12 (outflow x, reflect y) and rt at
+    12 x 36 (periodic x, hse y, gravity) -- boundary fill, stages and SDC node updates"""
+    from pyro2_amd.pyro_sim import Pyro
+    g = golden("comp_fv4_edge_runs")
+    prob, inputs, extra = {
+        "sodx": ("sod", "inputs.sod.x", {"mesh.nx": 44, "mesh.ny": 12, "mesh.xmax": 1.0, "mesh.ymax": 12 / 44}),
+        "rt": ("rt", "inputs.rt", {"mesh.nx": 12, "mesh.ny": 36, "mesh.xmax": 0.5, "mesh.ymax": 1.5})}[grid]
+    p = Pyro(solver)
+    p.initialize_problem(prob, inputs_file=inputs,
+                         inputs_dict=dict(extra, **{"driver.fix_dt": -1.0, "driver.max_steps": steps,
+                                                    "gpu.fast_math": fast}))
+    dts = []
+    for _ in range(steps):
+        p.single_step()
+        dts.append(p.sim.dt)
+    pre = f"{grid}_{solver}"
+    assert np.abs(np.array(dts) - g[pre + "_dts"]).max() <= 1e-12 * g[pre + "_dts"].max()
+    U = np.array(p.sim.cc_data.data)
+    err = _rel(U[4:-4, 4:-4], g[pre + "_U"][4:-4, 4:-4])
+    print(grid, solver, fast, err)
     assert max(err) <= tol
 
 

@@ -876,3 +876,61 @@ def test_oracle_burgers_viscous(golden, k):
     U, dts = oracle_bgv_run(g, pre, len(g[pre + "dts"]))
     assert np.abs(dts / g[pre + "dts"] - 1).max() < 1e-12
     assert np.abs(U[I] - g[pre + "final"][I]).max() < 1e-12
+
+
+# ------------------------------------------------------- compressible_fv4 rhs
+FV4_CASES = [("comp_fv4_rhs", c) for c in ("pulse", "sod", "rt")] + \
+            [("comp_fv4_edges", c) for c in ("sodx", "rt", "heating", "quad", "pulse_dy")]
+
+
+def fv4_oracle_params(g, case):
+    """orc.comp_params of a comp_fv4_* fixture case (meta, small_dens, heating)"""
+    U, meta = g[f"{case}_U"], g[f"{case}_meta"]
+    dx, dy, gamma, grav, flat, sponge, rb, rf, tau = meta
+    sd = float(g[f"{case}_small_dens"]) if f"{case}_small_dens" in g else -1.e200
+    heat = (float(g[f"{case}_heat_rate"]), g[f"{case}_heat"]) if f"{case}_heat" in g else None
+    return orc.comp_params(U.shape[0] - 8, U.shape[1] - 8, 4, dx, dy, gamma=gamma, use_flattening=int(flat),
+                           grav=grav, small_dens=sd, sponge=(rb, rf, tau) if sponge else None, heating=heat)
+
+
+@pytest.mark.parametrize("name,case", FV4_CASES, ids=[f"{n}-{c}" for n, c in FV4_CASES])
+def test_oracle_fv4_rhs(golden, name, case):
+    """orc_fv4_rhs against compressible_fv4 Simulation.substep / fluxes.fluxes of the reference:
+    interior k, F_x and F_y on the whole array (zero where the reference writes nothing) and,
+    where stored, the stage state after the call (clean_state floors the interior only).
+    Bit for bit with both readings of the njit riemann_prim's scalar c**2 (x*x as numba
+    compiles it, libm pow as the interpreted shim that made the fixtures evaluates it):
+    they agree on every face of these cases."""
+    g = golden(name)
+    assert case in [str(c) for c in g["cases"]]
+    I = (slice(4, -4), slice(4, -4))
+    for scalar_pow in (0, 1):
+        orc.set_scalar_pow(scalar_pow)
+        try:
+            U = g[f"{case}_U"].copy()
+            rc, k, Fx, Fy = orc.fv4_rhs(U, fv4_oracle_params(g, case), fluxes=True)
+        finally:
+            orc.set_scalar_pow(0)
+        assert rc == 0
+        assert np.array_equal(k[I], g[f"{case}_k"][I]), scalar_pow
+        assert np.array_equal(Fx, g[f"{case}_Fx"]), scalar_pow
+        assert np.array_equal(Fy, g[f"{case}_Fy"]), scalar_pow
+        if f"{case}_Uout" in g:
+            assert np.array_equal(U, g[f"{case}_Uout"])
+    if case == "sodx":       # the floor fired in the interior and left ghosts below it
+        sd = float(g["sodx_small_dens"])
+        assert (g["sodx_U"][I][..., 0] < sd).any() and (g["sodx_Uout"][..., 0] < sd).any()
+
+
+def test_oracle_fv4_rhs_assert():
+    """the two cons_to_prim asserts of fluxes.py:80-81: rc = 1 on a negative interior density
+    or pressure, rc = 0 when only a ghost cell is bad"""
+    nx, ny = 6, 5
+    U = np.zeros((nx + 8, ny + 8, 4))
+    U[..., 0], U[..., 1] = 1.0, 2.5
+    P = orc.comp_params(nx, ny, 4, 0.1, 0.1)
+    assert orc.fv4_rhs(U.copy(), P)[0] == 0
+    for (i, j, n, v), rc in (((5, 6, 0, -1.0), 1), ((7, 4, 1, -3.0), 1), ((1, 6, 1, -3.0), 0)):
+        V = U.copy()
+        V[i, j, n] = v
+        assert orc.fv4_rhs(V, P)[0] == rc, (i, j, n)
