@@ -95,10 +95,7 @@ __host__ __device__ inline int adv_nstrips(int ny, bool vneg)
 // (2, 3 and 6 rows in flight measured at the end of round 3: 27.1 / 27.2 / 29.9 us per 2048^2
 // launch under the event timers, 281 / 282 / 287 us at 8192^2 -- the strips do not wait for
 // their rows; three wavefronts per SIMD take turns at ~160 instructions per row)
-#ifndef PYRO_ADV_PF
-#define PYRO_ADV_PF 3
-#endif
-constexpr int ADV_PF = PYRO_ADV_PF;
+constexpr int ADV_PF = 3;
 
 constexpr int adv_gcd(int a, int b) { return b == 0 ? a : adv_gcd(b, a % b); }
 constexpr int adv_lcm(int a, int b) { return a / adv_gcd(a, b) * b; }
@@ -149,35 +146,10 @@ __device__ __forceinline__ D2 adv_left(const D2 &q) { return D2{adv_m1(q.b), q.a
 __device__ __forceinline__ D2 adv_right(const D2 &q) { return D2{q.b, adv_p1(q.a)}; }
 
 // limited slope from shared limit2 values (reconstruction.py:9-120)
-#if PYRO_FAST && defined(PYRO_ADV_HALFSLOPE)
-// NOT the default (round 6, measured: tools/build_variant.sh halfslope "-DPYRO_ADV_HALFSLOPE" adv_fast):
-// the form that pays in the compressible and shallow-water kernels keeps two more values alive per
-// cell (a, b), and the three-steps-per-launch instance -- 248-256 registers already -- starts to
-// spill (scratch 0 / 12 -> 20 / 68 B per lane): 8192^2 0.195 -> 0.209 ms per step, 2048^2 18.4 -> 18.0 us.
-// Contracted build: HALF slopes in signed min / max form -- with lo = min(dl, dr),
-// hi = max(dl, dr), a = max(lo, 0), b = min(hi, 0):  limit2 / 2 = max(min((ap - am) / 4, a), b),
-// and the same with half the fourth-order centred slope for limit4 (where dl dr > 0 it shares
-// their sign: stencil.h mc_select_l4); no sign copy, product, compare or select: 10 + 5 instead
-// of 12 + 7 instructions per cell and direction.  The interface states take (1 -+ c) x half slope.
-constexpr double ADV_HALF = 1.0;       // factor of the slope in the interface states
-__device__ __forceinline__ double adv_limit2(double am, double a0, double ap)
-{
-    const double dl = ap - a0, dr = a0 - am;
-    const double a = fmax(fmin(dl, dr), 0.0), b = fmin(fmax(dl, dr), 0.0);
-    return fmax(fmin(0.25 * (ap - am), a), b);
-}
-template <int LIM>
-__device__ __forceinline__ double adv_slope(double l2m, double l20, double l2p, double am1, double a0,
-                                            double ap1)
-{
-    if (LIM == 0) return 0.25 * (ap1 - am1);
-    if (LIM == 1) return l20;
-    const double dl = ap1 - a0, dr = a0 - am1;
-    const double a = fmax(fmin(dl, dr), 0.0), b = fmin(fmax(dl, dr), 0.0);
-    return fmax(fmin((1. / 3.) * (ap1 - am1 - 0.5 * (l2p + l2m)), a), b);
-}
-#else
-constexpr double ADV_HALF = 0.5;
+// (measured, contracted build: HALF slopes in signed min / max form, as in the compressible and
+// shallow-water kernels, keep two more values alive per cell and spill the three-steps-per-launch
+// instance: 8192^2 0.195 -> 0.209 ms per step, 2048^2 18.4 -> 18.0 us; docs/HISTORY.md)
+constexpr double ADV_HALF = 0.5;       // factor of the slope in the interface states
 __device__ __forceinline__ double adv_limit2(double am, double a0, double ap) { return limit2(am, a0, ap); }
 template <int LIM>
 __device__ __forceinline__ double adv_slope(double l2m, double l20, double l2p, double am1, double a0,
@@ -190,19 +162,12 @@ __device__ __forceinline__ double adv_slope(double l2m, double l20, double l2p, 
     const double dr = a0 - am1;
     return mc_select_l4(dc, dl, dr);
 }
-#endif
 
 // LIM: limiter (0 none, 1 MC2, 2 MC4); UNEG / VNEG: u < 0 / v < 0 (upwind side)
 // wavefronts per workgroup (they do not cooperate: no LDS, no barrier).  Four per workgroup,
 // so that the dispatcher hands out four strips at a time, was measured: 24.3 vs 23.2 us at
 // 2048^2, 267 vs 261 us at 8192^2 -- one it is.
-#ifndef PYRO_ADV_PRIO
-#define PYRO_ADV_PRIO 1
-#endif
-#ifndef PYRO_ADV_WPB
-#define PYRO_ADV_WPB 1
-#endif
-constexpr int ADV_WPB = PYRO_ADV_WPB;
+constexpr int ADV_WPB = 1;
 
 template <int LIM, bool UNEG, bool VNEG>
 __global__ __launch_bounds__(64 * ADV_WPB) void k_adv_step(const double *__restrict__ ain,
@@ -277,10 +242,7 @@ __global__ __launch_bounds__(64 * ADV_WPB) void k_adv_step(const double *__restr
     // over two or three periods was measured and changes nothing, and so does issuing the
     // row loads by inline assembly with a hand-placed s_waitcnt vmcnt(2 ADV_PF): 271-274 vs
     // 262-269 us at 8192^2 -- the waits are not the compiler's)
-#ifndef PYRO_ADV_UNR
-#define PYRO_ADV_UNR 1
-#endif
-    constexpr int NR = 6, UNR = PYRO_ADV_UNR * adv_lcm(NR, 6);
+    constexpr int NR = 6, UNR = adv_lcm(NR, 6);
     static_assert(UNR % NR == 0 && UNR % 3 == 0 && UNR % 2 == 0 && UNR % ADV_PF == 0 && UNR <= 36,
                   "ring periods");
     const D2 zero{0.0, 0.0};
@@ -361,7 +323,7 @@ __global__ __launch_bounds__(64 * ADV_WPB) void k_adv_step(const double *__restr
         Fxr[(U + 1) % 2] = Fx;
 #undef ADV_W
     };
-#if !defined(PYRO_EMU) && PYRO_ADV_PRIO
+#if !defined(PYRO_EMU)
     // the wavefronts of a SIMD are served oldest first (comp_wave.hip: the younger ones get
     // what is left and finish alone); they take turns at the priorities instead, by their
     // slot number on the SIMD, one block of the unrolled loop each
@@ -370,7 +332,7 @@ __global__ __launch_bounds__(64 * ADV_WPB) void k_adv_step(const double *__restr
     int turn = (int)(hw_id & 3u);
 #endif
     for (int k0 = ka; k0 <= kb; k0 += UNR) {
-#if !defined(PYRO_EMU) && PYRO_ADV_PRIO
+#if !defined(PYRO_EMU)
         switch (turn & 3) {
         case 0: __builtin_amdgcn_s_setprio(0); break;
         case 1: __builtin_amdgcn_s_setprio(1); break;
@@ -563,16 +525,7 @@ __device__ __forceinline__ bool adv_stage(AdvRings &R, const D2 &in, int k, int 
 
 // wavefronts per SIMD the instances are built for (registers: 84 carried per stage + the
 // rows in flight + ~50 temporaries)
-#ifndef PYRO_ADVM_NT
-#define PYRO_ADVM_NT 0      // non-temporal stores of the final level (developer A/B)
-#endif
-#ifndef PYRO_ADVM_WPE2
-#define PYRO_ADVM_WPE2 2
-#endif
-#ifndef PYRO_ADVM_WPE3
-#define PYRO_ADVM_WPE3 2
-#endif
-constexpr int advm_wpe(int K) { return K <= 1 ? 3 : (K == 2 ? PYRO_ADVM_WPE2 : PYRO_ADVM_WPE3); }
+constexpr int advm_wpe(int K) { return K <= 1 ? 3 : 2; }
 
 template <int LIM, bool UNEG, bool VNEG, int K>
 __global__ __launch_bounds__(64, advm_wpe(K)) void k_adv_multi(const double *__restrict__ ain,
@@ -664,28 +617,21 @@ __global__ __launch_bounds__(64, advm_wpe(K)) void k_adv_multi(const double *__r
             if constexpr (s == K - 1) {
                 if (made) {
                     const size_t ko = (size_t)(ks - TRAIL) * p + ja;
-#if PYRO_ADVM_NT == 1
-                    if (jout[0]) __builtin_nontemporal_store(nxt.a, &aout[ko]);
-                    if (jout[1]) __builtin_nontemporal_store(nxt.b, &aout[ko + 1]);
-#elif PYRO_ADVM_NT == 2     // write-through (sc1): no dirty lines left for the kernel boundary
-                    if (jout[0]) __hip_atomic_store(&aout[ko], nxt.a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (jout[1]) __hip_atomic_store(&aout[ko + 1], nxt.b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
+                    // (non-temporal and write-through stores here were measured: no change)
                     if (jout[0]) aout[ko] = nxt.a;
                     if (jout[1]) aout[ko + 1] = nxt.b;
-#endif
                 }
             }
             cur = nxt;
         });
     };
-#if !defined(PYRO_EMU) && PYRO_ADV_PRIO
+#if !defined(PYRO_EMU)
     unsigned hw_id;
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw_id));
     int turn = (int)(hw_id & 3u);
 #endif
     for (int k0 = ka; k0 <= kb; k0 += UNR) {
-#if !defined(PYRO_EMU) && PYRO_ADV_PRIO
+#if !defined(PYRO_EMU)
         if (P.prio) {
             switch (turn & 3) {
             case 0: __builtin_amdgcn_s_setprio(0); break;

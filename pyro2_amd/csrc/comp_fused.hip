@@ -81,7 +81,7 @@ __device__ __forceinline__ void lds_put(double *b, int t, const Cons &U)
 {
     b[t] = U.d; b[FNT + t] = U.E; b[2 * FNT + t] = U.mx; b[3 * FNT + t] = U.my;
 }
-// developer timing aid (tools/fused_phases.sh): -DPYRO_FUSED_STOP=k ends the
+// developer timing aid (tools/fused_phases.py): -DPYRO_FUSED_STOP=k ends the
 // kernel after phase k, storing one value that depends on the phase's results
 #ifndef PYRO_FUSED_STOP
 #define PYRO_FUSED_STOP 99
@@ -92,13 +92,11 @@ __device__ __forceinline__ void lds_put(double *b, int t, const Cons &U)
         return;                                                                  \
     }
 
-#ifndef PYRO_FUSED_MINW
 // waves per SIMD the register allocation must allow: 4 = two 512-thread
 // workgroups per CU (128 VGPRs, 48 B/lane scratch).  Measured at 8192^2:
 // 6.75 ms vs 9.48 ms with one workgroup per CU (146 VGPRs, no scratch) -- the
 // second workgroup fills the VALU while the first sits in a barrier.
-#define PYRO_FUSED_MINW 4
-#endif
+constexpr int FUSED_MINW = 4;
 
 // STD: the default reconstruction (limiter 2 = 4th-order MC, flattening on) as
 // compile-time constants: straight-line code the compiler schedules across the
@@ -106,7 +104,7 @@ __device__ __forceinline__ void lds_put(double *b, int t, const Cons &U)
 // constant gave 3.59 and was not kept: problems with gravity use this instance
 // too); STD = false reads both from the parameters
 template <int SOLVER, bool STD = false>   // compressible.riemann: 0 HLLC, 1 CGF, 2 HLLC_lm
-__global__ __launch_bounds__(FNT, PYRO_FUSED_MINW) void k_ctu_fused(const double *__restrict__ Uin,
+__global__ __launch_bounds__(FNT, FUSED_MINW) void k_ctu_fused(const double *__restrict__ Uin,
                                                    double *__restrict__ Uout, Geom g, FP P_in,
                                                    int *__restrict__ flag,
                                                    double *__restrict__ partial,
@@ -399,7 +397,7 @@ constexpr int FLDS_DOUBLES_SPH = FLDS_DOUBLES + 2 * FNT;       // + the face pre
 constexpr size_t FLDS_BYTES_SPH = (size_t)FLDS_DOUBLES_SPH * sizeof(double);
 
 template <bool STD, bool FAC>
-__global__ __launch_bounds__(FNT, PYRO_FUSED_MINW) void k_ctu_fused_sph(const double *__restrict__ Uin,
+__global__ __launch_bounds__(FNT, FUSED_MINW) void k_ctu_fused_sph(const double *__restrict__ Uin,
                                                        double *__restrict__ Uout, Geom g, FP P_in,
                                                        SphG G, int *__restrict__ flag,
                                                        double *__restrict__ partial,

@@ -209,7 +209,7 @@ __global__ __launch_bounds__(64, 2) void k_sph_wave(const double *__restrict__ U
     // time -- requested behind the delayed stores --: rebuilt from the primitives every step a conserved
     // state drifts (comp_wave.hip); only row k-3's (source terms on the face states, the other operand of
     // the x viscosity flux) is rebuilt
-#if PYRO_FAST && !defined(PYRO_EMU) && !defined(PYRO_SPHW_NO_DELAY)
+#if PYRO_FAST && !defined(PYRO_EMU)
     constexpr bool SPHW_DELAY = true;
 #else
     constexpr bool SPHW_DELAY = false;
@@ -660,12 +660,10 @@ int comp_step_wave_sph_ex(pyrohip_state *s, const pyrohip_comp_params *p, double
     P.nsb = (g.nx + P.L - 1) / P.L;
     if (P.nsb > 1 && g.nx - (P.nsb - 1) * P.L < g.ng) P.nsb--;
     // (one round: as many strips as wavefront slots; the pairs of the SIMDs told their rows left: comp_wave.hip)
-#if !defined(PYRO_SPHW_NO_EXTRA)
     P.n_extra = p->march_rows > 0 ? 0 : wave_fill_extra(P.ncb, P.nsb, g.nx, 8 * cus);
-#endif
     P.nunits = P.ncb * P.nsb + P.n_extra;
     P.prio_duty = (P.nunits <= 2 * 8 * cus) ? 5 : 0;
-#if !defined(PYRO_EMU) && !defined(PYRO_SPHW_NO_FEEDBACK)
+#if !defined(PYRO_EMU)
     if (P.prio_duty > 0) PYRO_TRY(prio_board_acquire(c, &P.prio_board, &P.prio_tag));
 #endif
     PYRO_TRY(c->reduce.ensure((P.nunits + kMinStageBlocks + 2) * sizeof(double)));

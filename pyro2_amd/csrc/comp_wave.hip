@@ -66,17 +66,13 @@ constexpr int WOUT = 56;          // columns a wavefront updates
 // stages are written in the order that keeps the live ranges short (a value is
 // produced right before the Riemann problem that consumes it); left alone, the
 // scheduler interleaves the stages for ILP and pushes the kernel over 256 VGPRs.
-#if defined(PYRO_EMU) || defined(PYRO_WAVE_NO_SCHED_BARRIER)
+#if defined(PYRO_EMU)
 #define STAGE_FENCE() do {} while (0)
 #else
 #define STAGE_FENCE() __builtin_amdgcn_sched_barrier(0)
 #endif
-#ifndef PYRO_WAVE_PRIO_SHIFT
-#define PYRO_WAVE_PRIO_SHIFT 1    // the priority changes hands in units of 2 rows
-#endif
-#ifndef PYRO_WAVE_MINW
-#define PYRO_WAVE_MINW 2          // waves per SIMD the register allocation must allow
-#endif
+constexpr int WAVE_PRIO_SHIFT = 1;    // the priority changes hands in units of 2 rows
+constexpr int WAVE_MINW = 2;          // waves per SIMD the register allocation must allow
 
 // value of the same variable in lane l-1 / l+1.  The ends of the wavefront are
 // apron lanes whose results are never stored, but what they compute matters
@@ -87,11 +83,12 @@ constexpr int WOUT = 56;          // columns a wavefront updates
 // 0, went to NaN and dragged the wavefront through the slow paths (+8 v_rsq /
 // v_rcp per row, PMC); shifts that keep the own value need a register copy in
 // front of every move (the `old` operand is tied to the destination).  The
-// shuffle variant (emulator, -DPYRO_WAVE_BPERMUTE) keeps the own value.  gfx950 keeps the GFX9 whole-wave DPP shifts (wave_shr:1 /
-// wave_shl:1 move data across all 64 lanes, tools/dpp_probe.hip): two
+// shuffle variant (the emulator's) keeps the own value.  gfx950 keeps the GFX9
+// whole-wave DPP shifts (wave_shr:1 / wave_shl:1 move data across all 64 lanes,
+// tools/dpp_probe.hip): two
 // v_mov_b32_dpp per double, a register-to-register VALU move without the
 // LDS-crossbar round trip of ds_bpermute (__shfl_up / __shfl_down).
-#if !defined(PYRO_EMU) && !defined(PYRO_WAVE_BPERMUTE)
+#if !defined(PYRO_EMU)
 template <int CTRL> __device__ __forceinline__ double lane_dpp(double v)
 {
     int lo = __double2loint(v), hi = __double2hiint(v);
@@ -156,23 +153,8 @@ constexpr size_t WLDS_BYTES = (size_t)(ST_SLOTS * 64 + C_N) * sizeof(double);
 #else
 #define US(name, expr) UC(name)
 #endif
-// ... a uniform that a row uses once (artificial viscosity, the two correction factors, the update's
-// factors, 1 / dx): experiment PYRO_WAVE_FEW_SGPR reads those from the table in the fast build too
-#if defined(PYRO_WAVE_FEW_SGPR)
-#define US1(name, expr) UC(name)
-#else
-#define US1(name, expr) US(name, expr)
-#endif
-#if defined(PYRO_WAVE_FEW_SGPR) && PYRO_WAVE_FEW_SGPR >= 2
-#define US2(name, expr) UC(name)
-#else
-#define US2(name, expr) US(name, expr)
-#endif
-#if defined(PYRO_WAVE_FEW_SGPR) && PYRO_WAVE_FEW_SGPR >= 3
-#define US3(name, expr) UC(name)
-#else
-#define US3(name, expr) US(name, expr)
-#endif
+// (measured: reading the uniforms a row uses once from the table in the fast build too removes
+// the scratch spills of lane masks / base addresses and is 0.5-5 % slower; docs/HISTORY.md)
 // an entry only one of the two builds uses (the table reads are volatile: an unused one
 // would still be issued)
 #if defined(PYRO_EMU)     // (the emulated fast build divides by the operand, not by its reciprocal)
@@ -185,7 +167,7 @@ constexpr size_t WLDS_BYTES = (size_t)(ST_SLOTS * 64 + C_N) * sizeof(double);
 #define UC_FAST(name) 0.0
 #define UC_EXACT(name) UC(name)
 #endif
-#define UC_GASK() GasKTab{ct, US3(GAMMA, P.gamma)}
+#define UC_GASK() GasKTab{ct, US(GAMMA, P.gamma)}
 // (an explicit LDS pointer type: a plain `volatile double *` is a generic pointer
 // that the address-space inference leaves alone, i.e. flat loads through vmcnt)
 #if defined(PYRO_EMU)
@@ -248,7 +230,7 @@ __device__ unsigned long long g_wave_timeline[4 * 65536];
 #endif
 template <int SOLVER, bool STD, bool MOL = false, bool ONE = false, bool RKF = false, bool SRC = true,
           int FINT = -1, bool FB = false>   // SOLVER, STD as k_ctu_fused
-__global__ __launch_bounds__(64, PYRO_WAVE_MINW) void k_ctu_wave(const double *__restrict__ Uin,
+__global__ __launch_bounds__(64, WAVE_MINW) void k_ctu_wave(const double *__restrict__ Uin,
                                                                  double *__restrict__ Uout, Geom g,
                                                                  FP P, int *__restrict__ flag,
                                                                  double *__restrict__ partial,
@@ -461,9 +443,6 @@ __global__ __launch_bounds__(64, PYRO_WAVE_MINW) void k_ctu_wave(const double *_
     auto loadU = [&](int row) {
         if (SADDR) {
             row = row < 0 ? 0 : (row > g.qx - 1 ? g.qx - 1 : row);
-#if defined(PYRO_WAVE_EXP_L2ROWS)      // (timing experiment, WRONG results: every strip re-reads its first 8 rows -- cache hits)
-            row = rbase + ((row - rbase) & 7);
-#endif
             const unsigned off = (unsigned)(row - rbase) * pitch8 + lane8;
             return Cons{*(const double *)(sbase_in + off), *(const double *)(sbase_in + plb + off),
                         *(const double *)(sbase_in + 2 * plb + off), *(const double *)(sbase_in + 3 * plb + off)};
@@ -543,15 +522,11 @@ __global__ __launch_bounds__(64, PYRO_WAVE_MINW) void k_ctu_wave(const double *_
     // u = m / rho, p = (gamma - 1)(E - ...) and back every step drifts: the developed 1024^2 blast (2333 steps)
     // was 1.1e-9 from the oracle instead of 4e-11.  It is read a second time as before (a cache hit), requested
     // behind the delayed stores at the top of the iteration whose end consumes it (Ucx).
-#if !defined(PYRO_WAVE_NO_DELAY)
     constexpr bool REBUILD = (PYRO_FAST != 0) && !MOL && !MAPS && SADDR;   // (viscosity operands only; GPU build)
     // (the bit-faithful build must keep the second read -- rebuilding changes bits -- and has no eight
     // registers for the waiting state: with the delayed stores it spills 76 instead of 28 B per lane,
     // 15.7 -> 17.3 ms per step at 16384^2; the method-of-lines stages are fabric-bound: 2.13 -> 2.15 ms)
     constexpr bool DELAY = REBUILD && SADDR;
-#else
-    constexpr bool REBUILD = false, DELAY = false;                   // (developer A/B)
-#endif
     constexpr bool NOREP = (PYRO_FAST != 0) && (MOL || REBUILD);
     Cons Urep = NOREP ? Cons{1.0, 1.0, 0.0, 0.0} : loadU(i0 - 7);    // row k-3 again, in flight
     Cons Krep = NOREP ? Cons{0.0, 0.0, 0.0, 0.0} : loadK(i0 - 7);
@@ -620,7 +595,7 @@ __global__ __launch_bounds__(64, PYRO_WAVE_MINW) void k_ctu_wave(const double *_
             else if (left < other_left) __builtin_amdgcn_s_setprio(0);
         } else
         if (P.prio_duty > 0) {
-            const int phase = ((k - i0) >> PYRO_WAVE_PRIO_SHIFT) & 7;
+            const int phase = ((k - i0) >> WAVE_PRIO_SHIFT) & 7;
             if (wslot ? (phase < P.prio_duty) : (phase >= P.prio_duty)) __builtin_amdgcn_s_setprio(1);
             else __builtin_amdgcn_s_setprio(0);
         }
@@ -630,17 +605,17 @@ __global__ __launch_bounds__(64, PYRO_WAVE_MINW) void k_ctu_wave(const double *_
             wr[n] = wr[n + 1]; wu[n] = wu[n + 1]; wv[n] = wv[n + 1]; wp[n] = wp[n + 1];
         }
         if (DELAY)     // (row k-4 = window index 0 after the shift: rebuilt, not carried -- eight registers)
-            Uem = prim_to_cons_g(Prim{wr[0], wu[0], wv[0], wp[0]}, US2(GM1, P.gm1), US2(RGM1, P.rgm1));
+            Uem = prim_to_cons_g(Prim{wr[0], wu[0], wv[0], wp[0]}, US(GM1, P.gm1), US(RGM1, P.rgm1));
         else
         Uem = Ue;
         if (NOREP) {
             // (window index 1 = row k-3 after the shift above; floor and signs are in the primitives)
-            Ue = prim_to_cons_g(Prim{wr[1], wu[1], wv[1], wp[1]}, US2(GM1, P.gm1), US2(RGM1, P.rgm1));
+            Ue = prim_to_cons_g(Prim{wr[1], wu[1], wv[1], wp[1]}, US(GM1, P.gm1), US(RGM1, P.rgm1));
         } else {
         Ue = Urep;
         addK(Ue, Krep);
         fix_sign(Ue, k - 3);
-        if (row_in(k - 3) && jin) Ue.d = fmax(Ue.d, US2(SMALLD, P.small_dens));      // clean_state
+        if (row_in(k - 3) && jin) Ue.d = fmax(Ue.d, US(SMALLD, P.small_dens));      // clean_state
         }
         // (issuing this second read of row k-2 in the middle of the iteration instead -- eight
         // registers less while the slopes and the first Riemann problems are worked on -- was
@@ -658,11 +633,11 @@ __global__ __launch_bounds__(64, PYRO_WAVE_MINW) void k_ctu_wave(const double *_
             }
             const bool interior = row_in(k) && jin;
             // (RKF: the stage state is a temporary of the step -- nothing to keep the floor in)
-            if (MOL && !RKF && interior && U.d < US2(SMALLD, P.small_dens))     // clean_state works in place
-                const_cast<double *>(Uin)[(size_t)k * p + jc] = US2(SMALLD, P.small_dens);
-            if (interior) U.d = fmax(U.d, US2(SMALLD, P.small_dens));
+            if (MOL && !RKF && interior && U.d < US(SMALLD, P.small_dens))     // clean_state works in place
+                const_cast<double *>(Uin)[(size_t)k * p + jc] = US(SMALLD, P.small_dens);
+            if (interior) U.d = fmax(U.d, US(SMALLD, P.small_dens));
             bool ok;
-            const Prim q = cons_to_prim_nb(U, US3(GAMMA, P.gamma), ok);
+            const Prim q = cons_to_prim_nb(U, US(GAMMA, P.gamma), ok);
             if (interior && !ok) bad = true;
             wr[4] = q.r; wu[4] = q.u; wv[4] = q.v; wp[4] = q.p;
             if (DELAY) {
@@ -795,7 +770,7 @@ __global__ __launch_bounds__(64, PYRO_WAVE_MINW) void k_ctu_wave(const double *_
                 const size_t kc = (size_t)(ina ? i : g.qx - 1) * p + (ina ? js : g.qy - 1);
                 Ug.d = Uin[kc]; Ug.my = Uin[3 * pl + kc];
                 if (i >= g.ilo && i <= g.ihi && js >= g.jlo && js <= g.jhi)
-                    Ug.d = fmax(Ug.d, US2(SMALLD, P.small_dens));
+                    Ug.d = fmax(Ug.d, US(SMALLD, P.small_dens));
                 sgn = ((j < g.jlo && P.refl_ylo) || (j > g.jhi && P.refl_yhi)) ? -1.0 : 1.0;
                 hp = P.heat ? P.heat[(size_t)(ina ? i : g.qx - 1) * p + (ina ? j : g.qy - 1)] : 0.0;
             }
@@ -803,13 +778,13 @@ __global__ __launch_bounds__(64, PYRO_WAVE_MINW) void k_ctu_wave(const double *_
             // artificial viscosity coefficients of the faces (i, j) in x and (i-1, j)
             // in y (interface.py:366-376: only faces i in [ilo, ihi], j in [jlo, jhi])
             Dn = div_u_vertex_r(q0[1], um, qm[1], up, q0[2], qm[2], vm, vp, UC_EXACT(DX), UC_EXACT(DY),
-                                US1(RDX, P.rdx), US1(RDY, P.rdy));
+                                US(RDX, P.rdx), US(RDY, P.rdy));
             const double Dn_p = lane_p1(Dn);
             double avx = 0.0, avy = 0.0;
             if (i >= g.ilo && (i <= g.ihi || (P.avx_hi && i == g.ihi + 1)) && jin) {
                 const double divU_x = 0.5 * (Dn + Dn_p);
 #if PYRO_FAST
-                avx = US1(CVDX, s_cvdx) * fmax(-divU_x, 0.0);
+                avx = US(CVDX, s_cvdx) * fmax(-divU_x, 0.0);
 #else
                 avx = UC(CVISC) * fmax(-divU_x * UC(DX), 0.0);
 #endif
@@ -817,7 +792,7 @@ __global__ __launch_bounds__(64, PYRO_WAVE_MINW) void k_ctu_wave(const double *_
             if (j >= g.jlo && (j <= g.jhi || (P.avy_hi && j == g.jhi + 1)) && row_in(i - 1)) {
                 const double divU_y = 0.5 * (Dp + Dn);
 #if PYRO_FAST
-                avy = US1(CVDY, s_cvdy) * fmax(-divU_y, 0.0);
+                avy = US(CVDY, s_cvdy) * fmax(-divU_y, 0.0);
 #else
                 avy = UC(CVISC) * fmax(-divU_y * UC(DY), 0.0);
 #endif
@@ -825,7 +800,7 @@ __global__ __launch_bounds__(64, PYRO_WAVE_MINW) void k_ctu_wave(const double *_
             STAGE_FENCE();
             // -- x states of row c, transverse x flux on its lower face
             Trace lo, hi;
-            double gamma = US3(GAMMA, P.gamma);
+            double gamma = US(GAMMA, P.gamma);
             if (MOL) {     // fluxes.py:107-140: V_r[i] = q - ld/2, V_l[i+1] = q + ld/2
                 lo = Trace{q0[0] + -1.0 * 0.5 * dqx[0], q0[1] + -1.0 * 0.5 * dqx[1],
                            q0[2] + -1.0 * 0.5 * dqx[2], q0[3] + -1.0 * 0.5 * dqx[3]};
@@ -833,8 +808,8 @@ __global__ __launch_bounds__(64, PYRO_WAVE_MINW) void k_ctu_wave(const double *_
                            q0[2] + 1.0 * 0.5 * dqx[2], q0[3] + 1.0 * 0.5 * dqx[3]};
             } else
                 trace_states(q0[0], q0[1], q0[2], q0[3], dqx[0], dqx[1], dqx[2], dqx[3], gamma,
-                             US2(DTDX, s_dtdx), lo, hi);
-            double gm1 = UC_EXACT(GM1), rgm1 = US2(RGM1, P.rgm1);
+                             US(DTDX, s_dtdx), lo, hi);
+            double gm1 = UC_EXACT(GM1), rgm1 = US(RGM1, P.rgm1);
             Cons XMn = prim_to_cons_g(Prim{lo.r, lo.un, lo.ut, lo.p}, gm1, rgm1);
             Cons XPn = prim_to_cons_g(Prim{hi.r, hi.un, hi.ut, hi.p}, gm1, rgm1);
             FaceQ qxm{lo.un, lo.ut, lo.p}, qxp{hi.un, hi.ut, hi.p};
@@ -869,7 +844,7 @@ __global__ __launch_bounds__(64, PYRO_WAVE_MINW) void k_ctu_wave(const double *_
                 else {
                 const Cons FxTp = st_get(st, ST_FXT);
 #if PYRO_FAST
-                const double kx = US1(KX, s_kx);
+                const double kx = US(KX, s_kx);
                 YMc = corr_k(st_get(st, ST_YM), FxTn, FxTp, kx);
                 YPc = corr_k(st_get(st, ST_YP), FxTn, FxTp, kx);
 #else
@@ -882,7 +857,7 @@ __global__ __launch_bounds__(64, PYRO_WAVE_MINW) void k_ctu_wave(const double *_
                                                   UC_GASK(), false, P.solid_yl && j == g.jlo), false);
                 // (DELAY: the exact old state of the row, read a second time -- not the rebuilt one)
                 Cons Uv = Uem;
-                if (DELAY) { Uv = Ucx; if (jin) Uv.d = fmax(Uv.d, US2(SMALLD, P.small_dens)); }
+                if (DELAY) { Uv = Ucx; if (jin) Uv.d = fmax(Uv.d, US(SMALLD, P.small_dens)); }
                 const Cons Umy = lane_m1(Uv);
                 Fy.d += avy * (Umy.d - Uv.d);
                 Fy.E += avy * (Umy.E - Uv.E);
@@ -893,7 +868,7 @@ __global__ __launch_bounds__(64, PYRO_WAVE_MINW) void k_ctu_wave(const double *_
             if (!MOL && xface) st_put(st, ST_FXT, FxTn);
             STAGE_FENCE();
             // -- y states of row c, transverse y flux on its lower face
-            gamma = US3(GAMMA, P.gamma);
+            gamma = US(GAMMA, P.gamma);
             if (MOL) {     // (normal / transverse frame of the y direction: un = v, ut = u)
                 lo = Trace{q0[0] + -1.0 * 0.5 * dqy[0], q0[2] + -1.0 * 0.5 * dqy[2],
                            q0[1] + -1.0 * 0.5 * dqy[1], q0[3] + -1.0 * 0.5 * dqy[3]};
@@ -901,8 +876,8 @@ __global__ __launch_bounds__(64, PYRO_WAVE_MINW) void k_ctu_wave(const double *_
                            q0[1] + 1.0 * 0.5 * dqy[1], q0[3] + 1.0 * 0.5 * dqy[3]};
             } else
                 trace_states(q0[0], q0[2], q0[1], q0[3], dqy[0], dqy[2], dqy[1], dqy[3], gamma,
-                             US2(DTDY, s_dtdy), lo, hi);
-            gm1 = UC_EXACT(GM1); rgm1 = US2(RGM1, P.rgm1);
+                             US(DTDY, s_dtdy), lo, hi);
+            gm1 = UC_EXACT(GM1); rgm1 = US(RGM1, P.rgm1);
             Cons YMn = prim_to_cons_g(Prim{lo.r, lo.ut, lo.un, lo.p}, gm1, rgm1);
             Cons YPn = prim_to_cons_g(Prim{hi.r, hi.ut, hi.un, hi.p}, gm1, rgm1);
             FaceQ qym{lo.un, lo.ut, lo.p}, qyp{hi.un, hi.ut, hi.p};
@@ -931,7 +906,7 @@ __global__ __launch_bounds__(64, PYRO_WAVE_MINW) void k_ctu_wave(const double *_
             if (!MOL) {
             const Cons FyTh = lane_p1(FyT);            // FyT at (i, j+1)
 #if PYRO_FAST
-            const double ky = US1(KY, s_ky);
+            const double ky = US(KY, s_ky);
             XMc = corr_k(XMn, FyTh, FyT, ky);
             XPc = corr_k(XPn, FyTh, FyT, ky);
 #else
@@ -949,7 +924,7 @@ __global__ __launch_bounds__(64, PYRO_WAVE_MINW) void k_ctu_wave(const double *_
                 Fxn = from_nf(riemann_face<SOLVER>(to_nf(st_get(st, ST_XPC), true), to_nf(XMc, true),
                                                    UC_GASK(), true, P.solid_xl && i == g.ilo), true);
                 Cons Uxm = Uem;
-                if (DELAY) { Uxm = Ucx; if (jin && row_in(i - 1)) Uxm.d = fmax(Uxm.d, US2(SMALLD, P.small_dens)); }
+                if (DELAY) { Uxm = Ucx; if (jin && row_in(i - 1)) Uxm.d = fmax(Uxm.d, US(SMALLD, P.small_dens)); }
                 Fxn.d += avx * (Uxm.d - Ue.d);
                 Fxn.E += avx * (Uxm.E - Ue.E);
                 Fxn.mx += avx * (Uxm.mx - Ue.mx);
@@ -961,7 +936,7 @@ __global__ __launch_bounds__(64, PYRO_WAVE_MINW) void k_ctu_wave(const double *_
             if (frow && jout) {
                 const Cons Fxp = st_get(st, ST_FX);
                 Cons Ucd = Ucx;
-                Ucd.d = fmax(Ucd.d, US2(SMALLD, P.small_dens));      // clean_state (the rows updated are interior rows)
+                Ucd.d = fmax(Ucd.d, US(SMALLD, P.small_dens));      // clean_state (the rows updated are interior rows)
                 const Cons &Uc = DELAY ? Ucd : Uem;
                 Cons Un;   // simulation.py:377-384
                 if (MOL) {
@@ -1001,7 +976,7 @@ __global__ __launch_bounds__(64, PYRO_WAVE_MINW) void k_ctu_wave(const double *_
                         double *O = P.rk_out + kr;
                         O[0] = Y.d; O[pl] = Y.E; O[2 * pl] = Y.mx; O[3 * pl] = Y.my;
                         double ax, ay;
-                        cfl_speeds(Y, US3(GAMMA, P.gamma), ax, ay);
+                        cfl_speeds(Y, US(GAMMA, P.gamma), ax, ay);
                         st[ST_AX * 64] = fmax(st[ST_AX * 64], pdiv(ax, dxx) + pdiv(ay, dyy));
                     } else {
                     Uout[kr] = Un.d; Uout[pl + kr] = Un.E; Uout[2 * pl + kr] = Un.mx;
@@ -1009,7 +984,7 @@ __global__ __launch_bounds__(64, PYRO_WAVE_MINW) void k_ctu_wave(const double *_
                     }
                 } else {
 #if PYRO_FAST
-                const double cx = US1(CX, s_cx), cy = US1(CY, s_cy);
+                const double cx = US(CX, s_cx), cy = US(CY, s_cy);
                 Un.d = fma(cx, Fxp.d - Fxn.d, fma(cy, Fy.d - Fyh.d, Uc.d));
                 Un.E = fma(cx, Fxp.E - Fxn.E, fma(cy, Fy.E - Fyh.E, Uc.E));
                 Un.mx = fma(cx, Fxp.mx - Fxn.mx, fma(cy, Fy.mx - Fyh.mx, Uc.mx));
@@ -1024,12 +999,6 @@ __global__ __launch_bounds__(64, PYRO_WAVE_MINW) void k_ctu_wave(const double *_
                 const size_t ko = (size_t)(i - 1) * p + j;
                 if (HAVE_SRC)   // simulation.py:406-423
                     grav_update(Un, Uc, UC(GRAV), UC(DT), UC(HEATR), P.heat ? P.heat[ko] : 0.0);
-#if defined(PYRO_WAVE_NT_STORE) && !defined(PYRO_EMU)
-                __builtin_nontemporal_store(Un.d, &Uout[ko]);
-                __builtin_nontemporal_store(Un.E, &Uout[pl + ko]);
-                __builtin_nontemporal_store(Un.mx, &Uout[2 * pl + ko]);
-                __builtin_nontemporal_store(Un.my, &Uout[3 * pl + ko]);
-#else
                 if (DELAY) {
                     Upend = Un;
                 } else if (SADDR) {
@@ -1040,9 +1009,8 @@ __global__ __launch_bounds__(64, PYRO_WAVE_MINW) void k_ctu_wave(const double *_
                 Uout[ko] = Un.d; Uout[pl + ko] = Un.E; Uout[2 * pl + ko] = Un.mx;
                 Uout[3 * pl + ko] = Un.my;
                 }
-#endif
                 double ax, ay;   // CFL: running maxima of the divisors, one division at the end
-                cfl_speeds(Un, US3(GAMMA, P.gamma), ax, ay);
+                cfl_speeds(Un, US(GAMMA, P.gamma), ax, ay);
                 st[ST_AX * 64] = fmax(st[ST_AX * 64], ax);
                 st[ST_AY * 64] = fmax(st[ST_AY * 64], ay);
                 }
@@ -1110,11 +1078,7 @@ static int wave_rows(int nx, int ncb, int slots)
 // eighths -- 3072^2 0.389 -> 0.374 ms, 4096^2 0.639 -> 0.623 with 7, 0.651 with 8 --, the 38-row strips of
 // 2048^2 with six: 0.193 vs 0.195 / 0.201 with 5 / 7; the method-of-lines launches pass L = 0 and keep six:
 // an RK4 step at 4096^2 took 2.20 ms with seven against 2.13)
-#if defined(PYRO_WAVE_PRIO_DUTY_FORCE)      // (developer A/B: tools/wave_timeline.py)
-static int wave_prio_duty(int nwaves, int slots, int) { return nwaves <= 2 * slots ? PYRO_WAVE_PRIO_DUTY_FORCE : 0; }
-#else
 static int wave_prio_duty(int nwaves, int slots, int L) { return nwaves <= 2 * slots ? (L >= 64 ? 7 : 6) : 0; }
-#endif
 
 // the launch geometry of a step on an nx x ny slab: column strips, rows per strip, row strips
 // (a last strip shorter than the ghost width joins its predecessor: the boundary strips of a
@@ -1122,7 +1086,6 @@ static int wave_prio_duty(int nwaves, int slots, int L) { return nwaves <= 2 * s
 // the last strip can go first with the halo exchange beside the interior ones
 // the rows-left board of the SIMD pairs for a launch whose wavefronts take turns (prio_duty > 0): 2^16 SIMD
 // numbers (XCC, SE, SH, CU, SIMD fields of the hardware id) x 2 slots, zeroed once, tagged per launch
-#if !defined(PYRO_WAVE_NO_FEEDBACK)
 static int wave_prio_feedback(pyrohip_ctx *c, FP &P)
 {
     P.prio_board = nullptr;
@@ -1132,15 +1095,12 @@ static int wave_prio_feedback(pyrohip_ctx *c, FP &P)
 #endif
     return 0;
 }
-#else
-static int wave_prio_feedback(pyrohip_ctx *, FP &P) { P.prio_board = nullptr; return 0; }
-#endif
 struct WaveGeom { int ncb, L, nsb, overlap; };
 static WaveGeom wave_geometry(int nx, int ny, int ng, int cus, int march_rows)
 {
     WaveGeom w;
     w.ncb = (ny + WOUT - 1) / WOUT;
-    w.L = wave_rows(nx, w.ncb, 4 * PYRO_WAVE_MINW * cus);      // slots: wavefronts resident at once
+    w.L = wave_rows(nx, w.ncb, 4 * WAVE_MINW * cus);      // slots: wavefronts resident at once
     if (march_rows > 0) w.L = march_rows < nx ? march_rows : nx;
     w.nsb = (nx + w.L - 1) / w.L;
     if (w.nsb > 1 && nx - (w.nsb - 1) * w.L < ng) w.nsb--;
@@ -1152,21 +1112,16 @@ static WaveGeom wave_geometry(int nx, int ny, int ng, int cus, int march_rows)
 // -- and the launch lasts as long as its last wavefront).  So the first n_extra column strips are cut into
 // nsb + 1 row strips instead of nsb: as many strips as slots.  Single domain only (a slab's strips are
 // its protocol), not with a strip length the caller chose.
-#if !defined(PYRO_WAVE_NO_EXTRA)
 static int wave_extra_units(const WaveGeom &w, int nx, int slots, int march_rows)
 {
     return march_rows > 0 ? 0 : wave_fill_extra(w.ncb, w.nsb, nx, slots);
 }
-#else
-static int wave_extra_units(const WaveGeom &, int, int, int) { return 0; }
-#endif
 // Many-round launches: the slots empty over the last strip's life (16384^2: 1815 / 1319 / 737 / 486 of 2048 wavefronts
 // alive 400 / 300 / 200 / 100 us before the end of an 8.4 ms launch, tools/wave_timeline.py: ~2.7 % of the launch, 3.5 % at
 // 8192^2).  So the row strips of the last round's worth of units are cut in two, and every XCD's queue of units ends
 // with its share of them (the kernel's unit numbering): the drain lasts a short strip's life.  Single domain,
 // launches of >= 4 rounds.  -> number of short strips (0: none), *Ls their length,
 // *nsb_long the long ones in front
-#if !defined(PYRO_WAVE_NO_SHORT_TAIL)
 static int wave_short_tail(const WaveGeom &w, int nx, int slots, int march_rows, int *Ls, int *nsb_long)
 {
     (void)march_rows;
@@ -1174,27 +1129,20 @@ static int wave_short_tail(const WaveGeom &w, int nx, int slots, int march_rows,
     // (measured, Gcell/s with halves / thirds / quarters: 16384^2 (126-row strips) 31.95 / 32.00 / 32.12, 8192^2 (59 rows)
     // 30.10 / 30.07 / 29.99, 6144^2 28.4 / 28.35 / 28.07; without the tail 31.75 / 29.7 / 27.65; a region of half a
     // round of units 31.81 / 29.85 / 27.85, of a round and a half 31.97 / 30.02 / 28.20: short strips of about 30 rows)
-#ifndef PYRO_WAVE_TAIL_DIV
-#define PYRO_WAVE_TAIL_DIV (w.L >= 100 ? 4 : 2)
-#endif
-#ifndef PYRO_WAVE_TAIL_ROUNDS_X2
-#define PYRO_WAVE_TAIL_ROUNDS_X2 2
-#endif
+    constexpr int TAIL_ROUNDS_X2 = 2;                      // half rounds of units the short region replaces
     const int nr1 = (slots + w.ncb - 1) / w.ncb;           // row strips of one round of units
     if (w.nsb < 4 * nr1) return 0;
-    const int nr = (nr1 * PYRO_WAVE_TAIL_ROUNDS_X2 + 1) / 2;
+    const int nr = (nr1 * TAIL_ROUNDS_X2 + 1) / 2;
     const int nl = w.nsb - nr;
     const int rows = nx - nl * w.L;                        // rows of the short region (>= 1: nsb strips cover nx)
-    const int ls = (w.L + PYRO_WAVE_TAIL_DIV - 1) / PYRO_WAVE_TAIL_DIV;
+    const int tail_div = w.L >= 100 ? 4 : 2;               // a short strip is this fraction of a long one
+    const int ls = (w.L + tail_div - 1) / tail_div;
     int ns = (rows + ls - 1) / ls;
     if (ns > 1 && rows - (ns - 1) * ls < 4) ns--;          // (a last strip of < 4 rows joins its predecessor)
     if (rows < 8 || ns < 1) return 0;
     *Ls = ls; *nsb_long = nl;
     return ns;
 }
-#else
-static int wave_short_tail(const WaveGeom &, int, int, int, int *, int *) { return 0; }
-#endif
 #if !PYRO_FAST
 // (for callers that want to know before they launch: bench.py's scaling line, the tests of
 // the decomposed runs)  out: ncb, L, nsb, overlap, wavefronts, resident slots
@@ -1202,7 +1150,7 @@ int comp_wave_geometry(int nx, int ny, int ng, int cus, int march_rows, int *out
 {
     const WaveGeom w = wave_geometry(nx, ny, ng, cus > 0 ? cus : 256, march_rows);
     out[0] = w.ncb; out[1] = w.L; out[2] = w.nsb; out[3] = w.overlap;
-    out[4] = w.ncb * w.nsb; out[5] = 4 * PYRO_WAVE_MINW * (cus > 0 ? cus : 256);
+    out[4] = w.ncb * w.nsb; out[5] = 4 * WAVE_MINW * (cus > 0 ? cus : 256);
     return 0;
 }
 #endif
@@ -1225,18 +1173,17 @@ int comp_step_wave_ex(pyrohip_state *s, const pyrohip_comp_params *p, double dt,
     // exchange of its new boundary rows (overlapped when the strips allow it), so the
     // protocol does not depend on this rank's geometry
     const bool post = s->nb_set && comm_can_overlap(s);
-    P.n_extra = (s->nb_set || post) ? 0 : wave_extra_units(wg, g.nx, 4 * PYRO_WAVE_MINW * cus, p->march_rows);
+    P.n_extra = (s->nb_set || post) ? 0 : wave_extra_units(wg, g.nx, 4 * WAVE_MINW * cus, p->march_rows);
     int nsb_long = nsb;
     if (!s->nb_set && !post && !(S && s->pol_next))
-        P.n_short = wave_short_tail(wg, g.nx, 4 * PYRO_WAVE_MINW * cus, p->march_rows, &P.Ls, &nsb_long);
+        P.n_short = wave_short_tail(wg, g.nx, 4 * WAVE_MINW * cus, p->march_rows, &P.Ls, &nsb_long);
     if (P.n_short > 0) { P.nsb = nsb_long + P.n_short; P.units_short = P.ncb * P.n_short; }
-#if !defined(PYRO_WAVE_NO_SLAB_TAIL)
     // (a slab with the boundary strips on the halo stream: the interior launch ends with short strips too -- the
     // row strips in front of the last boundary strip, which keeps its rows; strip lengths that divide only)
     int slab_short = 0;
     if (post && wg.overlap) {
         int ls = 0, nl1 = 0;
-        const int ns1 = wave_short_tail(wg, g.nx, 4 * PYRO_WAVE_MINW * cus, 0, &ls, &nl1);
+        const int ns1 = wave_short_tail(wg, g.nx, 4 * WAVE_MINW * cus, 0, &ls, &nl1);
         const int div = ls > 0 ? (P.L + ls - 1) / ls : 0;
         const int nr = nsb - nl1;                          // (row strips of one round of units: wave_short_tail)
         if (ns1 > 0 && div >= 2 && P.L % div == 0 && nsb - nr - 1 >= 2) {
@@ -1247,9 +1194,6 @@ int comp_step_wave_ex(pyrohip_state *s, const pyrohip_comp_params *p, double dt,
             slab_short = P.ncb * P.n_short;
         }
     }
-#else
-    const int slab_short = 0;
-#endif
     const int nwg = P.ncb * P.nsb + P.n_extra;
     PYRO_TRY(c->reduce.ensure((nwg + kMinStageBlocks + 2) * sizeof(double)));
     double *part = (double *)c->reduce.p;
@@ -1265,7 +1209,7 @@ int comp_step_wave_ex(pyrohip_state *s, const pyrohip_comp_params *p, double dt,
         {k_ctu_wave<1, false, false, false, false, false>, k_ctu_wave<1, true, false, false, false, false>},
         {k_ctu_wave<2, false, false, false, false, false>, k_ctu_wave<2, true, false, false, false, false>}};
     const KernelT (*kernels)[2] = P.have_src ? kernels_src : kernels_nosrc;
-#if !defined(PYRO_EMU) && !defined(PYRO_WAVE_NO_FEEDBACK)
+#if !defined(PYRO_EMU)
     // ... with the rows-left board of the SIMD pairs (launches of one or two rounds)
     static const KernelT kernels_src_fb[3][2] = {
         {k_ctu_wave<0, false, false, false, false, true, -1, true>, k_ctu_wave<0, true, false, false, false, true, -1, true>},
@@ -1310,7 +1254,7 @@ int comp_step_wave_ex(pyrohip_state *s, const pyrohip_comp_params *p, double dt,
         P.sb_first = 1; P.sb_step = 1;
         P.nunits = (P.nsb - 2) * P.ncb;
         P.units_short = slab_short;
-        P.prio_duty = wave_prio_duty(nwg, 4 * PYRO_WAVE_MINW * cus, P.L);
+        P.prio_duty = wave_prio_duty(nwg, 4 * WAVE_MINW * cus, P.L);
         const int nblk = slab_short > 0 ? 8 * ((P.nunits - slab_short + 7) / 8 + (slab_short + 7) / 8)
                                         : 8 * ((P.nunits + 7) / 8);
         PYRO_LAUNCH(c, "k_ctu_wave", kernels[solver][std_rec], dim3(nblk), dim3(64),
@@ -1325,7 +1269,7 @@ int comp_step_wave_ex(pyrohip_state *s, const pyrohip_comp_params *p, double dt,
         return rc;
     }
     P.nunits = nwg;
-    P.prio_duty = wave_prio_duty(nwg, 4 * PYRO_WAVE_MINW * cus, P.L);
+    P.prio_duty = wave_prio_duty(nwg, 4 * WAVE_MINW * cus, P.L);
     PYRO_TRY(wave_prio_feedback(c, P));
     if (S && s->pol_next && !post) {
         // this launch is the whole step (pyrohip_comp_evolve): ghost cells read through the
@@ -1390,7 +1334,7 @@ int comp_rk_rhs_wave(pyrohip_state *s, const pyrohip_comp_params *p, pyrohip_sta
     const int cus = c->num_cus > 0 ? c->num_cus : 256;
     const WaveGeom wg = wave_geometry(g.nx, g.ny, g.ng, cus, p->march_rows);
     P.ncb = wg.ncb; P.L = wg.L; P.nsb = wg.nsb;
-    P.n_extra = s->nb_set ? 0 : wave_extra_units(wg, g.nx, 4 * PYRO_WAVE_MINW * cus, p->march_rows);
+    P.n_extra = s->nb_set ? 0 : wave_extra_units(wg, g.nx, 4 * WAVE_MINW * cus, p->march_rows);
     const int nwg = P.ncb * wg.nsb + P.n_extra;
     PYRO_TRY(c->reduce.ensure((nwg + kMinStageBlocks + 2) * sizeof(double)));
     using KernelT = void (*)(const double *, double *, Geom, FP, int *, double *,
@@ -1402,7 +1346,7 @@ int comp_rk_rhs_wave(pyrohip_state *s, const pyrohip_comp_params *p, pyrohip_sta
     const int solver = (p->riemann == 1 || p->riemann == 2) ? p->riemann : 0;
     const int std_rec = (p->limiter == 2 && p->use_flattening) ? 1 : 0;
     P.nunits = nwg;
-    P.prio_duty = wave_prio_duty(nwg, 4 * PYRO_WAVE_MINW * cus, 0);
+    P.prio_duty = wave_prio_duty(nwg, 4 * WAVE_MINW * cus, 0);
     // (no rows-left board for the method-of-lines launches: measured, an RK4 step at 4096^2 2.20 ms with it, 2.14 without)
     PYRO_LAUNCH(c, "k_ctu_wave_mol", kernels[solver][std_rec], dim3(8 * ((nwg + 7) / 8)), dim3(64), WLDS_BYTES,
                 (const double *)Uin, Uout, g, P, s->d_flag, (double *)c->reduce.p, nullptr);
@@ -1442,7 +1386,7 @@ int comp_rk_step_wave(pyrohip_state *s, const pyrohip_comp_params *p, pyrohip_st
     const int cus = c->num_cus > 0 ? c->num_cus : 256;
     const WaveGeom wg = wave_geometry(g.nx, g.ny, g.ng, cus, p->march_rows);
     P.ncb = wg.ncb; P.L = wg.L; P.nsb = wg.nsb;
-    P.n_extra = s->nb_set ? 0 : wave_extra_units(wg, g.nx, 4 * PYRO_WAVE_MINW * cus, p->march_rows);
+    P.n_extra = s->nb_set ? 0 : wave_extra_units(wg, g.nx, 4 * WAVE_MINW * cus, p->march_rows);
     const int nwg = P.ncb * wg.nsb + P.n_extra;
     PYRO_TRY(c->reduce.ensure((nwg + kMinStageBlocks + 2) * sizeof(double)));
     double *part = (double *)c->reduce.p;
@@ -1451,7 +1395,7 @@ int comp_rk_step_wave(pyrohip_state *s, const pyrohip_comp_params *p, pyrohip_st
         {k_ctu_wave<0, false, true>, k_ctu_wave<0, true, true>},
         {k_ctu_wave<1, false, true>, k_ctu_wave<1, true, true>},
         {k_ctu_wave<2, false, true>, k_ctu_wave<2, true, true>}};
-#if PYRO_FAST && !defined(PYRO_EMU) && !defined(PYRO_RK_ONE_INSTANCE)
+#if PYRO_FAST && !defined(PYRO_EMU)
     static const KernelT later_mid[3][2] = {
         {k_ctu_wave<0, false, true, false, true, true, 0>, k_ctu_wave<0, true, true, false, true, true, 0>},
         {k_ctu_wave<1, false, true, false, true, true, 0>, k_ctu_wave<1, true, true, false, true, true, 0>},
@@ -1470,7 +1414,7 @@ int comp_rk_step_wave(pyrohip_state *s, const pyrohip_comp_params *p, pyrohip_st
     const int solver = (p->riemann == 1 || p->riemann == 2) ? p->riemann : 0;
     const int std_rec = (p->limiter == 2 && p->use_flattening) ? 1 : 0;
     P.nunits = nwg;
-    P.prio_duty = wave_prio_duty(nwg, 4 * PYRO_WAVE_MINW * cus, 0);
+    P.prio_duty = wave_prio_duty(nwg, 4 * WAVE_MINW * cus, 0);
     // (no rows-left board for the method-of-lines launches: measured, an RK4 step at 4096^2 2.20 ms with it, 2.14 without)
     const dim3 grid(8 * ((nwg + 7) / 8)), block(64);
     // stage 0: the state itself, ghost cells filled in memory (they stay the state's "stale"

@@ -29,16 +29,13 @@ inline namespace hydro_exact {
 // the ~12 of the IEEE sequence; divisions are ~40 % of this solver's VALU work
 // (profiles/r01_fused_8192_pmc.json).  Parity of the fast build is
 // tolerance-tested (north_star: 1e-10; 606-step quad and 945-step rt
-// regressions included), not bit-tested.  A second Newton step (full double
-// precision) costs 3 % of the step time: -DPYRO_RCP_NEWTON2.
+// regressions included), not bit-tested.  (Measured: a second Newton step, full
+// double precision, costs 3 % of the step time.)
 #if PYRO_FAST && !defined(PYRO_EMU)
 __device__ __forceinline__ double prcp(double b)
 {
     double r = __builtin_amdgcn_rcp(b);
     r = fma(fma(-b, r, 1.0), r, r);
-#ifdef PYRO_RCP_NEWTON2
-    r = fma(fma(-b, r, 1.0), r, r);
-#endif
     return r;
 }
 __device__ __forceinline__ double pdiv(double a, double b) { return a * prcp(b); }
@@ -54,10 +51,6 @@ __device__ __forceinline__ double psqrt(double x)
     const double r = fma(-h, g, 0.5);
     g = fma(g, r, g);
     h = fma(h, r, h);
-#ifdef PYRO_RCP_NEWTON2
-    const double d = fma(-g, g, x);   // residual correction: full double precision
-    g = fma(d, h, g);
-#endif
     return (x > 0.0) ? g : 0.0;
 }
 // the same without the x > 0 select, for arguments that are positive by
@@ -71,10 +64,6 @@ __device__ __forceinline__ double psqrt_nc(double x)
     const double r = fma(-h, g, 0.5);
     g = fma(g, r, g);
     h = fma(h, r, h);
-#ifdef PYRO_RCP_NEWTON2
-    const double d = fma(-g, g, x);
-    g = fma(d, h, g);
-#endif
     return g;
 }
 // sqrt(x) and 1/sqrt(x) of a strictly positive, normal argument from ONE
@@ -99,7 +88,7 @@ __device__ __forceinline__ double prsqrt(double x)
     const double h = 0.5 * y;
     return fma(y, fma(-h, x * y, 0.5), y);
 }
-#elif !PYRO_FAST && !defined(PYRO_EMU) && !defined(PYRO_IEEE_LIBCALLS)
+#elif !PYRO_FAST && !defined(PYRO_EMU)
 // Bit-faithful build on the GPU: IEEE-correct division and square root WITHOUT the
 // exponent scaling and the special-case fix-up of the compiler's expansion
 // (v_div_scale x 2, v_div_fmas, v_div_fixup; v_cmp_class / v_ldexp around the square
@@ -113,7 +102,7 @@ __device__ __forceinline__ double prsqrt(double x)
 // positivity checks.  8 instead of 11 instructions per division, 10 instead of 15 per
 // square root; bit-identity with `/` and sqrt() is probed on the GPU over 2^26 operand
 // pairs (tools/div_probe.hip -> profiles/r03_div_probe.txt) and pinned by the parity tests
-// of the bit-faithful build.  -DPYRO_IEEE_LIBCALLS restores the plain expressions.
+// of the bit-faithful build.
 __device__ __forceinline__ double prcp(double b)
 {
     double r = __builtin_amdgcn_rcp(b);
@@ -205,7 +194,7 @@ __device__ __forceinline__ double pdivr(double a, double b, double rb) { (void)r
 __device__ __forceinline__ double pvel(double m, double d, double rd)
 {
     const double q = pdivr(m, d, rd);
-#if !PYRO_FAST && !defined(PYRO_EMU) && !defined(PYRO_IEEE_LIBCALLS)
+#if !PYRO_FAST && !defined(PYRO_EMU)
     return (m == 0.0) ? m : q;
 #else
     return q;

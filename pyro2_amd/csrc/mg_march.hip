@@ -28,10 +28,6 @@
 #include "stencil.h"
 #include <type_traits>
 
-#ifndef MGM_SKIP
-#define MGM_SKIP 1     // no steps past the last one a stored row depends on (mgm_march)
-#endif
-
 namespace pyro {
 namespace {
 
@@ -377,11 +373,8 @@ __device__ __forceinline__ void mgm_march(const MGMarch &A, const Part &P, doubl
         }
     };
 
-#if MGM_SKIP
+    // no steps past the last one a stored row depends on (mgm_march)
     const int nsteps = (P.nload + NP < sk_hi + 1) ? P.nload + NP : sk_hi + 1;
-#else
-    const int nsteps = P.nload + NP;
-#endif
     for (int k0 = 0; k0 < nsteps; k0 += W)
         static_for<W>([&](auto uc) __attribute__((always_inline)) { step(uc, k0); });
     if constexpr (TAIL == 2) {

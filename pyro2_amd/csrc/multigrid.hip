@@ -263,10 +263,7 @@ constexpr int MG_SMALL_TILES_DEFAULT = 192;         // workgroups aimed at on sm
                                                    // one workgroup per CU: more than 256 is two rounds))
 constexpr int MGS_CELLS = 66 * 66;                 // single-tile levels: n <= 64
 constexpr size_t MGS_LDS = (size_t)2 * MGS_CELLS * sizeof(double);
-#ifndef PYRO_MGW_RI
-#define PYRO_MGW_RI 64
-#endif
-constexpr int MGW_RI = PYRO_MGW_RI, MGW_LP = 128, MGW_NT = 16 * MGW_RI, MGW_KMAX = 5;
+constexpr int MGW_RI = 64, MGW_LP = 128, MGW_NT = 16 * MGW_RI, MGW_KMAX = 5;
 constexpr size_t MGW_LDS = (size_t)MGW_RI * MGW_LP * sizeof(double);   // v only; f in registers
 
 struct MGTile {

@@ -30,7 +30,7 @@ template <bool FAC> struct SphAt {
 };
 // CGF interface state, its flux without the pressure and its pressure
 // (riemann_flux(return_cons=True) + cons_to_prim, unsplit_fluxes.py:411-423)
-#if PYRO_FAST && !defined(PYRO_SPHF_RESTATED)      // (PYRO_SPHF_RESTATED: developer A/B)
+#if PYRO_FAST
 // Contracted build (round 6): the two-shock solver of riemann.py:8-310 written for the instruction
 // count -- the bit-faithful restatement (hydro.h: cgf_state, then cons_to_prim and cons_flux_n of
 // the conserved interface state) issues 13 quarter-rate reciprocals / roots per face, this one 5
@@ -104,11 +104,6 @@ __device__ __forceinline__ Cons sphf_face(const Cons &Ul, const Cons &Ur, double
     F.mn = F.d * un_s;
     F.mt = F.d * ut_s;
     F.E = (fma(0.5 * rho_s, fma(un_s, un_s, ut_s * ut_s), rhoe_s) + pface) * un_s;
-#if defined(PYRO_EMU) && defined(SPHF_DEBUG)
-    if (!(pface == pface) || !(F.d == F.d) || !(F.E == F.E))
-        printf("NAN face: l %.17g %.17g %.17g %.17g r %.17g %.17g %.17g %.17g x %d wall %d ustar %g pstar %g rho_s %g rhoe_s %g un_s %g\n",
-               l.d, l.E, l.mn, l.mt, r.d, r.E, r.mn, r.mt, (int)x, (int)wall, ustar, pstar, rho_s, rhoe_s, un_s);
-#endif
     return from_nf(F, x);
 }
 #else

@@ -95,7 +95,7 @@ __device__ __forceinline__ V4 sw_cons_flux(const V4 &U, double g, bool x)
 // characteristic tracing of one cell in one direction, interface.py:5-213:
 // primitive states on the cell's lower face (q_r[face]) and upper face
 // (q_l[face+1])
-#if PYRO_FAST && !defined(SWE_DENSE_TRACE)
+#if PYRO_FAST
 // the same sums without the terms that are structurally zero: l_0 . dq = (dq_h / h - dq_n / c) / 2,
 // l_2 . dq = -(dq_h / h + dq_n / c) / 2 (sic: the reference's sign), l_1 . dq = dq_t, l_3 . dq = dq_X;
 // beta_l of wave 2 and beta_r of wave 0 vanish (e_2 - e_2, e_0 - e_0); r_0 = (h, -c), r_2 = (h, c)
@@ -221,7 +221,7 @@ __device__ __forceinline__ void sw_trace(const double q[4], const double dq[4], 
 #endif
 
 // interface.py:216-385
-#if PYRO_FAST && !defined(SWE_DENSE_ROE)
+#if PYRO_FAST
 // The contracted build's Roe solver: the reference's formulas with every quotient and root that
 // shares an operand taken ONCE (round 6; the straightforward form below has ~25 reciprocal /
 // root evaluations per face -- Ul_n / sqrt(h_l), Ur_n / sqrt(h_r), ... / (sqrt(h_l) + sqrt(h_r))
@@ -319,21 +319,10 @@ __device__ __forceinline__ V4 sw_roe(const V4 &Ul, const V4 &Ur, double g, bool 
         lambda[0] = pdiv(lambda[0] * (u_star - c_star - lambda[0]), u_star - c_star - (un_l - c_l));
     if (fabs(lambda[2]) < tol)
         lambda[2] = pdiv(lambda[2] * (u_star + c_star - lambda[2]), u_star + c_star - (un_r + c_r));
-#if PYRO_FAST && !defined(SWE_DENSE_ROE)
-    {   // K_0 = (1, u - c, u_t), K_1 = e_t, K_2 = (1, u + c, u_t), K_3 = e_X: the non-zero terms only
-        const double w0 = 0.5 * alpha[0] * fabs(lambda[0]), w1 = 0.5 * alpha[1] * fabs(lambda[1]);
-        const double w2 = 0.5 * alpha[2] * fabs(lambda[2]), w3 = 0.5 * alpha[3] * fabs(lambda[3]);
-        F.a[0] -= w0 + w2;
-        F.a[im] -= w0 * (un_roe - c_roe) + w2 * (un_roe + c_roe);
-        F.a[it] -= (w0 + w2) * U_roe[it] + w1;
-        F.a[3] -= w3;
-    }
-#else
 #pragma unroll
     for (int n = 0; n < 4; n++)
 #pragma unroll
         for (int m = 0; m < 4; m++) F.a[n] -= 0.5 * alpha[m] * fabs(lambda[m]) * K[m][n];
-#endif
     return F;
 }
 #endif
@@ -568,7 +557,7 @@ __device__ __forceinline__ V4 sww_p1(const V4 &v) { return V4{{sww_p1(v.a[0]), s
 template <int RS>
 __device__ __forceinline__ V4 sww_riemann(const V4 &Ul, const V4 &Ur, double g, bool x, double sg)
 {
-#if PYRO_FAST && !defined(SWE_DENSE_ROE)
+#if PYRO_FAST
     return RS == 1 ? sw_hllc(Ul, Ur, g, x) : sw_roe(Ul, Ur, g, x, sg);
 #else
     (void)sg;
@@ -667,7 +656,7 @@ __global__ __launch_bounds__(64, 2) void k_sw_wave(const double *__restrict__ Ui
     // wait for the prefetched row included the stores issued just before it.  The old state the update
     // starts from is still read a second time (rebuilt from the primitives every step a conserved state
     // drifts: comp_wave.hip), requested behind the delayed stores at the top of the iteration that consumes it.
-#if PYRO_FAST && !defined(PYRO_EMU) && !defined(PYRO_SWW_NO_DELAY)
+#if PYRO_FAST && !defined(PYRO_EMU)
     constexpr bool SWW_DELAY = true;
 #else
     constexpr bool SWW_DELAY = false;
@@ -862,12 +851,6 @@ static int sww_rows(int nx, int ncb, int cus)
     return best;
 }
 
-#if !defined(PYRO_SWW_NO_EXTRA)
-static int sww_fill_extra(int ncb, int nsb, int nx, int slots) { return wave_fill_extra(ncb, nsb, nx, slots); }
-#else
-static int sww_fill_extra(int, int, int, int) { return 0; }
-#endif
-
 // ghost frame of the four planes from one buffer to the other (1-d grid: 2 ng blocks of
 // columns for the ghost rows, then row blocks for the ghost columns)
 __global__ __launch_bounds__(256) void k_sw_copy_frame(const double *__restrict__ src,
@@ -913,17 +896,15 @@ int swe_step_wave(pyrohip_state *s, double dx, double dy, double grav, int limit
     P.ncb = (g.ny + SWW_OUT - 1) / SWW_OUT;
     P.L = sww_rows(g.nx, P.ncb, c->num_cus > 0 ? c->num_cus : 256);
     P.nsb = (g.nx + P.L - 1) / P.L;
-    P.n_extra = sww_fill_extra(P.ncb, P.nsb, g.nx, slots);
+    P.n_extra = wave_fill_extra(P.ncb, P.nsb, g.nx, slots);
     P.nunits = P.ncb * P.nsb + P.n_extra;
     if (nparts) *nparts = P.nunits;
-    {
-        // one round of resident wavefronts: the pair of a SIMD ends together -- the one with more rows left
-        // takes the priority (GPU; comp_wave.hip), turns by phase otherwise
-        P.prio_duty = (P.nunits <= slots) ? 6 : 0;
-#if !defined(PYRO_EMU) && !defined(PYRO_SWW_NO_FEEDBACK)
-        if (P.prio_duty > 0) PYRO_TRY(prio_board_acquire(c, &P.prio_board, &P.prio_tag));
+    // one round of resident wavefronts: the pair of a SIMD ends together -- the one with more rows left
+    // takes the priority (GPU; comp_wave.hip), turns by phase otherwise
+    P.prio_duty = (P.nunits <= slots) ? 6 : 0;
+#if !defined(PYRO_EMU)
+    if (P.prio_duty > 0) PYRO_TRY(prio_board_acquire(c, &P.prio_board, &P.prio_tag));
 #endif
-    }
     double *Uout = s->alt_base + geom_lead(g);
     const dim3 grid(8 * ((P.nunits + 7) / 8)), block(64);
     using KernelT = void (*)(const double *, double *, Geom, SWW, const StepScalars *, double *);
@@ -955,7 +936,7 @@ int swe_wave_units(const Geom &g, int cus)
     const int ncb = (g.ny + SWW_OUT - 1) / SWW_OUT;
     const int L = sww_rows(g.nx, ncb, cus > 0 ? cus : 256);
     const int nsb = (g.nx + L - 1) / L;
-    return ncb * nsb + sww_fill_extra(ncb, nsb, g.nx, 8 * (cus > 0 ? cus : 256));
+    return ncb * nsb + wave_fill_extra(ncb, nsb, g.nx, 8 * (cus > 0 ? cus : 256));
 }
 #endif
 

@@ -1,8 +1,8 @@
 #!/bin/bash
 # developer tool: a second library that differs from the product build in the flags of SOME units
 # (for A/B runs on the GPU box through PYRO2_AMD_LIB); the other objects are the product build's.
-#   tools/build_variant.sh w1 "-DPYRO_ADVM_WPE3=1" advection adv_fast
-# -> pyro2_amd/lib/libpyrohip_w1.so
+#   tools/build_variant.sh tl "-DPYRO_WAVE_TIMELINE" wave_fast
+# -> pyro2_amd/lib/libpyrohip_tl.so
 set -e
 name=$1; flags=$2; shift 2
 cd "$(dirname "$0")/.."

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """time of k_ctu_fused truncated after phase k (libraries built with
--DPYRO_FUSED_STOP=k, see tools/fused_phases.sh) -- developer tool"""
+tools/build_variant.sh stopK "-DPYRO_FUSED_STOP=k" fused_fast, run through PYRO2_AMD_LIB) -- developer tool"""
 import os
 import sys
 
