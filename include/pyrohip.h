@@ -637,6 +637,50 @@ int pyrohip_bgv_rhs(pyrohip_state *s, pyrohip_mg *mg, int iw, int comp, double d
    8 u_MAC, 9 v_MAC, 10 advect_x, 11 advect_y -> host (qx, qy)              */
 int pyrohip_inc_stage_dump(pyrohip_state *s, int which, double *host);
 
+/* ---- lm_atm: low Mach number atmosphere (pyro/lm_atm) --------------------
+   The state holds the solver's eight variables in the order it registers them:
+   density, x-velocity, y-velocity, eint, phi-MAC, phi, gradp_x, gradp_y
+   (ng >= 4).  mg: a pyrohip_mg with the state's nx (= ny) and the BCs of phi.
+   No field-sized array crosses to the host in any of these calls.            */
+/* the 1-d base state rho0, p0, beta0 = p0^(1/gamma) and beta0 on the y edges
+   (qy doubles each), once per simulation; allocates the solver's work area   */
+int pyrohip_lm_set_base(pyrohip_state *s, const double *rho0, const double *p0,
+                        const double *beta0, const double *beta0_edges);
+/* method_compute_timestep (simulation.py:138-178) on the device.  out6 = dt,
+   max|u|, max|v| over the interior, max|u|, max|v| over the whole array (the
+   reference's == 0 tests), F_buoy = max |rho' g| / rho                       */
+int pyrohip_lm_dt(pyrohip_state *s, double dx, double dy, double cfl, double grav,
+                  double *out6);
+/* variable coefficients of mg from device data: eta = beta0^2 / rho of the
+   state's density on the finest level, then the ghost fill (the density's
+   BCs) / edge coefficient / restriction chain of pyrohip_mg_set_coeffs       */
+int pyrohip_lm_mg_coeffs(pyrohip_state *s, pyrohip_mg *mg);
+/* 1. coeff = beta0 / rho and source = rho' g / rho with their ghost fills,
+      get_interface_states with coeff * grad p and the source,
+      riemann_and_upwind, mg.f = div(beta0 U_MAC), mg.v = 0, source norm      */
+int pyrohip_lm_mac_rhs(pyrohip_state *s, pyrohip_mg *mg, double dx, double dy,
+                       double dt, int limiter, double grav, double *source_norm);
+/* 2. after the MAC solve: phi-MAC <- solution, MAC correction, rho_states,
+      density update + ghost fill, eint, states with 2 beta0 / (rho + rho_old),
+      advective terms, provisional velocities (proj_type 1 | 2), buoyancy from
+      rho_half, velocity ghost fill (simulation.py:417-536)                   */
+int pyrohip_lm_advect(pyrohip_state *s, pyrohip_mg *mg, double dx, double dy,
+                      double dt, int limiter, int proj_type, double grav, double gamma);
+/* 3. mg.f = cell-centred div(beta0 U) [/ dt], mg.v = phi on buf 1 (use_guess)
+      or 0 (simulation.py:567-579; :222-233 for preevolve)                    */
+int pyrohip_lm_proj_rhs(pyrohip_state *s, pyrohip_mg *mg, double dx, double dy,
+                        double dt, int divide_by_dt, int use_guess, double *source_norm);
+/* 4. after the solve: phi <- solution, U -= fac (beta0 / rho) grad(solution),
+      gp_mode 0: grad p untouched, 1: +=, 2: = on the interior; ghost fills of
+      u, v (and grad p unless gp_mode 0)  (simulation.py:584-613, :236-255)   */
+int pyrohip_lm_proj_update(pyrohip_state *s, pyrohip_mg *mg, double dx, double dy,
+                           double fac, int gp_mode);
+/* test hook: which 0-7 full edge states u_xl u_xr u_yl u_yr v_xl v_xr v_yl
+   v_yr, 8 u_MAC, 9 v_MAC, 10 advect_x, 11 advect_y, 12 coeff, 13 source,
+   14 rho_old, 15-18 rho_xl rho_xr rho_yl rho_yr, 19 rho_xint, 20 rho_yint,
+   21-24 u_xint v_xint u_yint v_yint -> host (qx, qy)                         */
+int pyrohip_lm_stage_dump(pyrohip_state *s, int which, double *host);
+
 /* ---- multi-GPU: x-slab decomposition, one process per GPU, RCCL -------- */
 #define PYROHIP_UNIQUE_ID_BYTES 128
 int pyrohip_comm_unique_id(char *out_id /* PYROHIP_UNIQUE_ID_BYTES */);

@@ -146,6 +146,15 @@ _PROTOS = {
     "pyrohip_inc_proj_update": [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                 C.c_double, C.c_double, C.c_double, C.c_int],
     "pyrohip_inc_stage_dump": [_VP, C.c_int, _DP],
+    "pyrohip_lm_set_base": [_VP, _DP, _DP, _DP, _DP],
+    "pyrohip_lm_dt": [_VP, C.c_double, C.c_double, C.c_double, C.c_double, _DP],
+    "pyrohip_lm_mg_coeffs": [_VP, _VP],
+    "pyrohip_lm_mac_rhs": [_VP, _VP, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, _DP],
+    "pyrohip_lm_advect": [_VP, _VP, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int,
+                          C.c_double, C.c_double],
+    "pyrohip_lm_proj_rhs": [_VP, _VP, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, _DP],
+    "pyrohip_lm_proj_update": [_VP, _VP, C.c_double, C.c_double, C.c_double, C.c_int],
+    "pyrohip_lm_stage_dump": [_VP, C.c_int, _DP],
     "pyrohip_fill_bc": [_VP, C.c_int],
     "pyrohip_state_set_user_bc": [_VP, C.c_double, C.c_double, C.c_double, _DP],
     "pyrohip_state_set_heating": [_VP, _DP],

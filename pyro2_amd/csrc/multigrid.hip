@@ -3014,61 +3014,16 @@ int pyrohip_mg_set_coeffs(pyrohip_mg *m, const double *coeffs, const int *coeffs
 {
     PYRO_REQUIRE(m && coeffs && coeffs_bc, "NULL argument");
     pyrohip_ctx *c = m->ctx;
-    PYRO_CHECK_HIP(hipSetDevice(c->device));
-    if (!m->vc_pool) {
-        size_t total = 16;
-        for (int l = 0; l < m->nlevels; l++) {
-            Geom g = make_geom(m->lev[l].n, m->lev[l].n, 1);
-            total += 3 * g.plane + 16;
-        }
-        PYRO_CHECK_HIP(hipMalloc((void **)&m->vc_pool, total * sizeof(double)));
-        PYRO_CHECK_HIP(hipMemsetAsync(m->vc_pool, 0, total * sizeof(double), c->stream));
-        double *p = m->vc_pool;
-        for (int l = 0; l < m->nlevels; l++) {
-            Geom g = make_geom(m->lev[l].n, m->lev[l].n, 1);
-            MGLevel &L = m->lev[l];
-            L.c = p + geom_lead(g); p += g.plane;
-            L.ex = p + geom_lead(g); p += g.plane;
-            L.ey = p + geom_lead(g); p += g.plane;
-            p += 16;
-        }
-    }
-    MGBC cbc;
-    for (int s = 0; s < 4; s++) { cbc.code[s] = coeffs_bc[s]; cbc.val[s] = nullptr; }
-    const int Lf = m->nlevels - 1;
+    double *fc = nullptr;
+    int fpitch = 0;
+    PYRO_TRY(mg_coeffs_begin(m, &fc, &fpitch));
     {   // finest: c.v() = coeffs.v(); fill_BC; EdgeCoeffs (variable_coeff_MG.py:72-84)
-        MGLevel &F = m->lev[Lf];
-        const int q = F.n + 2;
-        PYRO_CHECK_HIP(hipMemcpy2DAsync(F.c, F.pitch * sizeof(double), coeffs, q * sizeof(double),
+        const int q = m->lev[m->nlevels - 1].n + 2;
+        PYRO_CHECK_HIP(hipMemcpy2DAsync(fc, fpitch * sizeof(double), coeffs, q * sizeof(double),
                                         q * sizeof(double), q, hipMemcpyHostToDevice, c->stream));
     }
-    for (int l = Lf; l >= 0; l--) {
-        MGLevel &L = m->lev[l];
-        if (l < Lf) {   // coeffs_c.v() = f_patch.restrict("coeffs").v()  (:86-93)
-            MGLevel &F = m->lev[l + 1];
-            const int bx = (L.n >= 256) ? 256 : 64;
-            hipLaunchKernelGGL(k_mg_restrict, dim3((L.n + bx - 1) / bx, L.n), dim3(bx), 0,
-                               c->stream, (const double *)F.c, F.pitch, L.c, L.pitch, L.n);
-        }
-        const int nt = L.n + 2;
-        hipLaunchKernelGGL(k_mg_fill_x, dim3((nt + 255) / 256), dim3(256), 0, c->stream, L.c, L.n,
-                           L.pitch, L.dx, cbc);
-        hipLaunchKernelGGL(k_mg_fill_y, dim3((nt + 255) / 256), dim3(256), 0, c->stream, L.c, L.n,
-                           L.pitch, L.dx, cbc);
-        if (l == Lf) {
-            hipLaunchKernelGGL(k_vc_edges, dim3((L.n + 1 + 63) / 64, L.n + 1), dim3(64), 0,
-                               c->stream, (const double *)L.c, L.ex, L.ey, L.n, L.pitch,
-                               L.dx * L.dx);
-        } else {
-            MGLevel &F = m->lev[l + 1];
-            hipLaunchKernelGGL(k_vc_edges_restrict, dim3((L.n + 1 + 63) / 64, L.n + 1), dim3(64), 0,
-                               c->stream, (const double *)F.ex, (const double *)F.ey, F.pitch,
-                               L.ex, L.ey, L.pitch, L.n, F.dx * F.dx, L.dx * L.dx);
-        }
-    }
-    PYRO_CHECK_HIP(hipGetLastError());
+    PYRO_TRY(mg_coeffs_finish(m, coeffs_bc));
     PYRO_CHECK_HIP(hipStreamSynchronize(c->stream));
-    m->vc = 1;
     return 0;
 }
 
@@ -3370,6 +3325,74 @@ int mg_rows_ptr(pyrohip_mg *m, int level, int var, int i0, int ni, double **ptr,
     *ptr = plane(m, level, var) + (size_t)i0 * L.pitch;
     *pitch = L.pitch;
     *ctx = m->ctx;
+    return 0;
+}
+
+// storage of the variable coefficients (cell values and the two edge arrays of every level),
+// allocated on first use; *c = the finest level's cell array
+int mg_coeffs_begin(pyrohip_mg *m, double **fc, int *fpitch)
+{
+    PYRO_REQUIRE(m && fc && fpitch, "NULL argument");
+    pyrohip_ctx *c = m->ctx;
+    PYRO_CHECK_HIP(hipSetDevice(c->device));
+    if (!m->vc_pool) {
+        size_t total = 16;
+        for (int l = 0; l < m->nlevels; l++) {
+            Geom g = make_geom(m->lev[l].n, m->lev[l].n, 1);
+            total += 3 * g.plane + 16;
+        }
+        PYRO_CHECK_HIP(hipMalloc((void **)&m->vc_pool, total * sizeof(double)));
+        PYRO_CHECK_HIP(hipMemsetAsync(m->vc_pool, 0, total * sizeof(double), c->stream));
+        double *p = m->vc_pool;
+        for (int l = 0; l < m->nlevels; l++) {
+            Geom g = make_geom(m->lev[l].n, m->lev[l].n, 1);
+            MGLevel &L = m->lev[l];
+            L.c = p + geom_lead(g); p += g.plane;
+            L.ex = p + geom_lead(g); p += g.plane;
+            L.ey = p + geom_lead(g); p += g.plane;
+            p += 16;
+        }
+    }
+    *fc = m->lev[m->nlevels - 1].c;
+    *fpitch = m->lev[m->nlevels - 1].pitch;
+    return 0;
+}
+
+// the finest level's cell coefficients are in place (interior): ghost fill, edge coefficients
+// and restriction down the hierarchy (variable_coeff_MG.py:72-93); queued on the context's stream
+int mg_coeffs_finish(pyrohip_mg *m, const int *coeffs_bc)
+{
+    PYRO_REQUIRE(m && coeffs_bc && m->vc_pool, "NULL argument");
+    pyrohip_ctx *c = m->ctx;
+    MGBC cbc;
+    for (int s = 0; s < 4; s++) { cbc.code[s] = coeffs_bc[s]; cbc.val[s] = nullptr; }
+    const int Lf = m->nlevels - 1;
+    for (int l = Lf; l >= 0; l--) {
+        MGLevel &L = m->lev[l];
+        if (l < Lf) {   // coeffs_c.v() = f_patch.restrict("coeffs").v()  (:86-93)
+            MGLevel &F = m->lev[l + 1];
+            const int bx = (L.n >= 256) ? 256 : 64;
+            hipLaunchKernelGGL(k_mg_restrict, dim3((L.n + bx - 1) / bx, L.n), dim3(bx), 0,
+                               c->stream, (const double *)F.c, F.pitch, L.c, L.pitch, L.n);
+        }
+        const int nt = L.n + 2;
+        hipLaunchKernelGGL(k_mg_fill_x, dim3((nt + 255) / 256), dim3(256), 0, c->stream, L.c, L.n,
+                           L.pitch, L.dx, cbc);
+        hipLaunchKernelGGL(k_mg_fill_y, dim3((nt + 255) / 256), dim3(256), 0, c->stream, L.c, L.n,
+                           L.pitch, L.dx, cbc);
+        if (l == Lf) {
+            hipLaunchKernelGGL(k_vc_edges, dim3((L.n + 1 + 63) / 64, L.n + 1), dim3(64), 0,
+                               c->stream, (const double *)L.c, L.ex, L.ey, L.n, L.pitch,
+                               L.dx * L.dx);
+        } else {
+            MGLevel &F = m->lev[l + 1];
+            hipLaunchKernelGGL(k_vc_edges_restrict, dim3((L.n + 1 + 63) / 64, L.n + 1), dim3(64), 0,
+                               c->stream, (const double *)F.ex, (const double *)F.ey, F.pitch,
+                               L.ex, L.ey, L.pitch, L.n, F.dx * F.dx, L.dx * L.dx);
+        }
+    }
+    PYRO_CHECK_HIP(hipGetLastError());
+    m->vc = 1;
     return 0;
 }
 

@@ -411,6 +411,65 @@ class DeviceState:
             check(self._l.pyrohip_inc_stage_dump(self.h, k, dptr(out)))
         return out
 
+    # ---- lm_atm (csrc/lm_atm.hip) ---------------------------------------------
+    LM_STAGES = ("u_xl", "u_xr", "u_yl", "u_yr", "v_xl", "v_xr", "v_yl", "v_yr",
+                 "u_MAC", "v_MAC", "advect_x", "advect_y", "coeff", "source", "rho_old",
+                 "rho_xl", "rho_xr", "rho_yl", "rho_yr", "rho_xint", "rho_yint",
+                 "u_xint", "v_xint", "u_yint", "v_yint")
+
+    def lm_set_base(self, rho0, p0, beta0, beta0_edges):
+        """the 1-d base state (qy doubles each), once per simulation"""
+        arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in (rho0, p0, beta0, beta0_edges)]
+        for a in arrs:
+            assert a.shape == (self.qy,)
+        with self.ctx.lock:
+            check(self._l.pyrohip_lm_set_base(self.h, *[dptr(a) for a in arrs]))
+
+    def lm_dt(self, dx, dy, cfl, grav):
+        """(dt, max|u|, max|v| interior, max|u|, max|v| whole array, F_buoy)"""
+        out = np.zeros(6)
+        with self.ctx.lock:
+            check(self._l.pyrohip_lm_dt(self.h, float(dx), float(dy), float(cfl), float(grav),
+                                        dptr(out)))
+        return tuple(float(x) for x in out)
+
+    def lm_mg_coeffs(self, mg):
+        """mg's variable coefficients beta0^2 / rho from the density on the device"""
+        with self.ctx.lock:
+            check(self._l.pyrohip_lm_mg_coeffs(self.h, mg.h))
+
+    def lm_mac_rhs(self, mg, dx, dy, dt, limiter, grav):
+        out = C.c_double()
+        with self.ctx.lock:
+            check(self._l.pyrohip_lm_mac_rhs(self.h, mg.h, float(dx), float(dy), float(dt),
+                                             int(limiter), float(grav), C.byref(out)))
+        return out.value
+
+    def lm_advect(self, mg, dx, dy, dt, limiter, proj_type, grav, gamma):
+        with self.ctx.lock:
+            check(self._l.pyrohip_lm_advect(self.h, mg.h, float(dx), float(dy), float(dt),
+                                            int(limiter), int(proj_type), float(grav),
+                                            float(gamma)))
+
+    def lm_proj_rhs(self, mg, dx, dy, dt, divide_by_dt, use_guess):
+        out = C.c_double()
+        with self.ctx.lock:
+            check(self._l.pyrohip_lm_proj_rhs(self.h, mg.h, float(dx), float(dy), float(dt),
+                                              int(divide_by_dt), int(use_guess), C.byref(out)))
+        return out.value
+
+    def lm_proj_update(self, mg, dx, dy, fac, gp_mode):
+        with self.ctx.lock:
+            check(self._l.pyrohip_lm_proj_update(self.h, mg.h, float(dx), float(dy), float(fac),
+                                                 int(gp_mode)))
+
+    def lm_stage(self, which):
+        k = self.LM_STAGES.index(which) if isinstance(which, str) else int(which)
+        out = np.zeros((self.qx, self.qy))
+        with self.ctx.lock:
+            check(self._l.pyrohip_lm_stage_dump(self.h, k, dptr(out)))
+        return out
+
     def set_heating(self, profile):
         """heating profile (qx, qy) of the problem source S[E] += rho e_rate profile
         (None removes it); e_rate travels in the comp params (heat_rate)"""

@@ -59,6 +59,9 @@ def read(filename):
     sim.cc_data = myd
     sim.particles = my_particles
     sim.cc_data.t = t
+    # simulation-specific data (io_pyro.py:121: the base state of lm_atm)
+    with h5lite.open_file(filename, "r") as f:
+        sim.read_extras(f)
     try:
         derives = importlib.import_module(f"pyro2_amd.{base}.derives")
         sim.cc_data.add_derived(derives.derive_primitives)
