@@ -112,6 +112,8 @@ typedef struct {
 
 static double *zalloc(size_t n) { return (double *)calloc(n, sizeof(double)); }
 static inline double dmax(double a, double b) { return a > b ? a : b; }
+/* np.maximum: a NaN stays (clean_state must hand it on to the assert of cons_to_prim) */
+static inline double np_maximum(double a, double b) { return (a != a) ? a : dmax(a, b); }
 static inline double dmin(double a, double b) { return a < b ? a : b; }
 /* Python's builtin max(a, b) / min(a, b) on scalars, as the njit kernels of
    the reference call them: the first argument wins unless the second one is
@@ -1177,7 +1179,7 @@ int orc_comp_step(double *U, const orc_comp_params *P, double dt,
     /* clean_state, simulation.py:452-456 */
     for (int i = ilo; i <= ihi; i++)
         for (int j = jlo; j <= jhi; j++)
-            U4(U, i, j, IDENS) = dmax(U4(U, i, j, IDENS), P->small_dens);
+            U4(U, i, j, IDENS) = np_maximum(U4(U, i, j, IDENS), P->small_dens);
 
     double *q = zalloc(N * 4), *xi = zalloc(N), *ldx = zalloc(N * 4),
            *ldy = zalloc(N * 4), *tmp = zalloc(N);
@@ -2491,7 +2493,7 @@ int orc_comp_rk_rhs(double *U, const orc_comp_params *P, double *kout,
 #define I2(i, j) ((size_t)(i) * qy + (j))
     for (int i = ilo; i <= ihi; i++)            /* clean_state */
         for (int j = jlo; j <= jhi; j++)
-            U4(U, i, j, IDENS) = dmax(U4(U, i, j, IDENS), P->small_dens);
+            U4(U, i, j, IDENS) = np_maximum(U4(U, i, j, IDENS), P->small_dens);
     double *S = zalloc(N * 4);                  /* simulation.py:16-19 */
     ext_sources_h(U, NULL, N, P->grav, 0.0, S, P->heat_rate, P->heat_prof);
 

@@ -40,8 +40,10 @@ UNITS = [
     # hides latency there is independent work inside a wavefront (12.30 -> 12.15 ms)
     ("comp_wave.hip", "wave_exact", ["-ffp-contract=off", "-DPYRO_FAST=0"] + WAVE_SCHED),
     # (contracted build: -fno-honor-nans drops the v_max x, x canonicalisations in front of every
-    # fmin / fmax of a loaded or lane-moved value, 22 per row; a valid state has no NaN, an invalid
-    # one is caught by the positivity flag)
+    # fmin / fmax of a loaded or lane-moved value, 22 per row.  A valid state has no NaN.  An invalid
+    # one is NOT caught by a floating-point compare in this unit -- the flag turns `!(p > 0)` into
+    # `p <= 0`, which a NaN passes -- so the validity test works on bit patterns (hydro.h
+    # positive_bits / nan_bits); tests/test_invalid_state.py holds it to the reference's verdicts)
     ("comp_wave.hip", "wave_fast", ["-ffp-contract=fast", "-DPYRO_FAST=1", "-fno-honor-nans"] + WAVE_SCHED),
     # the row-marching kernel of SphericalPolar grids (round 6)
     ("comp_sph_wave.hip", "sphw_exact", ["-ffp-contract=off", "-DPYRO_FAST=0"]),

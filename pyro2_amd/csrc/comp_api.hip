@@ -586,6 +586,11 @@ int pyrohip_comp_evolve(pyrohip_state *s, const pyrohip_comp_params *p, double c
     // advanced kept filling them -- rebuild the final state's, restore_frame_after_inactive)
     if (!one_launch && (wave || sphw) && !(flagv & 1))
         PYRO_TRY(restore_frame_after_inactive(s, H.steps, max_steps, true, sphw));
+    // after an invalid step: the reference's assert fires right behind fill_BC_all (pyro_sim.py:250-256), so the
+    // state left behind carries its own filled ghost cells -- whatever the step's launch and the inactive
+    // iterations behind it did to the frames of the two buffers (a step that applies the boundary rules itself
+    // never filled one)
+    if ((flagv & 1) && !s->nb_set) PYRO_TRY(pyrohip_fill_bc(s, -1));
     // the minimum of the last launch belongs to the state only if that launch advanced it
     s->next_cfl_min = (H.steps == max_steps && !(flagv & 1)) ? lastmin : -1.0;
     s->cfl_kind = 0;
@@ -899,6 +904,7 @@ int pyrohip_comp_rk_evolve(pyrohip_state *y, const pyrohip_comp_params *p, pyroh
         s->d = s->base + geom_lead(s->g);
     }
     if (!(flagv & 1)) PYRO_TRY(restore_frame_after_inactive(s, H.steps, max_steps, false, false));
+    else PYRO_TRY(pyrohip_fill_bc(s, -1));      // (as pyrohip_comp_evolve: the failing step was entered behind a fill)
     s->next_cfl_min = (H.steps == max_steps && !(flagv & 1)) ? lastmin : -1.0;
     s->cfl_kind = 1;
     s->cfl_par[0] = p->gamma; s->cfl_par[1] = p->dx; s->cfl_par[2] = p->dy;

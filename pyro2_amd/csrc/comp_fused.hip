@@ -182,10 +182,11 @@ __global__ __launch_bounds__(FNT, FUSED_MINW) void k_ctu_fused(const double *__r
         for (int n = 0; n < NIT; n++) {
             const int idx = t + n * FNT;
             Cons U = Ul[n];
+            const bool dnan = nan_bits(U.d);      // np.maximum keeps a NaN: the floor must not launder it
             if (interior[n]) U.d = fmax(U.d, P.small_dens);      // clean_state
             bool ok;
             const Prim q = cons_to_prim_nb(U, gamma, ok);
-            if (act[n] && interior[n] && !ok) bad = true;
+            if (act[n] && interior[n] && (!ok || dnan)) bad = true;
             if (act[n]) {
                 B0[idx] = q.r; B0[FQN + idx] = q.u; B0[2 * FQN + idx] = q.v; B0[3 * FQN + idx] = q.p;
             }
@@ -456,10 +457,11 @@ __global__ __launch_bounds__(FNT, FUSED_MINW) void k_ctu_fused_sph(const double 
         for (int n = 0; n < NIT; n++) {
             const int idx = t + n * FNT;
             Cons U = Ul[n];
+            const bool dnan = nan_bits(U.d);      // np.maximum keeps a NaN: the floor must not launder it
             if (interior[n]) U.d = fmax(U.d, P.small_dens);      // clean_state
             bool ok;
             const Prim q = cons_to_prim_nb(U, gamma, ok);
-            if (act[n] && interior[n] && !ok) bad = true;
+            if (act[n] && interior[n] && (!ok || dnan)) bad = true;
             if (act[n]) {
                 B0[idx] = q.r; B0[FQN + idx] = q.u; B0[2 * FQN + idx] = q.v; B0[3 * FQN + idx] = q.p;
             }

@@ -292,10 +292,11 @@ __global__ __launch_bounds__(64, 2) void k_sph_wave(const double *__restrict__ U
             Cons U = Upre;
             if (!SPHW_DELAY) { Upre = loadU(k + 1); prio_publish(k); }
             const bool interior = row_in(k) && jin;
+            const bool dnan = nan_bits(U.d);      // np.maximum keeps a NaN: the floor must not launder it
             if (interior) U.d = fmax(U.d, P.small_dens);
             bool ok;
             const Prim q = cons_to_prim_nb(U, gamma, ok);
-            if (interior && !ok) bad = true;
+            if (interior && (!ok || dnan)) bad = true;
             wr[4] = q.r; wu[4] = q.u; wv[4] = q.v; wp[4] = q.p;
             if (SPHW_DELAY) {
 #if !defined(PYRO_EMU)

@@ -633,12 +633,15 @@ __global__ __launch_bounds__(64, WAVE_MINW) void k_ctu_wave(const double *__rest
             }
             const bool interior = row_in(k) && jin;
             // (RKF: the stage state is a temporary of the step -- nothing to keep the floor in)
-            if (MOL && !RKF && interior && U.d < US(SMALLD, P.small_dens))     // clean_state works in place
-                const_cast<double *>(Uin)[(size_t)k * p + jc] = US(SMALLD, P.small_dens);
+            const bool dnan = nan_bits(U.d);      // np.maximum keeps a NaN: the floor must not launder it
+            const bool floored = MOL && !RKF && interior && U.d < US(SMALLD, P.small_dens);
             if (interior) U.d = fmax(U.d, US(SMALLD, P.small_dens));
             bool ok;
             const Prim q = cons_to_prim_nb(U, US(GAMMA, P.gamma), ok);
-            if (interior && !ok) bad = true;
+            if (interior && (!ok || dnan)) bad = true;
+            // clean_state works in place -- in a cell that passes: a rejected cell stays as it was handed over
+            if (floored && ok && !dnan)
+                const_cast<double *>(Uin)[(size_t)k * p + jc] = US(SMALLD, P.small_dens);
             wr[4] = q.r; wu[4] = q.u; wv[4] = q.v; wp[4] = q.p;
             if (DELAY) {
                 // (the row that arrived is consumed ABOVE this fence: its wait sees only its own loads

@@ -98,13 +98,18 @@ __global__ __launch_bounds__(256) void k_prim(double *__restrict__ U, double *__
     const size_t k = (size_t)i * g.pitch + j;
     const bool interior = (i >= g.ilo && i <= g.ihi && j >= g.jlo && j <= g.jhi);
     Cons Uc = load_cons(U, g.plane, k);
+    const bool dnan = nan_bits(Uc.d);         // np.maximum keeps a NaN: the floor must not launder it
+    bool floored = false;
     if (interior) {
         double dn = fmax(Uc.d, P.small_dens);
-        if (dn != Uc.d) U[k] = dn;
+        floored = (dn != Uc.d);
         Uc.d = dn;
     }
     bool ok;
     Prim q = cons_to_prim(Uc, P.gamma, &ok);
+    if (dnan) ok = false;
+    // clean_state works in place -- in a cell that passes: a rejected cell stays as it was handed over
+    if (floored && ok) U[k] = Uc.d;
     double *Q = W + (size_t)W_Q * g.plane;
     Q[k] = q.r; Q[g.plane + k] = q.u; Q[2 * g.plane + k] = q.v; Q[3 * g.plane + k] = q.p;
     if (interior && !ok) atomicOr(flag, 1);
@@ -342,7 +347,7 @@ __global__ __launch_bounds__(256) void k_final(const double *__restrict__ U,
 __global__ __launch_bounds__(256) void k_update(double *__restrict__ U,
                                                 const double *__restrict__ W_, Geom g, CP P,
                                                 double *__restrict__ partial, int gx, int gy,
-                                                double *__restrict__ keep)
+                                                double *__restrict__ keep, const int *__restrict__ flag)
 {
     int bx, by;
     if (!xcd_block_2d(gx, gy, bx, by)) return;   // whole block leaves together
@@ -377,7 +382,8 @@ __global__ __launch_bounds__(256) void k_update(double *__restrict__ U,
         } else if (P.have_src)
             grav_update(Uc, Cons{Uo[0], Uo[1], Uo[2], Uo[3]}, P.grav, P.dt, P.heat_rate,
                         P.heat ? P.heat[k] : 0.0);
-        store_cons(U, pl, k, Uc);
+        // (k_prim found the state invalid: it stays the one before this step)
+        if (!(*flag & 1)) store_cons(U, pl, k, Uc);
         cfl = cfl_cell(Uc, P.gamma, P.dx, P.dy);
     }
     cfl = block_reduce_min(cfl);
@@ -557,7 +563,7 @@ int comp_step_staged(pyrohip_state *s, const pyrohip_comp_params *p, double dt)
     // the primitive planes are dead by now: U^n's density and y momentum go there
     // when the step stops at the predictor of a host-evaluated source
     PYRO_LAUNCH(c, "k_update", k_update, dim3(xcd_grid_1d(gx, gy)), block, 0, U,
-                (const double *)W, g, P, part, gx, gy, W + (size_t)W_Q * g.plane);
+                (const double *)W, g, P, part, gx, gy, W + (size_t)W_Q * g.plane, (const int *)s->d_flag);
     if (P.ext) s->ext_pending = 1;
     const double *dmin = launch_min_reduce(c->stream, part, nb);
     s->cfl_is_global = false;
@@ -845,13 +851,14 @@ __global__ __launch_bounds__(256) void k_sph_final(const double *__restrict__ U,
 // and the source predictor-corrector, simulation.py:375-423
 __global__ __launch_bounds__(256) void k_sph_update(double *__restrict__ U,
                                                     const double *__restrict__ W_, Geom g, CP P,
-                                                    SG G, int gx, int gy)
+                                                    SG G, int gx, int gy, const int *__restrict__ flag)
 {
     int bx, by;
     if (!xcd_block_2d(gx, gy, bx, by)) return;
     const int j = g.jlo + bx * blockDim.x + threadIdx.x;
     const int i = g.ilo + by;
     if (j > g.jhi) return;
+    if (*flag & 1) return;      // k_prim found the state invalid: it stays the one before this step
     const int p = g.pitch;
     const size_t pl = g.plane;
     const size_t k = (size_t)i * p + j;
@@ -978,7 +985,7 @@ int comp_step_sph(pyrohip_state *s, const pyrohip_comp_params *p, double dt)
                 (const double *)U, (const double *)W, W, g, P, G, gx, gy);
     gx = (g.ny + 255) / 256; gy = g.nx;
     PYRO_LAUNCH(c, "k_sph_update", k_sph_update, dim3(xcd_grid_1d(gx, gy)), block, 0, U,
-                (const double *)W, g, P, G, gx, gy);
+                (const double *)W, g, P, G, gx, gy, (const int *)s->d_flag);
     PYRO_CHECK_HIP(hipGetLastError());
     PYRO_CHECK_HIP(hipMemcpyAsync(c->reduce_host, s->d_flag, sizeof(int), hipMemcpyDeviceToHost,
                                   c->stream));

@@ -171,8 +171,9 @@ __device__ __forceinline__ Prim cons_to_prim_nb(const Cons &U, double gamma, boo
 {
 #if PYRO_FAST
     // fast build: no guard for rho == 0 (a state the reference's assert rejects anyway:
-    // the quotients become NaN and `ok` comes out false), pressure without the detour
-    // through the specific internal energy
+    // the quotients become NaN and `ok` comes out false -- by positive_bits: this code is
+    // built with -fno-honor-nans in places), pressure without the detour through the
+    // specific internal energy
     {
         const double rd = prcp(U.d);
         Prim q;
@@ -180,7 +181,7 @@ __device__ __forceinline__ Prim cons_to_prim_nb(const Cons &U, double gamma, boo
         q.u = U.mx * rd;
         q.v = U.my * rd;
         q.p = fma(-0.5, fma(U.my, q.v, U.mx * q.u), U.E) * (gamma - 1.0);
-        ok = (q.p > 0.0) && (U.d > 0.0);
+        ok = positive_bits(q.p) && positive_finite_bits(U.d);
         return q;
     }
 #else
@@ -196,7 +197,7 @@ __device__ __forceinline__ Prim cons_to_prim_nb(const Cons &U, double gamma, boo
     q.v = nz ? v : 0.0;
     const double es = nz ? e : 0.0;
     q.p = U.d * es * (gamma - 1.0);
-    ok = (es > 0.0) && (U.d > 0.0);
+    ok = positive_bits(es) && positive_bits(U.d);
     return q;
 #endif
 }

@@ -201,6 +201,24 @@ __device__ __forceinline__ double pvel(double m, double d, double rd)
 #endif
 }
 
+// The validity test of a state (the reference's assert: min(rho) > 0 and min(e) > 0 with numpy
+// minima, so a NaN fails it) on BIT PATTERNS: an integer compare that no floating-point flag of a
+// build (-fno-honor-nans turns `!(x > 0)` into `x <= 0`, which a NaN passes) can fold.
+// x > 0, +inf included, false for a NaN:
+__device__ __forceinline__ bool positive_bits(double x)
+{
+    return (unsigned long long)(__double_as_longlong(x) - 1) < 0x7ff0000000000000ull;
+}
+// 0 < x < +inf (a density: the reference's e = (E - rho (u^2 + v^2) / 2) / rho of rho = +inf is a NaN)
+__device__ __forceinline__ bool positive_finite_bits(double x)
+{
+    return (unsigned long long)(__double_as_longlong(x) - 1) < 0x7fefffffffffffffull;
+}
+__device__ __forceinline__ bool nan_bits(double x)
+{
+    return ((unsigned long long)__double_as_longlong(x) & 0x7fffffffffffffffull) > 0x7ff0000000000000ull;
+}
+
 struct Cons { double d, E, mx, my; };   // density, energy, x-mom, y-mom
 struct Prim { double r, u, v, p; };     // rho, u, v, p
 
@@ -220,7 +238,7 @@ __device__ __forceinline__ Prim cons_to_prim(const Cons &U, double gamma, bool *
     q.u = u;
     q.v = v;
     q.p = U.d * e * (gamma - 1.0);
-    if (ok) *ok = (e > 0.0) && (U.d > 0.0);
+    if (ok) *ok = positive_bits(e) && positive_bits(U.d);
     return q;
 }
 

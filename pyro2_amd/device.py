@@ -25,6 +25,16 @@ def comp_wave_geometry(nx, ny, ng=4, num_cus=0, march_rows=0):
                     (int(v) for v in out)))
 
 
+def _check_run(rc, dts):
+    """check() for a device-side run: the error carries what the run did before it stopped
+    (steps_done, dts: the steps that advanced the state, which is the one before the failing step)"""
+    try:
+        check(rc)
+    except _lib.PyroHipError as e:
+        e.steps_done, e.dts = len(dts), dts
+        raise
+
+
 def device_count():
     n = C.c_int()
     check(_lib.lib().pyrohip_device_count(C.byref(n)))
@@ -597,7 +607,7 @@ class DeviceState:
                                                 float(cfl), C.byref(pc), int(max_steps), C.byref(done),
                                                 dptr(dts))
         policy.t, policy.dt_old, policy.n = pc.t, pc.dt_old, int(pc.n)
-        check(rc)
+        _check_run(rc, dts[:done.value])
         return dts[:done.value]
 
     def comp_evolve(self, params, cfl, policy, max_steps):
@@ -614,7 +624,7 @@ class DeviceState:
             rc = self._l.pyrohip_comp_evolve(self.h, C.byref(params), float(cfl), C.byref(pc),
                                              int(max_steps), C.byref(done), dptr(dts))
         policy.t, policy.dt_old, policy.n = pc.t, pc.dt_old, int(pc.n)
-        check(rc)
+        _check_run(rc, dts[:done.value])
         return dts[:done.value]
 
     STAGES = {"q": 0, "xi": 1, "XM": 2, "XP": 3, "YM": 4, "YP": 5, "FxT": 6,
