@@ -210,6 +210,44 @@ int pyrohip_adv_step_p(pyrohip_state *s, int n, const pyrohip_adv_params *p, dou
 int pyrohip_adv_evolve(pyrohip_state *s, int n, const pyrohip_adv_params *p,
                        const double *dts, int nsteps);
 
+/* ---- advection_nonuniform: linear advection in a cell-by-cell velocity field
+        (advection_nonuniform/simulation.py:64-118, advective_fluxes.py:1-127) ----
+   The state holds the advected variable ia and the velocity planes iu, iv (the
+   reference's order: x-velocity, y-velocity, x-shift, y-shift, density).  One launch per
+   step does what fill_BC_all + Simulation.evolve do: ghost cells of all three variables are
+   taken from their interior source cells by each variable's own boundary types (outflow /
+   reflect-even / reflect-odd / periodic sides only), never from memory, and the ghost frame
+   of the result holds the filled values of the old level.  The shift planes are NOT read:
+   the upwind offset of a cell is -1 where its velocity is > 0 and 0 otherwise, which is what
+   Simulation.initialize() stores there; a ghost cell takes the offset of its source cell,
+   negated where the velocity's reflection is odd, as the fill of the shift planes gives it.
+   ng must be 4.
+   fast_math   0: bit-faithful arithmetic (results identical to NumPy, the Courant number
+               u*dt/dx a product and a division per cell); 1: the contracted build         */
+typedef struct {
+    double dx, dy;
+    int limiter;       /* 0 none, 1 MC 2nd order, 2 MC 4th order (advection.limiter) */
+    int fast_math;
+} pyrohip_advnu_params;
+int pyrohip_advnu_step(pyrohip_state *s, int ia, int iu, int iv, const pyrohip_advnu_params *p,
+                       double dt);
+/* nsteps steps with the time steps dts[0 .. nsteps) (the velocities do not change, so the
+   driver's dt policy is known beforehand): one launch per step, no host round trip; the
+   steps alternate between the state's plane and a work plane, the result is copied into the
+   state at most once.  Bit for bit what nsteps calls of pyrohip_advnu_step give.           */
+int pyrohip_advnu_evolve(pyrohip_state *s, int ia, int iu, int iv, const pyrohip_advnu_params *p,
+                         const double *dts, int nsteps);
+/* dt = cfl min(dx / max|u|, dy / max|v|), the maxima over the whole array with the ghost
+   cells as they are in memory (call pyrohip_fill_bc first, like the driver); no floor on the
+   velocities: a zero maximum gives inf and the other direction decides                     */
+int pyrohip_advnu_dt(pyrohip_state *s, int iu, int iv, double dx, double dy, double cfl,
+                     double *dt);
+/* test hook: a_x, a_y, F_x, F_y (advective_fluxes.py:76-125) of one step from the state as it
+   is, on the lower faces of every cell: four (qx, qy) host arrays one after the other.  The
+   state is not changed.  Meaningful on rows ilo .. ihi + 1, columns jlo .. jhi + 1.        */
+int pyrohip_advnu_stage_dump(pyrohip_state *s, int ia, int iu, int iv,
+                             const pyrohip_advnu_params *p, double dt, double *host);
+
 /* ---- compressible ---------------------------------------------------- */
 /* conserved order: density(0) energy(1) x-momentum(2) y-momentum(3)
    (compressible/simulation.py:223-226)                                    */

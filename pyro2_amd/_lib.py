@@ -46,6 +46,11 @@ class AdvParams(C.Structure):
                 ("march_rows", C.c_int), ("multi_k", C.c_int), ("multi_prio", C.c_int)]
 
 
+class AdvNuParams(C.Structure):
+    """pyrohip_advnu_params (include/pyrohip.h)"""
+    _fields_ = [("dx", C.c_double), ("dy", C.c_double), ("limiter", C.c_int), ("fast_math", C.c_int)]
+
+
 class MGTuning(C.Structure):
     _fields_ = [("kmax", C.c_int), ("kmax_small", C.c_int), ("nsmall", C.c_int),
                 ("march_min", C.c_int), ("march_waves", C.c_int), ("march_side", C.c_double),
@@ -169,6 +174,11 @@ _PROTOS = {
     "pyrohip_adv_step_p": [_VP, C.c_int, C.POINTER(AdvParams), C.c_double],
     "pyrohip_comp_wave_geometry": [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)],
     "pyrohip_adv_evolve": [_VP, C.c_int, C.POINTER(AdvParams), C.POINTER(C.c_double), C.c_int],
+    "pyrohip_advnu_step": [_VP, C.c_int, C.c_int, C.c_int, C.POINTER(AdvNuParams), C.c_double],
+    "pyrohip_advnu_evolve": [_VP, C.c_int, C.c_int, C.c_int, C.POINTER(AdvNuParams),
+                             C.POINTER(C.c_double), C.c_int],
+    "pyrohip_advnu_dt": [_VP, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, _DP],
+    "pyrohip_advnu_stage_dump": [_VP, C.c_int, C.c_int, C.c_int, C.POINTER(AdvNuParams), C.c_double, _DP],
     "pyrohip_comp_dt": [_VP, C.POINTER(CompParams), C.c_double, _DP],
     "pyrohip_comp_evolve": [_VP, C.POINTER(CompParams), C.c_double, C.POINTER(DtPolicyC), C.c_int,
                             _IP, _DP],

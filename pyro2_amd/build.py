@@ -32,6 +32,9 @@ UNITS = [
     ("ctx.hip", "ctx", ["-ffp-contract=off"]),
     ("advection.hip", "advection", ["-ffp-contract=off", "-DPYRO_FAST=0"]),
     ("advection.hip", "adv_fast", ["-ffp-contract=fast", "-DPYRO_FAST=1"]),
+    # per-cell velocities (advection_nonuniform): LDS tiles instead of the row march
+    ("advection_nonuniform.hip", "advnu", ["-ffp-contract=off", "-DPYRO_FAST=0"]),
+    ("advection_nonuniform.hip", "advnu_fast", ["-ffp-contract=fast", "-DPYRO_FAST=1"]),
     ("compressible.hip", "comp_exact", ["-ffp-contract=off", "-DPYRO_FAST=0"]),
     ("compressible.hip", "comp_fast", ["-ffp-contract=fast", "-DPYRO_FAST=1"]),
     ("comp_fused.hip", "fused_exact", ["-ffp-contract=off", "-DPYRO_FAST=0"]),

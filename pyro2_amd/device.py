@@ -176,6 +176,7 @@ class DeviceState:
         self.qx, self.qy = self.nx + 2 * self.ng, self.ny + 2 * self.ng
         self.bc = np.ascontiguousarray(bc_table(bcs_per_var))
         self.nvar = self.bc.shape[0]
+        self.uploads = 0      # host data handed over so far (callers that cache what they derived from it)
         self.h = C.c_void_p()
         with ctx.lock:
             check(self._l.pyrohip_state_create(ctx.h, self.nx, self.ny, self.ng,
@@ -199,6 +200,7 @@ class DeviceState:
 
     def upload(self, data):
         a = self._aos(data)
+        self.uploads += 1
         with self.ctx.lock:
             check(self._l.pyrohip_state_upload(self.h, dptr(a)))
 
@@ -212,6 +214,7 @@ class DeviceState:
 
     def upload_rows(self, i0, data):
         a = self._aos(data, rows=data.shape[0])
+        self.uploads += 1
         with self.ctx.lock:
             check(self._l.pyrohip_state_upload_rows(self.h, int(i0), a.shape[0], dptr(a)))
 
@@ -224,6 +227,7 @@ class DeviceState:
     def upload_var(self, n, a):
         a = np.ascontiguousarray(a, dtype=np.float64)
         assert a.shape == (self.qx, self.qy)
+        self.uploads += 1
         with self.ctx.lock:
             check(self._l.pyrohip_state_upload_var(self.h, int(n), dptr(a)))
 
@@ -535,6 +539,42 @@ class DeviceState:
         arr = (C.c_double * len(dts))(*[float(d) for d in dts])
         with self.ctx.lock:
             check(self._l.pyrohip_adv_evolve(self.h, int(n), C.byref(ap), arr, len(dts)))
+
+    # ---- advection_nonuniform (csrc/advection_nonuniform.hip) -----------------
+    def advnu_step(self, ia, iu, iv, dx, dy, dt, limiter, fast_math=0):
+        """ghost fill of the density, u and v + one step of variable ia, one launch"""
+        from ._lib import AdvNuParams
+        ap = AdvNuParams(dx, dy, int(limiter), int(fast_math))
+        with self.ctx.lock:
+            check(self._l.pyrohip_advnu_step(self.h, int(ia), int(iu), int(iv), C.byref(ap), dt))
+
+    def advnu_evolve(self, ia, iu, iv, dx, dy, dts, limiter, fast_math=0):
+        """len(dts) x (ghost fill + step) without a host round trip (pyrohip_advnu_evolve)"""
+        from ._lib import AdvNuParams
+        ap = AdvNuParams(dx, dy, int(limiter), int(fast_math))
+        arr = (C.c_double * len(dts))(*[float(d) for d in dts])
+        with self.ctx.lock:
+            check(self._l.pyrohip_advnu_evolve(self.h, int(ia), int(iu), int(iv), C.byref(ap), arr,
+                                               len(dts)))
+
+    def advnu_stages(self, ia, iu, iv, dx, dy, dt, limiter, fast_math=0):
+        """(a_x, a_y, F_x, F_y) of one step from the state as it is, (4, qx, qy); the state
+        stays as it is (test hook)"""
+        from ._lib import AdvNuParams
+        ap = AdvNuParams(dx, dy, int(limiter), int(fast_math))
+        out = np.zeros((4, self.qx, self.qy))
+        with self.ctx.lock:
+            check(self._l.pyrohip_advnu_stage_dump(self.h, int(ia), int(iu), int(iv), C.byref(ap), dt,
+                                                   dptr(out)))
+        return out
+
+    def advnu_dt(self, iu, iv, dx, dy, cfl):
+        """cfl min(dx / max|u|, dy / max|v|) over the whole array as it is in memory"""
+        dt = C.c_double()
+        with self.ctx.lock:
+            check(self._l.pyrohip_advnu_dt(self.h, int(iu), int(iv), float(dx), float(dy), float(cfl),
+                                           C.byref(dt)))
+        return dt.value
 
     def comp_dt(self, params, cfl):
         dt = C.c_double()

@@ -25,7 +25,7 @@ from .util.runparams import RuntimeParameters, _get_val
 # other solvers are not in scope
 valid_solvers = ["advection", "burgers", "compressible", "compressible_rk", "diffusion", "swe",
                  "incompressible", "incompressible_viscous", "burgers_viscous", "compressible_fv4",
-                 "compressible_sdc", "lm_atm"]
+                 "compressible_sdc", "lm_atm", "advection_nonuniform"]
 # a solver that keeps its inputs files in another solver's problem directory
 problem_home = {"compressible_rk": "compressible", "compressible_fv4": "compressible",
                 "compressible_sdc": "compressible"}
