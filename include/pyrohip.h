@@ -248,6 +248,53 @@ int pyrohip_advnu_dt(pyrohip_state *s, int iu, int iv, double dx, double dy, dou
 int pyrohip_advnu_stage_dump(pyrohip_state *s, int ia, int iu, int iv,
                              const pyrohip_advnu_params *p, double dt, double *host);
 
+/* ---- advection_rk / advection_fv4: method-of-lines advection of a scalar with a constant
+        velocity (advection_rk/simulation.py:10-90, advection_rk/fluxes.py, advection_fv4/fluxes.py,
+        mesh/fourth_order.py, mesh/integration.py) ----
+   One launch of a tile kernel per Runge-Kutta stage: the stage start (the linear combination of
+   pyrohip_state_lincomb) is formed as the tile is loaded, every cell from its interior source
+   cell under the boundary rules (outflow / reflect-even / periodic sides only), so ghost cells
+   are never read from memory; the last stage also writes the final update.  ng must be 4.
+   scheme      2: advection_rk (limiter 0 none, 1 MC 2nd order, otherwise MC 4th order; >= 10 is
+                  refused: it does not run in the reference); 4: advection_fv4 (limiter 0: the
+                  unlimited face averages, otherwise the limited states of fourth_order.states)
+   fast_math   0: bit-faithful arithmetic (results identical to NumPy / numba, true divisions by
+                  dx and dy); 1: the contracted build                                          */
+typedef struct {
+    double dx, dy;
+    double u, v;       /* advection.u, advection.v */
+    int limiter;       /* advection.limiter */
+    int scheme;        /* 2 | 4 */
+    int fast_math;
+} pyrohip_advrk_params;
+/* temporal methods of mesh/integration.py */
+#define PYROHIP_RK_RK2 0
+#define PYROHIP_RK_TVD2 1
+#define PYROHIP_RK_TVD3 2
+#define PYROHIP_RK_RK4 3
+/* k = -div F of variable var of y -- its ghost cells taken through the boundary rules, not from
+   memory -- into plane `slot` of kstate (interior cells only): the right-hand side alone, for
+   the stage-by-stage path (mesh/integration.py RKIntegrator + pyrohip_state_lincomb)          */
+int pyrohip_advrk_rhs(pyrohip_state *y, int var, const pyrohip_advrk_params *p,
+                      pyrohip_state *kstate, int slot);
+/* one whole Runge-Kutta step of variable var in nstages launches.  Bit for bit what the
+   stage-by-stage path gives, ghost frame included: the ghost cells of the result hold the
+   filled values of the OLD level (the reference's final update touches the interior only)    */
+int pyrohip_advrk_step(pyrohip_state *s, int var, const pyrohip_advrk_params *p, int method,
+                       double dt);
+/* nsteps steps with the time steps dts[0 .. nsteps) (the advective time step is closed-form, so
+   the driver's dt policy is known beforehand), no host round trip.  Bit for bit what nsteps
+   calls of pyrohip_advrk_step give.                                                           */
+int pyrohip_advrk_evolve(pyrohip_state *s, int var, const pyrohip_advrk_params *p, int method,
+                         const double *dts, int nsteps);
+/* test hook: the intermediates of stage `stage` of one step from the state as it is: the face
+   values a_x, a_y and the fluxes F_x, F_y on the lower faces of every cell, k_s, the stage
+   start -- six (qx, qy) host arrays one after the other.  The state is not changed.  a_x, F_x
+   are meaningful on rows ilo .. ihi + 1 of the interior columns, a_y, F_y on columns
+   jlo .. jhi + 1 of the interior rows, k_s on the interior.                                   */
+int pyrohip_advrk_stage_dump(pyrohip_state *s, int var, const pyrohip_advrk_params *p, int method,
+                             double dt, int stage, double *host);
+
 /* ---- compressible ---------------------------------------------------- */
 /* conserved order: density(0) energy(1) x-momentum(2) y-momentum(3)
    (compressible/simulation.py:223-226)                                    */

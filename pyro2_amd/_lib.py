@@ -51,6 +51,16 @@ class AdvNuParams(C.Structure):
     _fields_ = [("dx", C.c_double), ("dy", C.c_double), ("limiter", C.c_int), ("fast_math", C.c_int)]
 
 
+class AdvRkParams(C.Structure):
+    """pyrohip_advrk_params (include/pyrohip.h)"""
+    _fields_ = [("dx", C.c_double), ("dy", C.c_double), ("u", C.c_double), ("v", C.c_double),
+                ("limiter", C.c_int), ("scheme", C.c_int), ("fast_math", C.c_int)]
+
+
+# temporal methods of mesh/integration.py -> PYROHIP_RK_*
+RK_METHODS = {"RK2": 0, "TVD2": 1, "TVD3": 2, "RK4": 3}
+
+
 class MGTuning(C.Structure):
     _fields_ = [("kmax", C.c_int), ("kmax_small", C.c_int), ("nsmall", C.c_int),
                 ("march_min", C.c_int), ("march_waves", C.c_int), ("march_side", C.c_double),
@@ -179,6 +189,10 @@ _PROTOS = {
                              C.POINTER(C.c_double), C.c_int],
     "pyrohip_advnu_dt": [_VP, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, _DP],
     "pyrohip_advnu_stage_dump": [_VP, C.c_int, C.c_int, C.c_int, C.POINTER(AdvNuParams), C.c_double, _DP],
+    "pyrohip_advrk_rhs": [_VP, C.c_int, C.POINTER(AdvRkParams), _VP, C.c_int],
+    "pyrohip_advrk_step": [_VP, C.c_int, C.POINTER(AdvRkParams), C.c_int, C.c_double],
+    "pyrohip_advrk_evolve": [_VP, C.c_int, C.POINTER(AdvRkParams), C.c_int, C.POINTER(C.c_double), C.c_int],
+    "pyrohip_advrk_stage_dump": [_VP, C.c_int, C.POINTER(AdvRkParams), C.c_int, C.c_double, C.c_int, _DP],
     "pyrohip_comp_dt": [_VP, C.POINTER(CompParams), C.c_double, _DP],
     "pyrohip_comp_evolve": [_VP, C.POINTER(CompParams), C.c_double, C.POINTER(DtPolicyC), C.c_int,
                             _IP, _DP],

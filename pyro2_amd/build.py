@@ -35,6 +35,9 @@ UNITS = [
     # per-cell velocities (advection_nonuniform): LDS tiles instead of the row march
     ("advection_nonuniform.hip", "advnu", ["-ffp-contract=off", "-DPYRO_FAST=0"]),
     ("advection_nonuniform.hip", "advnu_fast", ["-ffp-contract=fast", "-DPYRO_FAST=1"]),
+    # method-of-lines advection (advection_rk / advection_fv4): one tile kernel per Runge-Kutta stage
+    ("advection_rk.hip", "advrk", ["-ffp-contract=off", "-DPYRO_FAST=0"]),
+    ("advection_rk.hip", "advrk_fast", ["-ffp-contract=fast", "-DPYRO_FAST=1"]),
     ("compressible.hip", "comp_exact", ["-ffp-contract=off", "-DPYRO_FAST=0"]),
     ("compressible.hip", "comp_fast", ["-ffp-contract=fast", "-DPYRO_FAST=1"]),
     ("comp_fused.hip", "fused_exact", ["-ffp-contract=off", "-DPYRO_FAST=0"]),

@@ -576,6 +576,43 @@ class DeviceState:
                                            C.byref(dt)))
         return dt.value
 
+    # ---- advection_rk / advection_fv4 (csrc/advection_rk.hip) -----------------
+    @staticmethod
+    def _advrk_method(method):
+        from ._lib import RK_METHODS
+        if method not in RK_METHODS:
+            raise ValueError(f"unknown temporal method {method!r} (one of {sorted(RK_METHODS)})")
+        return RK_METHODS[method]
+
+    def advrk_rhs(self, n, params, kstate, slot):
+        """k = -div F of variable n (ghost cells through the boundary rules) into plane `slot`
+        of kstate (pyrohip_advrk_rhs); params: _lib.AdvRkParams"""
+        with self.ctx.lock:
+            check(self._l.pyrohip_advrk_rhs(self.h, int(n), C.byref(params), kstate.h, int(slot)))
+
+    def advrk_step(self, n, params, method, dt):
+        """one Runge-Kutta step of variable n, one launch per stage (pyrohip_advrk_step)"""
+        m = self._advrk_method(method)
+        with self.ctx.lock:
+            check(self._l.pyrohip_advrk_step(self.h, int(n), C.byref(params), m, float(dt)))
+
+    def advrk_evolve(self, n, params, method, dts):
+        """len(dts) Runge-Kutta steps without a host round trip (pyrohip_advrk_evolve)"""
+        m = self._advrk_method(method)
+        arr = (C.c_double * len(dts))(*[float(d) for d in dts])
+        with self.ctx.lock:
+            check(self._l.pyrohip_advrk_evolve(self.h, int(n), C.byref(params), m, arr, len(dts)))
+
+    def advrk_stages(self, n, params, method, dt, stage):
+        """(a_x, a_y, F_x, F_y, k_s, stage start) of stage `stage` of one step from the state as
+        it is, (6, qx, qy); the state stays as it is (test hook)"""
+        m = self._advrk_method(method)
+        out = np.zeros((6, self.qx, self.qy))
+        with self.ctx.lock:
+            check(self._l.pyrohip_advrk_stage_dump(self.h, int(n), C.byref(params), m, float(dt),
+                                                   int(stage), dptr(out)))
+        return out
+
     def comp_dt(self, params, cfl):
         dt = C.c_double()
         with self.ctx.lock:

@@ -24,7 +24,12 @@ def read(filename):
         dt, dt_old = f.attrs.get("dt"), f.attrs.get("dt_old")
         params = dict(f["runtime parameters"].attrs.items()) \
             if "runtime parameters" in f else {}
-        myd = CellCenterData2d(myg)
+        # (cell averages of the fourth-order advection solver: its data class)
+        if solver_name in ("advection_fv4", b"advection_fv4"):
+            from ..mesh.fv import FV2d
+            myd = FV2d(myg)
+        else:
+            myd = CellCenterData2d(myg)
         for n in names:
             a = f["state"][n].attrs
             known = {k: (a[k] if a[k] in bnd.bc_solid else "outflow")
