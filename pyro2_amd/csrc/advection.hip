@@ -741,42 +741,6 @@ using namespace pyro;
 
 constexpr int AW_GHOST_COLS = 4;   // = pyro::exact::AW_GHOST
 
-static bool simple_bc(int b)
-{
-    return b == PYROHIP_BC_OUTFLOW || b == PYROHIP_BC_REFLECT_EVEN || b == PYROHIP_BC_REFLECT_ODD ||
-           b == PYROHIP_BC_PERIODIC;
-}
-
-// after a step of variable n from s->d into s->work: the new level becomes the state's
-static int adv_commit(pyrohip_state *s, int n)
-{
-    pyrohip_ctx *c = s->ctx;
-    const Geom &g = s->g;
-    if (s->nvar == 1) {
-        // single-variable state: swap the two allocations
-        double *old_base = s->base;
-        s->base = s->work;
-        s->work = old_base;
-        s->d = s->base + geom_lead(g);
-    } else {
-        PYRO_CHECK_HIP(hipMemcpyAsync(s->d + (size_t)n * g.plane, s->work + geom_lead(g),
-                                      g.plane * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    }
-    s->next_cfl_min = -1.0;
-    return 0;
-}
-
-static int adv_ensure_work(pyrohip_state *s)
-{
-    if (s->work_planes < 1) {
-        if (s->work) PYRO_CHECK_HIP(hipFree(s->work));
-        s->work = nullptr;
-        PYRO_CHECK_HIP(hipMalloc((void **)&s->work, (s->g.plane + 16) * sizeof(double)));
-        s->work_planes = 1;
-    }
-    return 0;
-}
-
 extern "C" int pyrohip_adv_step_p(pyrohip_state *s, int n, const pyrohip_adv_params *ap, double dt)
 {
     PYRO_REQUIRE(s && ap, "NULL argument");
@@ -792,15 +756,15 @@ extern "C" int pyrohip_adv_step_p(pyrohip_state *s, int n, const pyrohip_adv_par
     const Geom &g = s->g;
     if (ap->fill)
         for (int k = 0; k < 4; k++)
-            PYRO_REQUIRE(simple_bc(s->bc[n * 4 + k]),
+            PYRO_REQUIRE(bc_is_index_map(s->bc[n * 4 + k], true),
                          "fused ghost fill: outflow / reflect / periodic boundaries only");
     PYRO_TRY(comm_wait_halo(s));
-    PYRO_TRY(adv_ensure_work(s));
+    PYRO_TRY(state_work(s, WorkOwner::ADV, 1));
     double *cur = s->d + (size_t)n * g.plane;
     double *nxt = s->work + geom_lead(g);
     PYRO_TRY(ap->fast_math ? fastm::adv_step_launch(s, n, ap, dt, cur, nxt)
                            : exact::adv_step_launch(s, n, ap, dt, cur, nxt));
-    return adv_commit(s, n);
+    return state_take_work(s, n);
 }
 
 // nsteps x (ghost fill of variable n + step) with the time steps dts[0 .. nsteps): what the
@@ -818,7 +782,7 @@ extern "C" int pyrohip_adv_evolve(pyrohip_state *s, int n, const pyrohip_adv_par
     PYRO_REQUIRE(ap->dx > 0.0 && ap->dy > 0.0, "bad dx / dy");
     const Geom &g = s->g;
     for (int k = 0; k < 4; k++)
-        PYRO_REQUIRE(simple_bc(s->bc[n * 4 + k]),
+        PYRO_REQUIRE(bc_is_index_map(s->bc[n * 4 + k], true),
                      "pyrohip_adv_evolve: outflow / reflect / periodic boundaries only");
     bool periodic = true;
     for (int k = 0; k < 4; k++) periodic = periodic && s->bc[n * 4 + k] == PYROHIP_BC_PERIODIC;
@@ -832,7 +796,7 @@ extern "C" int pyrohip_adv_evolve(pyrohip_state *s, int n, const pyrohip_adv_par
     // must fit the grid; u = 0 or v = 0 keep the single step (its upwind offsets are not the signs)
     if (!periodic || ap->u == 0.0 || ap->v == 0.0 || s->nb_set || g.nx < 16 || g.ny < 16) kmax = 1;
     PYRO_TRY(comm_wait_halo(s));
-    PYRO_TRY(adv_ensure_work(s));
+    PYRO_TRY(state_work(s, WorkOwner::ADV, 1));
     pyrohip_adv_params one = *ap;
     one.fill = 1;
     int done = 0;
@@ -847,7 +811,7 @@ extern "C" int pyrohip_adv_evolve(pyrohip_state *s, int n, const pyrohip_adv_par
             PYRO_TRY(ap->fast_math ? fastm::adv_multi_launch(s, &one, dts + done, K, cur, nxt)
                                    : exact::adv_multi_launch(s, &one, dts + done, K, cur, nxt));
         }
-        PYRO_TRY(adv_commit(s, n));
+        PYRO_TRY(state_take_work(s, n));
         done += K;
     }
     return 0;

@@ -73,19 +73,6 @@ struct AdvNuParams {
     int bc[12];             // xl, xr, yl, yr of the density, u, v
 };
 
-// array cell (i, j) of a variable under its ghost fill: the interior source cell and whether
-// the value changes sign on the way (x fill, then y fill: the corner is the composition)
-struct NuSrc { size_t off; bool neg; };
-__device__ __forceinline__ NuSrc nu_src(const Geom &g, const BcMap &mr, const BcMap &mc, int i, int j)
-{
-    i = i < 0 ? 0 : (i > g.qx - 1 ? g.qx - 1 : i);       // (cells beyond the array feed ghost cells'
-    j = j < 0 ? 0 : (j > g.qy - 1 ? g.qy - 1 : j);       //  discarded fluxes only: any address inside)
-    const int is = bc_src(mr, i, g.ilo, g.ihi), js = bc_src(mc, j, g.jlo, g.jhi);
-    const bool nr = (i < g.ilo && mr.odd_lo) || (i > g.ihi && mr.odd_hi);
-    const bool nc = (j < g.jlo && mc.odd_lo) || (j > g.jhi && mc.odd_hi);
-    return NuSrc{(size_t)is * g.pitch + js, nr != nc};
-}
-
 // index of a cell in the slopes' / velocities' LDS array -> its index in the array of a
 __device__ __forceinline__ int nu_b2a(int k)
 {
@@ -116,7 +103,7 @@ __global__ __launch_bounds__(NU_THREADS) void k_advnu_step(const double *__restr
         const BcMap mc = bc_map(g.jlo, g.jhi, g.ng, P.bc[2], P.bc[3], true);
         for (int n = tid; n < NU_AH * NU_AW; n += NU_THREADS) {
             const int r = n / NU_AW, c = n - r * NU_AW;
-            const NuSrc s = nu_src(g, mr, mc, I0 + r - NU_HA, J0 + c - NU_HA);
+            const TileSrc s = tile_src(g, mr, mc, I0 + r - NU_HA, J0 + c - NU_HA);
             const double raw = ain[s.off];
             A[n] = s.neg ? -raw : raw;
         }
@@ -128,12 +115,12 @@ __global__ __launch_bounds__(NU_THREADS) void k_advnu_step(const double *__restr
             const int r = n / NU_BW, c = n - r * NU_BW;
             const int i = I0 + r - NU_HB, j = J0 + c - NU_HB;
             // offset of the source cell (simulation.py:18-26), negated with an odd reflection
-            const NuSrc su = nu_src(g, ur, uc, i, j);
+            const TileSrc su = tile_src(g, ur, uc, i, j);
             const double ru = uin[su.off];
             const int ou = (ru > 0.0) ? -1 : 0;
             U[n] = su.neg ? -ru : ru;
             SU[n] = su.neg ? -ou : ou;
-            const NuSrc sv = nu_src(g, vr, vc, i, j);
+            const TileSrc sv = tile_src(g, vr, vc, i, j);
             const double rv = vin[sv.off];
             const int ov = (rv > 0.0) ? -1 : 0;
             V[n] = sv.neg ? -rv : rv;
@@ -281,12 +268,6 @@ int advnu_step_launch(pyrohip_state *, int, int, int, const pyrohip_advnu_params
 
 using namespace pyro;
 
-static bool advnu_simple_bc(int b)
-{
-    return b == PYROHIP_BC_OUTFLOW || b == PYROHIP_BC_REFLECT_EVEN || b == PYROHIP_BC_REFLECT_ODD ||
-           b == PYROHIP_BC_PERIODIC;
-}
-
 static int advnu_check(pyrohip_state *s, int ia, int iu, int iv, const pyrohip_advnu_params *ap)
 {
     PYRO_REQUIRE(s && ap, "NULL argument");
@@ -301,51 +282,24 @@ static int advnu_check(pyrohip_state *s, int ia, int iu, int iv, const pyrohip_a
     const int var[3] = {ia, iu, iv};
     for (int m = 0; m < 3; m++)
         for (int k = 0; k < 4; k++)
-            PYRO_REQUIRE(advnu_simple_bc(s->bc[var[m] * 4 + k]),
+            PYRO_REQUIRE(bc_is_index_map(s->bc[var[m] * 4 + k], true),
                          "fused ghost fill: outflow / reflect / periodic boundaries only");
     return 0;
 }
 
-static int advnu_ensure_work(pyrohip_state *s)
-{
-    if (s->work_planes < 1) {
-        if (s->work) PYRO_CHECK_HIP(hipFree(s->work));
-        s->work = nullptr;
-        PYRO_CHECK_HIP(hipMalloc((void **)&s->work, (s->g.plane + 16) * sizeof(double)));
-        s->work_planes = 1;
-    }
-    return 0;
-}
-
-// nsteps x (ghost fill of the density, u and v + step).  The state has five variables, so the
-// new level cannot become the state's by a swap of allocations: the steps alternate between
-// the density's plane of the state and the work plane, and the result is copied into the state
-// once, after an odd number of steps.
+// nsteps x (ghost fill of the density, u and v + step), alternating between the density's plane
+// of the state and the work plane (common.h: evolve_pingpong)
 extern "C" int pyrohip_advnu_evolve(pyrohip_state *s, int ia, int iu, int iv, const pyrohip_advnu_params *ap,
                                     const double *dts, int nsteps)
 {
     PYRO_TRY(advnu_check(s, ia, iu, iv, ap));
     PYRO_REQUIRE(dts || nsteps == 0, "NULL argument");
     PYRO_REQUIRE(nsteps >= 0, "negative step count");
-    const Geom &g = s->g;
-    PYRO_TRY(comm_wait_halo(s));
-    PYRO_TRY(advnu_ensure_work(s));
-    double *plane = s->d + (size_t)ia * g.plane, *work = s->work + geom_lead(g);
-    double *cur = plane, *nxt = work;
-    for (int k = 0; k < nsteps; k++) {
-        PYRO_TRY(ap->fast_math ? fastm::advnu_step_launch(s, ia, iu, iv, ap, dts[k], cur, nxt, nullptr)
-                               : exact::advnu_step_launch(s, ia, iu, iv, ap, dts[k], cur, nxt, nullptr));
-        double *t = cur; cur = nxt; nxt = t;
-    }
-    if (cur != plane)
-        PYRO_CHECK_HIP(hipMemcpyAsync(plane, work, g.plane * sizeof(double), hipMemcpyDeviceToDevice,
-                                      s->ctx->stream));
-    if (nsteps > 0) {
-        s->next_cfl_min = -1.0;
-        s->ghost_by_rules = false;
-        s->stages_valid = false;
-    }
-    return 0;
+    auto step = [&](int k, const double *cur, double *nxt) {
+        return ap->fast_math ? fastm::advnu_step_launch(s, ia, iu, iv, ap, dts[k], cur, nxt, nullptr)
+                             : exact::advnu_step_launch(s, ia, iu, iv, ap, dts[k], cur, nxt, nullptr);
+    };
+    return evolve_pingpong(s, ia, WorkOwner::ADVNU, 1, nsteps, step);
 }
 
 extern "C" int pyrohip_advnu_step(pyrohip_state *s, int ia, int iu, int iv, const pyrohip_advnu_params *ap,
@@ -363,28 +317,17 @@ extern "C" int pyrohip_advnu_stage_dump(pyrohip_state *s, int ia, int iu, int iv
 {
     PYRO_TRY(advnu_check(s, ia, iu, iv, ap));
     PYRO_REQUIRE(host, "NULL argument");
-    pyrohip_ctx *c = s->ctx;
     const Geom &g = s->g;
     PYRO_TRY(comm_wait_halo(s));
-    PYRO_TRY(advnu_ensure_work(s));
+    PYRO_TRY(state_work(s, WorkOwner::ADVNU, 1));
     DevBuf tmp;
     PYRO_TRY(tmp.ensure(4 * g.plane * sizeof(double)));
     double *dump = (double *)tmp.p;
-    int rc = ap->fast_math ? fastm::advnu_step_launch(s, ia, iu, iv, ap, dt, s->d + (size_t)ia * g.plane,
-                                                      s->work + geom_lead(g), dump)
-                           : exact::advnu_step_launch(s, ia, iu, iv, ap, dt, s->d + (size_t)ia * g.plane,
-                                                      s->work + geom_lead(g), dump);
-    hipError_t e = hipSuccess;
-    for (int k = 0; k < 4 && rc == 0 && e == hipSuccess; k++)
-        e = hipMemcpy2DAsync(host + (size_t)k * g.qx * g.qy, g.qy * sizeof(double), dump + (size_t)k * g.plane,
-                             g.pitch * sizeof(double), g.qy * sizeof(double), g.qx, hipMemcpyDeviceToHost,
-                             c->stream);
-    const hipError_t e2 = hipStreamSynchronize(c->stream);
-    tmp.release();
-    PYRO_TRY(rc);
-    PYRO_CHECK_HIP(e);
-    PYRO_CHECK_HIP(e2);
-    return 0;
+    const int rc = ap->fast_math ? fastm::advnu_step_launch(s, ia, iu, iv, ap, dt, s->d + (size_t)ia * g.plane,
+                                                            s->work + geom_lead(g), dump)
+                                 : exact::advnu_step_launch(s, ia, iu, iv, ap, dt, s->d + (size_t)ia * g.plane,
+                                                            s->work + geom_lead(g), dump);
+    return dump_planes_to_host(s, tmp, 4, rc, hipSuccess, host);
 }
 
 // method_compute_timestep (advection_nonuniform/simulation.py:64-82): the maxima run over the

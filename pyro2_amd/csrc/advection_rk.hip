@@ -106,18 +106,12 @@ __global__ __launch_bounds__(RK_THREADS) void k_advrk_stage(const double *__rest
     const double u = P.u, v = P.v;
     const BcMap mr = bc_map(g.ilo, g.ihi, g.ng, P.bc[0], P.bc[1], true);
     const BcMap mc = bc_map(g.jlo, g.jhi, g.ng, P.bc[2], P.bc[3], true);
-    // array cell -> its interior source cell (cells beyond the array feed discarded faces only)
-    auto src = [&](int i, int j) {
-        i = i < 0 ? 0 : (i > g.qx - 1 ? g.qx - 1 : i);
-        j = j < 0 ? 0 : (j > g.qy - 1 ? g.qy - 1 : j);
-        return (size_t)bc_src(mr, i, g.ilo, g.ihi) * g.pitch + bc_src(mc, j, g.jlo, g.jhi);
-    };
     auto in_array = [&](int i, int j) { return i < g.qx && j >= 0 && j < g.qy; };
 
     // ---- 1. the stage start, through the ghost fill
     for (int n = tid; n < TL::AH * AW; n += RK_THREADS) {
         const int r = n / AW, c = n - r * AW;
-        const size_t o = src(I0 + r - H, J0 + c - H);
+        const size_t o = tile_src_off(g, mr, mc, I0 + r - H, J0 + c - H);
         double a = y[o];
 #pragma unroll
         for (int s = 0; s < NK; s++) a += P.ca[s] * kin[s * kstride + o];
@@ -127,7 +121,7 @@ __global__ __launch_bounds__(RK_THREADS) void k_advrk_stage(const double *__rest
         for (int n = tid; n < TI * TJ; n += RK_THREADS) {
             const int r = n / TJ, c = n - r * TJ;
             const int i = I0 + r, j = J0 + c;
-            const size_t o = src(i, j);
+            const size_t o = tile_src_off(g, mr, mc, i, j);
             double a = y[o];
             if (i >= g.ilo && i <= g.ihi && j >= g.jlo && j <= g.jhi) {
 #pragma unroll
@@ -335,11 +329,6 @@ const Tableau kTableau[4] = {
      {1. / 6., 1. / 3., 1. / 3., 1. / 6.}},                                              // RK4
 };
 
-bool advrk_bc_ok(int b)
-{
-    return b == PYROHIP_BC_OUTFLOW || b == PYROHIP_BC_REFLECT_EVEN || b == PYROHIP_BC_PERIODIC;
-}
-
 int advrk_check(pyrohip_state *s, int var, const pyrohip_advrk_params *ap)
 {
     PYRO_REQUIRE(s && ap, "NULL argument");
@@ -353,24 +342,13 @@ int advrk_check(pyrohip_state *s, int var, const pyrohip_advrk_params *ap)
     PYRO_REQUIRE(ap->dx > 0.0 && ap->dy > 0.0, "bad dx / dy");
     PYRO_REQUIRE(!s->nb_set, "advection_rk / advection_fv4 do not step slabs of a decomposed grid");
     for (int k = 0; k < 4; k++)
-        PYRO_REQUIRE(advrk_bc_ok(s->bc[var * 4 + k]),
+        PYRO_REQUIRE(bc_is_index_map(s->bc[var * 4 + k], false),
                      "fused ghost fill: outflow / reflect-even / periodic boundaries only");
     return 0;
 }
 
 // work planes: the other level of the ping-pong, then the increments of all stages but the last
 constexpr size_t kAdvRkWork = 4;
-int advrk_ensure_work(pyrohip_state *s)
-{
-    if (s->work_planes < kAdvRkWork) {
-        if (s->work) PYRO_CHECK_HIP(hipFree(s->work));
-        s->work = nullptr;
-        s->work_planes = 0;
-        PYRO_CHECK_HIP(hipMalloc((void **)&s->work, (kAdvRkWork * s->g.plane + 16) * sizeof(double)));
-        s->work_planes = kAdvRkWork;
-    }
-    return 0;
-}
 
 // the stages 0 .. upto of one step from plane cur; the last stage writes plane nxt.  dump: the
 // intermediates of stage `upto` (pyrohip_advrk_stage_dump)
@@ -417,10 +395,8 @@ extern "C" int pyrohip_advrk_rhs(pyrohip_state *y, int var, const pyrohip_advrk_
                                            nullptr);
 }
 
-// nsteps Runge-Kutta steps, nstages launches each.  The new level cannot become the state's by a
-// swap of allocations (the state may hold other variables): the steps alternate between the
-// variable's plane of the state and a work plane, and the result is copied into the state once,
-// after an odd number of steps.
+// nsteps Runge-Kutta steps, nstages launches each, alternating between the variable's plane of
+// the state and a work plane (common.h: evolve_pingpong)
 extern "C" int pyrohip_advrk_evolve(pyrohip_state *s, int var, const pyrohip_advrk_params *ap, int method,
                                     const double *dts, int nsteps)
 {
@@ -428,25 +404,11 @@ extern "C" int pyrohip_advrk_evolve(pyrohip_state *s, int var, const pyrohip_adv
     PYRO_REQUIRE(method >= 0 && method <= 3, "unknown temporal method");
     PYRO_REQUIRE(dts || nsteps == 0, "NULL argument");
     PYRO_REQUIRE(nsteps >= 0, "negative step count");
-    const Geom &g = s->g;
     const Tableau &tb = kTableau[method];
-    PYRO_TRY(comm_wait_halo(s));
-    PYRO_TRY(advrk_ensure_work(s));
-    double *plane = s->d + (size_t)var * g.plane, *work = s->work + geom_lead(g);
-    double *cur = plane, *nxt = work;
-    for (int k = 0; k < nsteps; k++) {
-        PYRO_TRY(advrk_stages(s, var, ap, tb, dts[k], cur, nxt, tb.ns - 1, nullptr));
-        double *t = cur; cur = nxt; nxt = t;
-    }
-    if (cur != plane)
-        PYRO_CHECK_HIP(hipMemcpyAsync(plane, work, g.plane * sizeof(double), hipMemcpyDeviceToDevice,
-                                      s->ctx->stream));
-    if (nsteps > 0) {
-        s->next_cfl_min = -1.0;
-        s->ghost_by_rules = false;
-        s->stages_valid = false;
-    }
-    return 0;
+    auto step = [&](int k, const double *cur, double *nxt) {
+        return advrk_stages(s, var, ap, tb, dts[k], cur, nxt, tb.ns - 1, nullptr);
+    };
+    return evolve_pingpong(s, var, WorkOwner::ADVRK, kAdvRkWork, nsteps, step);
 }
 
 extern "C" int pyrohip_advrk_step(pyrohip_state *s, int var, const pyrohip_advrk_params *ap, int method,
@@ -469,23 +431,14 @@ extern "C" int pyrohip_advrk_stage_dump(pyrohip_state *s, int var, const pyrohip
     pyrohip_ctx *c = s->ctx;
     const Geom &g = s->g;
     PYRO_TRY(comm_wait_halo(s));
-    PYRO_TRY(advrk_ensure_work(s));
+    PYRO_TRY(state_work(s, WorkOwner::ADVRK, kAdvRkWork));
     DevBuf tmp;
     PYRO_TRY(tmp.ensure(RK_DUMP_PLANES * g.plane * sizeof(double)));
     double *dump = (double *)tmp.p;
-    hipError_t e = hipMemsetAsync(dump, 0, RK_DUMP_PLANES * g.plane * sizeof(double), c->stream);
+    const hipError_t e = hipMemsetAsync(dump, 0, RK_DUMP_PLANES * g.plane * sizeof(double), c->stream);
     int rc = 0;
     if (e == hipSuccess)
         rc = advrk_stages(s, var, ap, tb, dt, s->d + (size_t)var * g.plane, s->work + geom_lead(g), stage, dump);
-    for (int k = 0; k < RK_DUMP_PLANES && rc == 0 && e == hipSuccess; k++)
-        e = hipMemcpy2DAsync(host + (size_t)k * g.qx * g.qy, g.qy * sizeof(double), dump + (size_t)k * g.plane,
-                             g.pitch * sizeof(double), g.qy * sizeof(double), g.qx, hipMemcpyDeviceToHost,
-                             c->stream);
-    const hipError_t e2 = hipStreamSynchronize(c->stream);
-    tmp.release();
-    PYRO_TRY(rc);
-    PYRO_CHECK_HIP(e);
-    PYRO_CHECK_HIP(e2);
-    return 0;
+    return dump_planes_to_host(s, tmp, RK_DUMP_PLANES, rc, e, host);
 }
 #endif

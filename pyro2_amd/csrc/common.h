@@ -264,6 +264,9 @@ struct StepPolicy {
     unsigned long long *slots;   // 3 sets of kPolSetWords bit patterns
     double *dts;                 // dt sequence of the call
 };
+
+// which solver's planes a state's work area holds (pyrohip_state::work_owner, state_work)
+struct WorkOwner { enum { NONE, ADV, ADVNU, ADVRK, COMP, SWE, INC, LM }; };
 }  // namespace pyro
 
 struct pyrohip_state {
@@ -291,9 +294,11 @@ struct pyrohip_state {
     double *d_x = nullptr;    // cell-centre x coordinates (qx)
     double r_cxoff = 0.0, r_post[4] = {0, 0, 0, 0}, r_pre[4] = {0, 0, 0, 0};
     double r_sfd[8] = {0}, r_sfu[8] = {0};
-    // compressible work space (allocated on first use)
+    // work area (state_work, ctx.hip): work_planes planes laid out like the state's, then
+    // work_tail doubles; zeroed whenever it passes to another owner
     double *work = nullptr;
-    size_t work_planes = 0;
+    size_t work_planes = 0, work_tail = 0;
+    int work_owner = pyro::WorkOwner::NONE;
     int *d_flag = nullptr;    // positivity flag
     pyro::StepScalars *d_scal = nullptr;   // pyrohip_comp_evolve
     double *d_dts = nullptr;  // ... dt of every step of a call
@@ -365,4 +370,82 @@ inline bool cfl_min_cached(const pyrohip_state *s, int kind, double a, double dx
     return s->next_cfl_min > 0.0 && s->cfl_kind == kind && s->cfl_par[0] == a && s->cfl_par[1] == dx &&
            s->cfl_par[2] == dy;
 }
+
+namespace pyro {
+// ---- a state's on-demand device memory: allocated, handed over and exchanged in ctx.hip only ----
+// The work area for `owner`: at least `planes` planes and exactly `tail_doubles` behind them.  A
+// call of the owner it already serves returns at once; any other call (first use, growth, another
+// solver's area) leaves it zeroed on the context's stream, so that positions the owner's kernels
+// never write read as 0, and tags it.
+int state_work(pyrohip_state *s, int owner, size_t planes, size_t tail_doubles = 0);
+// "has this solver's producer run on the state?"
+inline bool state_work_is(const pyrohip_state *s, int owner, size_t planes)
+{
+    return s->work_owner == owner && s->work_planes >= planes;
+}
+// the new level of variable n sits in work plane 0: it becomes the state's -- by exchanging the two
+// allocations where they have the same size, by a copy everywhere else
+int state_take_work(pyrohip_state *s, int n);
+// the second buffer (nvar planes, zeroed once)
+int state_alt(pyrohip_state *s);
+// set-up of a run that advances on the device: the step scalars and the dt sequence (max_steps + 1
+// slots) in device memory, *H zeroed and filled from the policy.  The caller sets min0 / keep0 and
+// uploads H.
+int evolve_begin(pyrohip_state *s, const pyrohip_dt_policy *pol, double cfl, double dx, double dy,
+                 int max_steps, StepScalars *H);
+// enqueue the copy of one plane (laid out like the state's) into a (qx, qy) host array; the
+// caller synchronises
+int plane_to_host(pyrohip_state *s, const double *dev_plane, double *host);
+
+// boundary types a kernel can apply as an index map while it loads (stencil.h: bc_map)
+inline bool bc_is_index_map(int b, bool allow_odd)
+{
+    return b == PYROHIP_BC_OUTFLOW || b == PYROHIP_BC_REFLECT_EVEN || b == PYROHIP_BC_PERIODIC ||
+           (allow_odd && b == PYROHIP_BC_REFLECT_ODD);
+}
+
+// nsteps steps of ONE variable of a state that may hold others, so that the new level cannot
+// become the state's by an exchange of allocations: step(k, cur, nxt) -> int alternates between
+// the variable's plane and work plane 0, and the result is copied into the state once, after an
+// odd number of steps.
+template <class Step>
+int evolve_pingpong(pyrohip_state *s, int var, int owner, size_t planes, int nsteps, Step step)
+{
+    const Geom &g = s->g;
+    PYRO_TRY(comm_wait_halo(s));
+    PYRO_TRY(state_work(s, owner, planes));
+    double *plane = s->d + (size_t)var * g.plane, *work = s->work + geom_lead(g);
+    double *cur = plane, *nxt = work;
+    for (int k = 0; k < nsteps; k++) {
+        PYRO_TRY(step(k, (const double *)cur, nxt));
+        double *t = cur; cur = nxt; nxt = t;
+    }
+    if (cur != plane)
+        PYRO_CHECK_HIP(hipMemcpyAsync(plane, work, g.plane * sizeof(double), hipMemcpyDeviceToDevice,
+                                      s->ctx->stream));
+    if (nsteps > 0) {
+        s->next_cfl_min = -1.0;
+        s->ghost_by_rules = false;
+        s->stages_valid = false;
+    }
+    return 0;
+}
+
+// tail of a stage-dump hook whose launches (result rc, HIP error e) filled nplanes planes of tmp:
+// copy them to the host one after the other, wait, release tmp, report the first failure
+inline int dump_planes_to_host(pyrohip_state *s, DevBuf &tmp, int nplanes, int rc, hipError_t e, double *host)
+{
+    const Geom &g = s->g;
+    int rc_copy = 0;
+    for (int k = 0; k < nplanes && rc == 0 && e == hipSuccess && rc_copy == 0; k++)
+        rc_copy = plane_to_host(s, (const double *)tmp.p + (size_t)k * g.plane, host + (size_t)k * g.qx * g.qy);
+    const hipError_t e2 = hipStreamSynchronize(s->ctx->stream);
+    tmp.release();
+    PYRO_TRY(rc);
+    PYRO_CHECK_HIP(e);
+    PYRO_TRY(rc_copy);
+    PYRO_CHECK_HIP(e2);
+    return 0;
+}
+}  // namespace pyro
 

@@ -362,20 +362,8 @@ int pyrohip_comp_evolve(pyrohip_state *s, const pyrohip_comp_params *p, double c
                  "a SphericalPolar grid needs CGF and outflow / reflect / periodic sides "
                  "(use pyrohip_comp_dt / pyrohip_comp_step)");
     pyrohip_ctx *c = s->ctx;
-    if (!s->d_scal) PYRO_CHECK_HIP(hipMalloc((void **)&s->d_scal, sizeof(StepScalars)));
-    if (s->dts_cap < max_steps + 1) {
-        if (s->d_dts) PYRO_CHECK_HIP(hipFree(s->d_dts));
-        s->d_dts = nullptr;
-        // (not less than 1024: a run that asks for more steps call by call must not free + allocate every time)
-        const int cap = max_steps + 1 > 1024 ? max_steps + 1 : 1024;
-        PYRO_CHECK_HIP(hipMalloc((void **)&s->d_dts, (size_t)cap * sizeof(double)));
-        s->dts_cap = cap;
-    }
     StepScalars H;
-    memset(&H, 0, sizeof(H));
-    H.t = pol->t; H.dt_old = pol->dt_old; H.n = pol->n;
-    H.tmax = pol->tmax; H.f0 = pol->init_tstep_factor; H.mx = pol->max_dt_change;
-    H.fix_dt = pol->fix_dt; H.cfl = cfl; H.dx = p->dx; H.dy = p->dy;
+    PYRO_TRY(evolve_begin(s, pol, cfl, p->dx, p->dy, max_steps, &H));
     // the CFL minimum of the state as handed over: the one the last step of the previous call left, where
     // nothing has touched the state since (what pyrohip_comp_dt answers from as well) -- a pass over the
     // whole array otherwise (1.55 ms at 16384^2, 0.14 ms at 4096^2 per call)
@@ -823,20 +811,8 @@ int pyrohip_comp_rk_evolve(pyrohip_state *y, const pyrohip_comp_params *p, pyroh
     pyrohip_state *s = y;
     pyrohip_ctx *c = s->ctx;
     PYRO_REQUIRE(!c->global_cfl, "device-side stepping: compressible_rk runs on a single domain");
-    if (!s->d_scal) PYRO_CHECK_HIP(hipMalloc((void **)&s->d_scal, sizeof(StepScalars)));
-    if (s->dts_cap < max_steps + 1) {
-        if (s->d_dts) PYRO_CHECK_HIP(hipFree(s->d_dts));
-        s->d_dts = nullptr;
-        // (not less than 1024: a run that asks for more steps call by call must not free + allocate every time)
-        const int cap = max_steps + 1 > 1024 ? max_steps + 1 : 1024;
-        PYRO_CHECK_HIP(hipMalloc((void **)&s->d_dts, (size_t)cap * sizeof(double)));
-        s->dts_cap = cap;
-    }
     StepScalars H;
-    memset(&H, 0, sizeof(H));
-    H.t = pol->t; H.dt_old = pol->dt_old; H.n = pol->n;
-    H.tmax = pol->tmax; H.f0 = pol->init_tstep_factor; H.mx = pol->max_dt_change;
-    H.fix_dt = pol->fix_dt; H.cfl = cfl; H.dx = p->dx; H.dy = p->dy;
+    PYRO_TRY(evolve_begin(s, pol, cfl, p->dx, p->dy, max_steps, &H));
     const bool min_cached = cfl_min_cached(s, 1, p->gamma, p->dx, p->dy);      // (pyrohip_comp_evolve)
     H.min0 = min_cached ? s->next_cfl_min : 0.0;
     PYRO_CHECK_HIP(hipMemcpyAsync(s->d_scal, &H, sizeof(H), hipMemcpyHostToDevice, c->stream));

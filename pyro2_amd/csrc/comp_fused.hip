@@ -740,11 +740,7 @@ int fused_prepare(pyrohip_state *s, const pyrohip_comp_params *p, double dt, FP 
     const Geom &g = s->g;
     // (second_buffer = false: a launch that writes somewhere else -- the method-of-lines
     // right-hand side into the k state: no 4 planes allocated and zeroed on every stage state)
-    if (!s->alt_base && second_buffer) {
-        size_t n = g.plane * 4 + 16;
-        PYRO_CHECK_HIP(hipMalloc((void **)&s->alt_base, n * sizeof(double)));
-        PYRO_CHECK_HIP(hipMemsetAsync(s->alt_base, 0, n * sizeof(double), c->stream));
-    }
+    if (second_buffer) PYRO_TRY(state_alt(s));
     Uin = s->d;
     Uout = s->alt_base ? s->alt_base + geom_lead(g) : nullptr;
     P.gamma = p->gamma; P.dx = p->dx; P.dy = p->dy; P.dt = dt;

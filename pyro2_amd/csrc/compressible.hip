@@ -476,19 +476,6 @@ static CP make_cp(const pyrohip_comp_params *p, double dt, const pyrohip_state *
     return c;
 }
 
-static int ensure_work(pyrohip_state *s, size_t planes)
-{
-    if (s->work_planes >= planes) return 0;
-    if (s->work) PYRO_CHECK_HIP(hipFree(s->work));
-    s->work = nullptr; s->work_planes = 0;
-    size_t n = s->g.plane * planes + 16;
-    PYRO_CHECK_HIP(hipMalloc((void **)&s->work, n * sizeof(double)));
-    // zero once: stage dumps of never-written cells then read as 0
-    PYRO_CHECK_HIP(hipMemsetAsync(s->work, 0, n * sizeof(double), s->ctx->stream));
-    s->work_planes = planes;
-    return 0;
-}
-
 // CFL minimum over the whole array, left in device memory (no read-back)
 int comp_cfl_min_device(pyrohip_state *s, const pyrohip_comp_params *p, const double **dmin)
 {
@@ -534,7 +521,7 @@ int comp_step_staged(pyrohip_state *s, const pyrohip_comp_params *p, double dt)
 {
     pyrohip_ctx *c = s->ctx;
     const Geom &g = s->g;
-    PYRO_TRY(ensure_work(s, W_NPLANES));
+    PYRO_TRY(state_work(s, WorkOwner::COMP, W_NPLANES));
     const CP P = make_cp(p, dt, s);
     double *U = s->d;
     double *W = s->work + geom_lead(g);
@@ -956,7 +943,7 @@ int comp_step_sph(pyrohip_state *s, const pyrohip_comp_params *p, double dt)
 {
     pyrohip_ctx *c = s->ctx;
     const Geom &g = s->g;
-    PYRO_TRY(ensure_work(s, W_NPLANES_SPH));
+    PYRO_TRY(state_work(s, WorkOwner::COMP, W_NPLANES_SPH));
     const CP P = make_cp(p, dt, s);
     const SG G = make_sg(s);
     double *U = s->d;
@@ -1204,7 +1191,7 @@ int comp_rk_rhs(pyrohip_state *s, const pyrohip_comp_params *p, pyrohip_state *k
 {
     pyrohip_ctx *c = s->ctx;
     const Geom &g = s->g;
-    PYRO_TRY(ensure_work(s, W_NPLANES));
+    PYRO_TRY(state_work(s, WorkOwner::COMP, W_NPLANES));
     const CP P = make_cp(p, 0.0, s);
     double *U = s->d;
     double *W = s->work + geom_lead(g);
@@ -1244,14 +1231,12 @@ int comp_stage_dump(pyrohip_state *s, int stage_id, double *out)
     pyrohip_ctx *c = s->ctx;
     const Geom &g = s->g;
     PYRO_REQUIRE(stage_id >= 0 && stage_id < 10, "stage id out of range");
-    PYRO_REQUIRE(s->work_planes >= W_NPLANES, "no staged step has been run");
+    PYRO_REQUIRE(state_work_is(s, WorkOwner::COMP, W_NPLANES), "no staged step has been run");
     const int ncomp = (stage_id == 1) ? 1 : 4;
     const double *W = s->work + geom_lead(g) + (size_t)first[stage_id] * g.plane;
     std::vector<double> tmp((size_t)g.qx * g.qy);
     for (int n = 0; n < ncomp; n++) {
-        PYRO_CHECK_HIP(hipMemcpy2DAsync(tmp.data(), g.qy * sizeof(double), W + (size_t)n * g.plane,
-                                        g.pitch * sizeof(double), g.qy * sizeof(double), g.qx,
-                                        hipMemcpyDeviceToHost, c->stream));
+        PYRO_TRY(plane_to_host(s, W + (size_t)n * g.plane, tmp.data()));
         PYRO_CHECK_HIP(hipStreamSynchronize(c->stream));
         for (size_t k = 0; k < tmp.size(); k++) out[k * ncomp + n] = tmp[k];
     }

@@ -281,6 +281,77 @@ int fill_bc_planes(pyrohip_state *s, double *planes, int n0, int cnt)
     return 0;
 }
 
+// ---------------------------------------------------------------------------
+// a state's on-demand device memory (common.h)
+// ---------------------------------------------------------------------------
+int state_work(pyrohip_state *s, int owner, size_t planes, size_t tail_doubles)
+{
+    if (s->work_owner == owner && s->work_planes >= planes && s->work_tail == tail_doubles) return 0;
+    if (s->work_planes < planes || s->work_tail != tail_doubles) {
+        if (s->work) PYRO_CHECK_HIP(hipFree(s->work));
+        // (reset first: a failed allocation leaves a consistent empty state)
+        s->work = nullptr; s->work_planes = 0; s->work_tail = 0; s->work_owner = WorkOwner::NONE;
+        PYRO_CHECK_HIP(hipMalloc((void **)&s->work, (planes * s->g.plane + 16 + tail_doubles) * sizeof(double)));
+        s->work_planes = planes; s->work_tail = tail_doubles;
+    }
+    const size_t n = s->work_planes * s->g.plane + 16 + s->work_tail;
+    PYRO_CHECK_HIP(hipMemsetAsync(s->work, 0, n * sizeof(double), s->ctx->stream));
+    s->work_owner = owner;
+    return 0;
+}
+
+int state_take_work(pyrohip_state *s, int n)
+{
+    const Geom &g = s->g;
+    if (s->nvar == 1 && s->work_planes == 1 && s->work_tail == 0) {
+        double *old_base = s->base;       // both are plane + 16 doubles
+        s->base = s->work;
+        s->work = old_base;
+        s->d = s->base + geom_lead(g);
+    } else {
+        PYRO_CHECK_HIP(hipMemcpyAsync(s->d + (size_t)n * g.plane, s->work + geom_lead(g),
+                                      g.plane * sizeof(double), hipMemcpyDeviceToDevice, s->ctx->stream));
+    }
+    s->next_cfl_min = -1.0;
+    return 0;
+}
+
+int state_alt(pyrohip_state *s)
+{
+    if (s->alt_base) return 0;
+    const size_t n = (size_t)s->nvar * s->g.plane + 16;
+    PYRO_CHECK_HIP(hipMalloc((void **)&s->alt_base, n * sizeof(double)));
+    PYRO_CHECK_HIP(hipMemsetAsync(s->alt_base, 0, n * sizeof(double), s->ctx->stream));
+    return 0;
+}
+
+int evolve_begin(pyrohip_state *s, const pyrohip_dt_policy *pol, double cfl, double dx, double dy,
+                 int max_steps, StepScalars *H)
+{
+    if (!s->d_scal) PYRO_CHECK_HIP(hipMalloc((void **)&s->d_scal, sizeof(StepScalars)));
+    if (s->dts_cap < max_steps + 1) {
+        if (s->d_dts) PYRO_CHECK_HIP(hipFree(s->d_dts));
+        s->d_dts = nullptr; s->dts_cap = 0;
+        // (not less than 1024: a run that asks for more steps call by call must not free + allocate every time)
+        const int cap = max_steps + 1 > 1024 ? max_steps + 1 : 1024;
+        PYRO_CHECK_HIP(hipMalloc((void **)&s->d_dts, (size_t)cap * sizeof(double)));
+        s->dts_cap = cap;
+    }
+    memset(H, 0, sizeof(*H));
+    H->t = pol->t; H->dt_old = pol->dt_old; H->n = pol->n;
+    H->tmax = pol->tmax; H->f0 = pol->init_tstep_factor; H->mx = pol->max_dt_change;
+    H->fix_dt = pol->fix_dt; H->cfl = cfl; H->dx = dx; H->dy = dy;
+    return 0;
+}
+
+int plane_to_host(pyrohip_state *s, const double *dev_plane, double *host)
+{
+    const Geom &g = s->g;
+    PYRO_CHECK_HIP(hipMemcpy2DAsync(host, g.qy * sizeof(double), dev_plane, g.pitch * sizeof(double),
+                                    g.qy * sizeof(double), g.qx, hipMemcpyDeviceToHost, s->ctx->stream));
+    return 0;
+}
+
 }  // namespace pyro
 
 using namespace pyro;
@@ -590,10 +661,7 @@ int pyrohip_state_download_var(pyrohip_state *s, int n, double *host)
     pyrohip_ctx *c = s->ctx;
     PYRO_CHECK_HIP(hipSetDevice(c->device));
     PYRO_TRY(comm_wait_halo(s));
-    const Geom &g = s->g;
-    PYRO_CHECK_HIP(hipMemcpy2DAsync(host, g.qy * sizeof(double), s->d + (size_t)n * g.plane,
-                                    g.pitch * sizeof(double), g.qy * sizeof(double), g.qx,
-                                    hipMemcpyDeviceToHost, c->stream));
+    PYRO_TRY(plane_to_host(s, s->d + (size_t)n * s->g.plane, host));
     PYRO_CHECK_HIP(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -752,9 +820,7 @@ int pyrohip_fill_bc(pyrohip_state *s, int n)
     if (n < 0) {
         // every ghost cell is now the image its side's rule gives (index maps only)
         bool rules = !s->nb_set;
-        for (size_t k = 0; k < s->bc.size(); k++)
-            rules = rules && (s->bc[k] == PYROHIP_BC_OUTFLOW || s->bc[k] == PYROHIP_BC_REFLECT_EVEN ||
-                              s->bc[k] == PYROHIP_BC_REFLECT_ODD || s->bc[k] == PYROHIP_BC_PERIODIC);
+        for (size_t k = 0; k < s->bc.size(); k++) rules = rules && bc_is_index_map(s->bc[k], true);
         s->ghost_by_rules = rules;
     }
     return 0;

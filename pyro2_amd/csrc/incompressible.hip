@@ -383,20 +383,6 @@ __global__ __launch_bounds__(256) void k_inc_proj_update(double *__restrict__ u,
     else if (gp_mode == 2) { gpx[k] = gx; gpy[k] = gy; }
 }
 
-static int bg_work(pyrohip_state *s)
-{
-    if (s->work_planes >= (size_t)W_NPL) return 0;
-    if (s->work) PYRO_CHECK_HIP(hipFree(s->work));
-    s->work = nullptr; s->work_planes = 0;
-    const size_t n = s->g.plane * W_NPL + 16;
-    PYRO_CHECK_HIP(hipMalloc((void **)&s->work, n * sizeof(double)));
-    // zero once: positions the kernels never write are read as 0, like the
-    // reference's scratch arrays
-    PYRO_CHECK_HIP(hipMemsetAsync(s->work, 0, n * sizeof(double), s->ctx->stream));
-    s->work_planes = W_NPL;
-    return 0;
-}
-
 static BP make_bp(double dx, double dy, double dt, int limiter, double nu = 0.0, double eps = 0.0)
 {
     BP P;
@@ -411,7 +397,7 @@ static int bg_predict(pyrohip_state *s, int iu, int iv, int igpx, int igpy, cons
     pyrohip_ctx *c = s->ctx;
     const Geom &g = s->g;
     PYRO_REQUIRE(g.ng >= 4, "the CTU predictor needs ng >= 4");
-    PYRO_TRY(bg_work(s));
+    PYRO_TRY(state_work(s, WorkOwner::INC, W_NPL));
     double *W = s->work + geom_lead(g);
     const double *u = s->d + (size_t)iu * g.plane, *v = s->d + (size_t)iv * g.plane;
     const double *gpx = igpx >= 0 ? s->d + (size_t)igpx * g.plane : nullptr;
@@ -481,7 +467,7 @@ int pyrohip_inc_advect(pyrohip_state *s, pyrohip_mg *m, int iu, int iv, int iphi
 {
     INC_CHECK_MG(s, m, F);
     BG_CHECK_VARS(s, iu, iv, iphimac, igpx, igpy);
-    PYRO_REQUIRE(s->work_planes >= (size_t)W_NPL, "call pyrohip_inc_mac_rhs first");
+    PYRO_REQUIRE(state_work_is(s, WorkOwner::INC, W_NPL), "call pyrohip_inc_mac_rhs first");
     const BP P = make_bp(dx, dy, dt, 0);
     const Geom &g = s->g;
     pyrohip_ctx *c = s->ctx;
@@ -551,7 +537,7 @@ int pyrohip_inc_visc_rhs(pyrohip_state *s, pyrohip_mg *m, int iw, int comp, int 
     BG_CHECK_VARS(s, iw, igp);
     PYRO_REQUIRE(comp == 0 || comp == 1, "comp: 0 = u, 1 = v");
     PYRO_REQUIRE(proj_type == 1 || proj_type == 2, "proj_type must be 1 or 2");
-    PYRO_REQUIRE(s->work_planes >= (size_t)W_NPL, "call pyrohip_inc_advect first");
+    PYRO_REQUIRE(state_work_is(s, WorkOwner::INC, W_NPL), "call pyrohip_inc_advect first");
     const BP P = make_bp(dx, dy, dt, 0, nu);
     const Geom &g = s->g;
     PYRO_TRY(pyrohip_mg_zero(m, F.level, 1));
@@ -580,7 +566,7 @@ int pyrohip_bgv_rhs(pyrohip_state *s, pyrohip_mg *m, int iw, int comp, double dx
     INC_CHECK_MG(s, m, F);
     BG_CHECK_VARS(s, iw);
     PYRO_REQUIRE(comp == 0 || comp == 1, "comp: 0 = u, 1 = v");
-    PYRO_REQUIRE(s->work_planes >= (size_t)W_NPL, "call pyrohip_bgv_predict first");
+    PYRO_REQUIRE(state_work_is(s, WorkOwner::INC, W_NPL), "call pyrohip_bgv_predict first");
     const BP P = make_bp(dx, dy, dt, 0, 0.0, eps);
     const Geom &g = s->g;
     PYRO_TRY(pyrohip_mg_zero(m, F.level, 0));   // init_zeros
@@ -610,13 +596,10 @@ int pyrohip_inc_stage_dump(pyrohip_state *s, int which, double *host)
 {
     PYRO_REQUIRE(s && host, "NULL argument");
     PYRO_REQUIRE(which >= 0 && which < 12, "which out of range");
-    PYRO_REQUIRE(s->work_planes >= (size_t)W_NPL, "no predictor work area yet");
+    PYRO_REQUIRE(state_work_is(s, WorkOwner::INC, W_NPL), "no predictor work area yet");
     const Geom &g = s->g;
     const int plane = (which < 8) ? C_UXL + which : W_UMAC + (which - 8);
-    PYRO_CHECK_HIP(hipMemcpy2DAsync(host, g.qy * sizeof(double),
-                                    s->work + geom_lead(g) + (size_t)plane * g.plane,
-                                    g.pitch * sizeof(double), g.qy * sizeof(double), g.qx,
-                                    hipMemcpyDeviceToHost, s->ctx->stream));
+    PYRO_TRY(plane_to_host(s, s->work + geom_lead(g) + (size_t)plane * g.plane, host));
     PYRO_CHECK_HIP(hipStreamSynchronize(s->ctx->stream));
     return 0;
 }

@@ -483,20 +483,6 @@ __global__ __launch_bounds__(256) void k_lm_dt_final(const double *__restrict__ 
 
 static size_t lm_base_stride(const Geom &g) { return (size_t)((g.qy + 15) / 16) * 16; }
 
-// work planes + the four base-state arrays behind them
-static int lm_work(pyrohip_state *s)
-{
-    if (s->work_planes == (size_t)L_NPL) return 0;
-    PYRO_REQUIRE(s->work == nullptr, "the state's work area belongs to another solver");
-    const size_t n = s->g.plane * L_NPL + 16 + 4 * lm_base_stride(s->g);
-    PYRO_CHECK_HIP(hipMalloc((void **)&s->work, n * sizeof(double)));
-    // zero once: positions the kernels never write are read as 0, like the reference's
-    // scratch arrays
-    PYRO_CHECK_HIP(hipMemsetAsync(s->work, 0, n * sizeof(double), s->ctx->stream));
-    s->work_planes = L_NPL;
-    return 0;
-}
-
 static LP make_lp(const pyrohip_state *s, double dx, double dy, double dt, int limiter,
                   double grav, double gamma)
 {
@@ -533,7 +519,7 @@ using namespace pyro;
     PYRO_REQUIRE((s), "NULL state");                                                           \
     PYRO_REQUIRE((s)->nvar == LV_NVAR && (s)->g.ng >= 4,                                       \
                  "lm_atm needs the solver's eight variables and ng >= 4");                     \
-    PYRO_REQUIRE((s)->work_planes == (size_t)L_NPL, "call pyrohip_lm_set_base first")
+    PYRO_REQUIRE(state_work_is((s), WorkOwner::LM, L_NPL), "call pyrohip_lm_set_base first")
 #define LM_CHECK_MG(s, m, F)                                                                   \
     LM_CHECK_STATE(s);                                                                         \
     PYRO_REQUIRE((m), "NULL mg");                                                              \
@@ -550,7 +536,8 @@ int pyrohip_lm_set_base(pyrohip_state *s, const double *rho0, const double *p0,
     PYRO_REQUIRE(s && rho0 && p0 && beta0 && beta0_edges, "NULL argument");
     PYRO_REQUIRE(s->nvar == LV_NVAR && s->g.ng >= 4,
                  "lm_atm needs the solver's eight variables and ng >= 4");
-    PYRO_TRY(lm_work(s));
+    // work planes + the four base-state arrays behind them; owner LM = the base state is set
+    PYRO_TRY(state_work(s, WorkOwner::LM, L_NPL, 4 * lm_base_stride(s->g)));
     const LP P = make_lp(s, 1.0, 1.0, 0.0, 0, 0.0, 0.0);
     const size_t nb = (size_t)s->g.qy * sizeof(double);
     hipStream_t st = s->ctx->stream;
@@ -718,10 +705,7 @@ int pyrohip_lm_stage_dump(pyrohip_state *s, int which, double *host)
     PYRO_REQUIRE(host, "NULL argument");
     PYRO_REQUIRE(which >= 0 && which < L_NPL - T_UXL, "which out of range");
     const Geom &g = s->g;
-    PYRO_CHECK_HIP(hipMemcpy2DAsync(host, g.qy * sizeof(double),
-                                    s->work + geom_lead(g) + (size_t)(T_UXL + which) * g.plane,
-                                    g.pitch * sizeof(double), g.qy * sizeof(double), g.qx,
-                                    hipMemcpyDeviceToHost, s->ctx->stream));
+    PYRO_TRY(plane_to_host(s, s->work + geom_lead(g) + (size_t)(T_UXL + which) * g.plane, host));
     PYRO_CHECK_HIP(hipStreamSynchronize(s->ctx->stream));
     return 0;
 }

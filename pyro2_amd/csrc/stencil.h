@@ -137,5 +137,29 @@ __device__ __forceinline__ int bc_src(const BcMap &m, int i, int lo, int hi)
     return i < lo ? m.alo * i + m.blo : (i > hi ? m.ahi * i + m.bhi : i);
 }
 
+// Tile kernels that load THROUGH the ghost fill (advection_nonuniform.hip, advection_rk.hip):
+// array cell (i, j) of a variable with the row / column maps mr / mc -> the offset of its interior
+// source cell in the plane.  Cells beyond the array feed discarded faces only: any address inside.
+// (G: the plane's geometry, common.h's Geom)
+template <class G>
+__device__ __forceinline__ size_t tile_src_off(const G &g, const BcMap &mr, const BcMap &mc, int i, int j)
+{
+    i = i < 0 ? 0 : (i > g.qx - 1 ? g.qx - 1 : i);
+    j = j < 0 ? 0 : (j > g.qy - 1 ? g.qy - 1 : j);
+    return (size_t)bc_src(mr, i, g.ilo, g.ihi) * g.pitch + bc_src(mc, j, g.jlo, g.jhi);
+}
+// ... and whether the value changes sign on the way (x fill, then y fill: the corner is the
+// composition of the two odd reflections)
+struct TileSrc { size_t off; bool neg; };
+template <class G>
+__device__ __forceinline__ TileSrc tile_src(const G &g, const BcMap &mr, const BcMap &mc, int i, int j)
+{
+    const size_t off = tile_src_off(g, mr, mc, i, j);
+    i = i < 0 ? 0 : (i > g.qx - 1 ? g.qx - 1 : i);       // (the clamped cell lies on the same side)
+    j = j < 0 ? 0 : (j > g.qy - 1 ? g.qy - 1 : j);
+    const bool nr = (i < g.ilo && mr.odd_lo) || (i > g.ihi && mr.odd_hi);
+    const bool nc = (j < g.jlo && mc.odd_lo) || (j > g.jhi && mc.odd_hi);
+    return TileSrc{off, nr != nc};
+}
 
 }  // namespace pyro

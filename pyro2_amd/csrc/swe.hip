@@ -886,11 +886,7 @@ int swe_step_wave(pyrohip_state *s, double dx, double dy, double grav, int limit
 {
     pyrohip_ctx *c = s->ctx;
     const Geom &g = s->g;
-    if (!s->alt_base) {
-        const size_t n = (size_t)s->nvar * g.plane + 16;
-        PYRO_CHECK_HIP(hipMalloc((void **)&s->alt_base, n * sizeof(double)));
-        PYRO_CHECK_HIP(hipMemsetAsync(s->alt_base, 0, n * sizeof(double), c->stream));
-    }
+    PYRO_TRY(state_alt(s));
     SWW P{dx, dy, dt, grav, limiter, 0, 0, 0, 0, 0, 0, nullptr, 0};
     const int slots = 8 * (c->num_cus > 0 ? c->num_cus : 256);
     P.ncb = (g.ny + SWW_OUT - 1) / SWW_OUT;
@@ -960,18 +956,6 @@ int restore_frame_after_inactive(pyrohip_state *s, int steps, int max_steps, boo
 using namespace pyro;
 using namespace pyro::swx;
 
-static int sw_work(pyrohip_state *s)
-{
-    if (s->work_planes >= (size_t)SW_NPL) return 0;
-    if (s->work) PYRO_CHECK_HIP(hipFree(s->work));
-    s->work = nullptr; s->work_planes = 0;
-    const size_t n = s->g.plane * SW_NPL + 16;
-    PYRO_CHECK_HIP(hipMalloc((void **)&s->work, n * sizeof(double)));
-    PYRO_CHECK_HIP(hipMemsetAsync(s->work, 0, n * sizeof(double), s->ctx->stream));
-    s->work_planes = SW_NPL;
-    return 0;
-}
-
 static int sw_check(pyrohip_state *s, double dx, double dy, double grav, int limiter, int riemann)
 {
     PYRO_REQUIRE(s, "NULL state");
@@ -1035,7 +1019,7 @@ int pyrohip_swe_step_ex(pyrohip_state *s, double dx, double dy, double grav, int
     if (kernel_set != 0)
         return fast_math ? swf::swe_step_wave(s, dx, dy, grav, limiter, riemann, dt, nullptr, nullptr, nullptr, false)
                          : swx::swe_step_wave(s, dx, dy, grav, limiter, riemann, dt, nullptr, nullptr, nullptr, false);
-    PYRO_TRY(sw_work(s));
+    PYRO_TRY(state_work(s, WorkOwner::SWE, SW_NPL));
     const SW P{dx, dy, dt, grav, limiter, riemann};
     double *W = s->work + geom_lead(g);
     const dim3 block(256);
@@ -1081,35 +1065,13 @@ int pyrohip_swe_evolve(pyrohip_state *s, double dx, double dy, double grav, int 
     // from the second step on the CFL minimum is the step kernel's (interior of the new state):
     // equal to the reference's whole-array minimum only where every ghost cell is an image of an
     // interior cell (a constant-value side is not: swe/simulation.py:127-141 after fill_BC_all)
-    for (int k = 0; k < 4 * s->nvar; k++) {
-        const int b = s->bc[k];
-        PYRO_REQUIRE(b == PYROHIP_BC_OUTFLOW || b == PYROHIP_BC_REFLECT_EVEN || b == PYROHIP_BC_REFLECT_ODD ||
-                         b == PYROHIP_BC_PERIODIC,
+    for (int k = 0; k < 4 * s->nvar; k++)
+        PYRO_REQUIRE(bc_is_index_map(s->bc[k], true),
                      "device-side stepping: outflow / reflect / periodic boundaries only");
-    }
     pyrohip_ctx *c = s->ctx;
-    if (!s->d_scal) PYRO_CHECK_HIP(hipMalloc((void **)&s->d_scal, sizeof(StepScalars)));
-    if (!s->d_flag) {
-        PYRO_CHECK_HIP(hipMalloc((void **)&s->d_flag, sizeof(int)));
-    }
-    if (s->dts_cap < max_steps + 1) {
-        if (s->d_dts) PYRO_CHECK_HIP(hipFree(s->d_dts));
-        s->d_dts = nullptr;
-        // (not less than 1024: a run that asks for more steps call by call must not free + allocate every time)
-        const int cap = max_steps + 1 > 1024 ? max_steps + 1 : 1024;
-        PYRO_CHECK_HIP(hipMalloc((void **)&s->d_dts, (size_t)cap * sizeof(double)));
-        s->dts_cap = cap;
-    }
-    if (!s->alt_base) {     // (k_fill_frame2 writes the second buffer's frame)
-        const size_t n = (size_t)s->nvar * s->g.plane + 16;
-        PYRO_CHECK_HIP(hipMalloc((void **)&s->alt_base, n * sizeof(double)));
-        PYRO_CHECK_HIP(hipMemsetAsync(s->alt_base, 0, n * sizeof(double), c->stream));
-    }
     StepScalars H;
-    memset(&H, 0, sizeof(H));
-    H.t = pol->t; H.dt_old = pol->dt_old; H.n = pol->n;
-    H.tmax = pol->tmax; H.f0 = pol->init_tstep_factor; H.mx = pol->max_dt_change;
-    H.fix_dt = pol->fix_dt; H.cfl = cfl; H.dx = dx; H.dy = dy;
+    PYRO_TRY(evolve_begin(s, pol, cfl, dx, dy, max_steps, &H));
+    PYRO_TRY(state_alt(s));     // (k_fill_frame2 writes the second buffer's frame)
     // (the CFL minimum the previous call's last step left, where nothing touched the state since:
     // pyrohip_comp_evolve)
     const bool min_cached = cfl_min_cached(s, 2, grav, dx, dy);
@@ -1192,7 +1154,7 @@ int pyrohip_swe_stage_dump(pyrohip_state *s, int stage, double *out)
 {
     PYRO_REQUIRE(s && out, "NULL argument");
     PYRO_REQUIRE(stage >= 0 && stage < 8, "stage out of range");
-    PYRO_REQUIRE(s->work_planes >= (size_t)SW_NPL && s->stages_valid,
+    PYRO_REQUIRE(state_work_is(s, WorkOwner::SWE, SW_NPL) && s->stages_valid,
                  "no staged swe step has been run on this state (the last step was the one-launch "
                  "kernel, which keeps no stage planes: pyrohip_swe_step_ks with kernel_set 0)");
     static const int first[8] = {SW_XP, SW_XM, SW_YP, SW_YM, SW_FXT, SW_FYT, SW_FX, SW_FY};
@@ -1203,10 +1165,7 @@ int pyrohip_swe_stage_dump(pyrohip_state *s, int stage, double *out)
     // cell so that out[i, j] is the reference's U_xl[i, j] / U_yl[i, j]
     const int si = (stage == 0) ? 1 : 0, sj = (stage == 2) ? 1 : 0;
     for (int n = 0; n < 4; n++) {
-        PYRO_CHECK_HIP(hipMemcpy2DAsync(tmp.data(), g.qy * sizeof(double),
-                                        s->work + geom_lead(g) + (size_t)(first[stage] + n) * g.plane,
-                                        g.pitch * sizeof(double), g.qy * sizeof(double), g.qx,
-                                        hipMemcpyDeviceToHost, c->stream));
+        PYRO_TRY(plane_to_host(s, s->work + geom_lead(g) + (size_t)(first[stage] + n) * g.plane, tmp.data()));
         PYRO_CHECK_HIP(hipStreamSynchronize(c->stream));
         for (int i = 0; i < g.qx; i++)
             for (int j = 0; j < g.qy; j++) {

@@ -158,6 +158,56 @@ def test_evolve_is_single_steps(dev, golden, k, nsteps):
     assert not np.array_equal(_plane(many), c["Uin"])
 
 
+def test_work_area_survives_a_change_of_solver(dev):
+    """A state's work area is one allocation that advection_rk (four planes), advection (one plane,
+    exchanged with the state's own allocation where both have one plane) and every other solver
+    use in turn.  The same four calls on ONE one-variable state and on a fresh state per call,
+    uploaded with the previous result, give the same bits after every call, ghost frame included,
+    in both builds: same kernels, same inputs.  8 x 8 is the smallest grid with room over the
+    entry points' nx >= 4.  And a work area that another solver filled is no answer to "has the
+    producer run": the compressible stage dump of a state on which only swe stepped is refused."""
+    nx = ny = 8
+    ng = 4
+    dx = dy = 1.0 / nx
+    x = (np.arange(nx + 2 * ng) - ng + 0.5) * dx
+    X, Y = np.meshgrid(x, x, indexing="ij")
+    a0 = 1.0 + 0.5 * np.sin(2 * np.pi * X) * np.cos(2 * np.pi * Y) + 0.25 * np.sin(4 * np.pi * (X + Y))
+    dts = [0.4 * dx, 0.3 * dx]
+
+    def fresh(a):
+        s = device.DeviceState(dev, nx, ny, ng, [["periodic"] * 4])
+        s.upload(np.ascontiguousarray(a[:, :, None]))
+        return s
+
+    for fast_math in (0, 1):
+        P = _lib.AdvRkParams(dx, dy, 1.0, 1.0, 2, 2, fast_math)
+        calls = (("advrk_evolve", lambda s: s.advrk_evolve(0, P, "RK4", dts)),
+                 ("adv_step, fill folded in",
+                  lambda s: s.adv_step(0, dx, dy, 1.0, 1.0, dts[0], 2, fill=True, fast_math=fast_math)),
+                 ("advrk_evolve again", lambda s: s.advrk_evolve(0, P, "RK4", dts)),
+                 ("adv_evolve", lambda s: s.adv_evolve(0, dx, dy, 1.0, 1.0, dts, 2, fast_math=fast_math)))
+        one, prev = fresh(a0), a0
+        for what, call in calls:
+            call(one)
+            each = fresh(prev)
+            call(each)
+            got, prev = _plane(one), _plane(each)
+            assert not np.array_equal(prev[ng:-ng, ng:-ng], a0[ng:-ng, ng:-ng])
+            _same(got, prev, f"fast_math {fast_math}, after {what}: one state against a fresh one per call")
+
+    # refusals stay refusals
+    h = np.zeros((nx + 2 * ng, ny + 2 * ng, 4))
+    h[:, :, 0] = 1.0 + 0.1 * np.exp(-40.0 * ((X - 0.5) ** 2 + (Y - 0.5) ** 2))
+    s = device.DeviceState(dev, nx, ny, ng, [["outflow"] * 4] * 4)
+    s.upload(h)
+    s.fill_bc()
+    s.swe_step(dx, dy, 1.0, 2, "Roe", 0.1 * dx, kernel_set=0)     # (the staged set: it has work planes)
+    s.swe_step(dx, dy, 1.0, 2, "Roe", 0.1 * dx)
+    with pytest.raises(_lib.PyroHipError, match="no staged step has been run") as e:
+        s.comp_stage("q")
+    assert e.value.code == ERR_ARG
+
+
 # ---- through the driver -----------------------------------------------------------------------
 
 @pytest.fixture
