@@ -248,24 +248,30 @@ int pyrohip_advnu_dt(pyrohip_state *s, int iu, int iv, double dx, double dy, dou
 int pyrohip_advnu_stage_dump(pyrohip_state *s, int ia, int iu, int iv,
                              const pyrohip_advnu_params *p, double dt, double *host);
 
-/* ---- advection_rk / advection_fv4: method-of-lines advection of a scalar with a constant
-        velocity (advection_rk/simulation.py:10-90, advection_rk/fluxes.py, advection_fv4/fluxes.py,
-        mesh/fourth_order.py, mesh/integration.py) ----
+/* ---- advection_rk / advection_fv4 / advection_weno: method-of-lines advection of a scalar with
+        a constant velocity (advection_rk/simulation.py:10-90, advection_rk/fluxes.py,
+        advection_fv4/fluxes.py, advection_weno/fluxes.py, mesh/fourth_order.py,
+        mesh/reconstruction.py weno_upwind, mesh/integration.py) ----
    One launch of a tile kernel per Runge-Kutta stage: the stage start (the linear combination of
    pyrohip_state_lincomb) is formed as the tile is loaded, every cell from its interior source
    cell under the boundary rules (outflow / reflect-even / periodic sides only), so ghost cells
    are never read from memory; the last stage also writes the final update.  ng must be 4.
    scheme      2: advection_rk (limiter 0 none, 1 MC 2nd order, otherwise MC 4th order; >= 10 is
                   refused: it does not run in the reference); 4: advection_fv4 (limiter 0: the
-                  unlimited face averages, otherwise the limited states of fourth_order.states)
+                  unlimited face averages, otherwise the limited states of fourth_order.states);
+               5: advection_weno (WENO reconstructions of order weno_order of the Lax-Friedrichs
+                  split fluxes (vel a +- alpha a) / 2; the limiter is not read)
    fast_math   0: bit-faithful arithmetic (results identical to NumPy / numba, true divisions by
                   dx and dy); 1: the contracted build                                          */
 typedef struct {
     double dx, dy;
     double u, v;       /* advection.u, advection.v */
     int limiter;       /* advection.limiter */
-    int scheme;        /* 2 | 4 */
+    int scheme;        /* 2 | 4 | 5 */
     int fast_math;
+    /* scheme 5 only (the other schemes do not read them) */
+    int weno_order;    /* advection.weno_order: 2 | 3 */
+    double alpha;      /* sqrt(u^2 + v^2) as the caller's arithmetic gives it: finite, >= 0 */
 } pyrohip_advrk_params;
 /* temporal methods of mesh/integration.py */
 #define PYROHIP_RK_RK2 0
@@ -288,7 +294,8 @@ int pyrohip_advrk_step(pyrohip_state *s, int var, const pyrohip_advrk_params *p,
 int pyrohip_advrk_evolve(pyrohip_state *s, int var, const pyrohip_advrk_params *p, int method,
                          const double *dts, int nsteps);
 /* test hook: the intermediates of stage `stage` of one step from the state as it is: the face
-   values a_x, a_y and the fluxes F_x, F_y on the lower faces of every cell, k_s, the stage
+   values a_x, a_y (scheme 5: the reconstructed positive parts of the split flux, flux_p_r of
+   fvs, in x and y) and the fluxes F_x, F_y on the lower faces of every cell, k_s, the stage
    start -- six (qx, qy) host arrays one after the other.  The state is not changed.  a_x, F_x
    are meaningful on rows ilo .. ihi + 1 of the interior columns, a_y, F_y on columns
    jlo .. jhi + 1 of the interior rows, k_s on the interior.                                   */

@@ -54,7 +54,8 @@ class AdvNuParams(C.Structure):
 class AdvRkParams(C.Structure):
     """pyrohip_advrk_params (include/pyrohip.h)"""
     _fields_ = [("dx", C.c_double), ("dy", C.c_double), ("u", C.c_double), ("v", C.c_double),
-                ("limiter", C.c_int), ("scheme", C.c_int), ("fast_math", C.c_int)]
+                ("limiter", C.c_int), ("scheme", C.c_int), ("fast_math", C.c_int),
+                ("weno_order", C.c_int), ("alpha", C.c_double)]      # (scheme 5 only)
 
 
 # temporal methods of mesh/integration.py -> PYROHIP_RK_*

@@ -1,10 +1,13 @@
 // Method-of-lines advection of a scalar with a constant velocity (advection_rk: second order,
-// advection_fv4: fourth order): ONE launch per Runge-Kutta stage.
+// advection_fv4: fourth order, advection_weno: WENO reconstructions of Lax-Friedrichs split
+// fluxes): ONE launch per Runge-Kutta stage.
 //
 // Replaces (reference file:line)
 //   pyro/advection_rk/simulation.py:10-90        substep, evolve
 //   pyro/advection_rk/fluxes.py:52-100           fluxes (second order)
 //   pyro/advection_fv4/fluxes.py:52-116          fluxes (fourth order)
+//   pyro/advection_weno/fluxes.py:6-105          fvs, fluxes (WENO)
+//   pyro/mesh/reconstruction.py:186-258          weno_upwind and its constants
 //   pyro/mesh/fourth_order.py:8-235              states (fv4_limit.h: mc_limit)
 //   pyro/mesh/reconstruction.py:9-120            limit / limit2 / limit4 (stencil.h)
 //   pyro/mesh/integration.py:103-129             get_stage_start, compute_final_update
@@ -19,7 +22,8 @@
 //      every coefficient is applied, zeros included.  No stage-start plane exists in memory.
 //   2. face values, fluxes and k_s = -div F of the tile (second order: limited slopes, upwind
 //      face value, F = u a; fourth order: face averages -- Eq. 17 or the limited states --,
-//      face centres by the transverse Laplacian, F = u a_cc + lap_t(u a) / 24).
+//      face centres by the transverse Laplacian, F = u a_cc + lap_t(u a) / 24; WENO: per face
+//      the two reconstructions of (u a +- alpha a) / 2 from the 2 R cells around it).
 //   3. LAST: the final update y_{n+1} = y_n + sum b_s dt k_s (compute_final_update's order, the
 //      stage's own k_s from registers) into a SECOND plane -- neighbouring tiles still read y_n
 //      for their halos in this launch; ghost cells of the new plane get the filled value of
@@ -35,19 +39,28 @@
 //                 sweep direction; the transverse Laplacians reach one face sideways: 1 cell.
 //                 The tile keeps ONE array of a with the larger apron on all four sides (the x
 //                 sweep needs rows +-4 x columns +-1, the y sweep the transpose).
+//   WENO:         face i reads cells i - R .. i + R - 1 (R = weno_order, 2 or 3): the second-order
+//                 tile with its 3 cells; no transverse reach.  ng = 4 > R: none of the zeros at
+//                 the ends of the reference's flux_p_r / flux_m_l reaches a face the update reads.
 // Nothing of the reference's zero-initialised scratch arrays is read inside those ranges except
 // d3a above the y sweep's last cell (mc_limit's d3a_top_zero), which is repeated.
 //
 // LDS (TI = 16, TJ = 32, 256 threads; y, the contiguous index, runs across the lanes, so that
 // neighbouring lanes read neighbouring 8-byte words -- conflict-free -- whichever neighbour of a
-// cell the stencil takes):      second order 14.9 KiB (+4 KiB in the last stage): 8 workgroups
-// per CU; fourth order 25.0 KiB (+4 KiB): 5 workgroups = 20 wavefronts per CU.
+// cell the stencil takes):      second order and WENO 14.9 KiB (+4 KiB in the last stage): 8
+// workgroups per CU; fourth order 25.0 KiB (+4 KiB): 5 workgroups = 20 wavefronts per CU.
 //
 // Compiled twice (build.py): bit-faithful (-ffp-contract=off, true divisions by dx, dy) and
 // contracted (-ffp-contract=fast, reciprocals); pyrohip_advrk_params.fast_math selects.
+// Two places of weno_upwind are not plain IEEE operations in the reference: np.dot at its end is
+// a chain of fused multiply-adds in the reference's BLAS -- the bit-faithful unit calls fma()
+// there --, and beta**2 is the C library's pow(), which is not always the product (libm_pow2.h).
+#include <cmath>
+
 #include "common.h"
 #include "stencil.h"
 #include "fv4_limit.h"
+#include "libm_pow2.h"
 
 #ifndef PYRO_FAST
 #define PYRO_FAST 0
@@ -65,6 +78,7 @@ constexpr int RK_DUMP_PLANES = 6;
 
 struct AdvRkArgs {
     double dx, dy, rdx, rdy, u, v;
+    double alpha;       // WENO: the speed of the Lax-Friedrichs split, sqrt(u^2 + v^2)
     double ca[3];       // dt a[s][0 .. NK): the stage start
     double cb[4];       // dt b[0 .. NK]: the final update (LAST)
     int limiter;
@@ -75,18 +89,70 @@ struct AdvRkArgs {
 
 namespace PYRO_NS {
 
+// mesh/reconstruction.py:224-258: weno_upwind of the window p[0 .. 2 R - 2], the reference's
+// operations in its order (beta and the stencil values start at 0.0; sigma's entries with m > l
+// are not visited).  The constants are the quotients the reference forms (:188-212).
+template <int R>
+__device__ __forceinline__ double weno_upwind(const double *p)
+{
+    static_assert(R == 2 || R == 3, "weno_order 2 or 3");
+    const double C3[3] = {1. / 10., 6. / 10., 3. / 10.};
+    const double a3[3][3] = {{11. / 6., -7. / 6., 2. / 6.}, {2. / 6., 5. / 6., -1. / 6.}, {-1. / 6., 5. / 6., 2. / 6.}};
+    const double s3[3][3][3] = {{{40. / 12., 0, 0}, {-124. / 12., 100. / 12., 0}, {44. / 12., -76. / 12., 16. / 12.}},
+                                {{16. / 12., 0, 0}, {-52. / 12., 52. / 12., 0}, {20. / 12., -52. / 12., 16. / 12.}},
+                                {{16. / 12., 0, 0}, {-76. / 12., 100. / 12., 0}, {44. / 12., -124. / 12., 40. / 12.}}};
+    const double C2[3] = {1. / 3., 2. / 3., 0};
+    const double a2[3][3] = {{3. / 2., -1. / 2., 0}, {1. / 2., 1. / 2., 0}, {0, 0, 0}};
+    const double s2[3][3][3] = {{{1., 0, 0}, {-2., 1., 0}, {0, 0, 0}}, {{1., 0, 0}, {-2., 1., 0}, {0, 0, 0}},
+                                {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}};
+    double al[R], st[R];
+#pragma unroll
+    for (int k = 0; k < R; k++) {
+        double beta = 0.0, sk = 0.0;
+#pragma unroll
+        for (int l = 0; l < R; l++) {
+#pragma unroll
+            for (int m = 0; m <= l; m++)
+                beta += ((R == 3 ? s3[k][l][m] : s2[k][l][m]) * p[R - 1 + k - l]) * p[R - 1 + k - m];
+        }
+#if PYRO_FAST
+        const double b2 = beta * beta;
+#else
+        const double b2 = square_as_libm_pow(beta);      // beta[k]**2 is the C library's pow()
+#endif
+        al[k] = (R == 3 ? C3[k] : C2[k]) / (1e-16 + b2);
+#pragma unroll
+        for (int l = 0; l < R; l++) sk += (R == 3 ? a3[k][l] : a2[k][l]) * p[R - 1 + k - l];
+        st[k] = sk;
+    }
+    double sum = al[0] + al[1];
+    if constexpr (R == 3) sum += al[2];
+#if PYRO_FAST
+    double d = al[0] * st[0] + al[1] * st[1];
+    if constexpr (R == 3) d += al[2] * st[2];
+    return d * (1.0 / sum);
+#else
+    // np.dot(w, q_stencils): fused multiply-adds from 0, in order
+    double d = 0.0;
+#pragma unroll
+    for (int k = 0; k < R; k++) d = fma(al[k] / sum, st[k], d);
+    return d;
+#endif
+}
+
 template <int SCHEME>
 struct RkTile {
-    static constexpr int H = SCHEME == 2 ? 3 : 4;          // apron of a
-    static constexpr int T = SCHEME == 2 ? 0 : 1;          // transverse reach of the face values
+    static constexpr int H = SCHEME == 4 ? 4 : 3;          // apron of a
+    static constexpr int T = SCHEME == 4 ? 1 : 0;          // transverse reach of the face values
     static constexpr int AH = RK_TI + 2 * H, AW = RK_TJ + 2 * H;
     static constexpr int XW = RK_TJ + 2 * T, NX = (RK_TI + 1) * XW;          // x faces 0 .. TI
     static constexpr int YW = RK_TJ + 1, NY = (RK_TI + 2 * T) * YW;          // y faces 0 .. TJ
-    static constexpr int NFX = SCHEME == 2 ? 1 : (RK_TI + 1) * RK_TJ;
-    static constexpr int NFY = SCHEME == 2 ? 1 : RK_TI * (RK_TJ + 1);
+    static constexpr int NFX = SCHEME == 4 ? (RK_TI + 1) * RK_TJ : 1;
+    static constexpr int NFY = SCHEME == 4 ? RK_TI * (RK_TJ + 1) : 1;
 };
 
-template <int SCHEME, int NK, bool LAST>
+// SCHEME 2 | 4 | 5 (WENO; R = weno_order, 0 otherwise)
+template <int SCHEME, int NK, bool LAST, int R = 0>
 __global__ __launch_bounds__(RK_THREADS) void k_advrk_stage(const double *__restrict__ y,
                                                             const double *__restrict__ kin, size_t kstride,
                                                             double *__restrict__ kout,
@@ -96,7 +162,7 @@ __global__ __launch_bounds__(RK_THREADS) void k_advrk_stage(const double *__rest
     using TL = RkTile<SCHEME>;
     constexpr int H = TL::H, T = TL::T, AW = TL::AW, TI = RK_TI, TJ = RK_TJ;
     __shared__ double A[TL::AH * TL::AW];      // the stage start
-    __shared__ double QX[TL::NX], QY[TL::NY];  // second order: F_x, F_y; fourth order: face averages
+    __shared__ double QX[TL::NX], QY[TL::NY];  // second order, WENO: F_x, F_y; fourth order: face averages
     __shared__ double FX[TL::NFX], FY[TL::NFY];
     __shared__ double Y1[LAST ? TI * TJ : 1];  // y_n + sum_{s < NK} b_s dt k_s (ghost cells: filled y_n)
     int bx, by;
@@ -168,6 +234,43 @@ __global__ __launch_bounds__(RK_THREADS) void k_advrk_stage(const double *__rest
             }
         }
         __syncthreads();
+    } else if constexpr (SCHEME == 5) {
+        // advection_weno/fluxes.py:28-39, 96-103: F = weno_upwind(f+ behind the face, left to
+        // right) + weno_upwind(f- in front of it, right to left), f+- = (vel a +- alpha a) / 2.
+        // x and y faces in ONE loop with one body -- the face's first cell and the stride along
+        // its pencil differ, nothing else --: 1072 faces are 5 passes of the workgroup, not 3 + 3,
+        // and the wavefront that holds the last x and the first y faces does not run the body twice
+        constexpr int NFX = (TI + 1) * TJ, NF = NFX + TI * (TJ + 1);
+#if PYRO_FAST
+        const double cpx = 0.5 * (u + P.alpha), cmx = 0.5 * (u - P.alpha);
+        const double cpy = 0.5 * (v + P.alpha), cmy = 0.5 * (v - P.alpha);
+#endif
+        for (int n = tid; n < NF; n += RK_THREADS) {
+            const bool isx = n < NFX;
+            const int m = isx ? n : n - NFX, w = isx ? TJ : TJ + 1;
+            const int r = m / w, c = m - r * w;
+            const int k = (r + H) * AW + c + H, sd = isx ? AW : 1;      // the cell in front of the face
+            double fp[2 * R], fm[2 * R];
+#pragma unroll
+            for (int e = 0; e < 2 * R; e++) {
+                const double q = A[k + (e - R) * sd];
+#if PYRO_FAST
+                fp[e] = (isx ? cpx : cpy) * q;
+                fm[2 * R - 1 - e] = (isx ? cmx : cmy) * q;
+#else
+                const double fl = (isx ? u : v) * q, aq = P.alpha * q;
+                fp[e] = (fl + aq) / 2;
+                fm[2 * R - 1 - e] = (fl - aq) / 2;
+#endif
+            }
+            const double fpr = weno_upwind<R>(fp), f = fpr + weno_upwind<R>(fm);
+            (isx ? QX : QY)[m] = f;
+            if (dump && (isx ? r < TI : c < TJ) && in_array(I0 + r, J0 + c)) {
+                double *d = dump + (isx ? 0 : g.plane) + (size_t)(I0 + r) * g.pitch + J0 + c;
+                d[0] = fpr; d[2 * g.plane] = f;
+            }
+        }
+        __syncthreads();
     } else {
         // advection_fv4/fluxes.py:64-84: face averages.  Limited: a_l (from the cell behind the
         // face) when the velocity is > 0, else a_r (from the cell in front of it) -- u == 0
@@ -236,7 +339,7 @@ __global__ __launch_bounds__(RK_THREADS) void k_advrk_stage(const double *__rest
     }
 
     // ---- 3. k_s = -div F on the interior; LAST: the new level on the whole array
-    const double *Fx = SCHEME == 2 ? QX : FX, *Fy = SCHEME == 2 ? QY : FY;
+    const double *Fx = SCHEME == 4 ? FX : QX, *Fy = SCHEME == 4 ? FY : QY;
     for (int n = tid; n < TI * TJ; n += RK_THREADS) {
         const int r = n / TJ, c = n - r * TJ;
         const int i = I0 + r, j = J0 + c;
@@ -271,7 +374,7 @@ int advrk_stage_launch(pyrohip_state *s, int var, const pyrohip_advrk_params *ap
     const Geom &g = s->g;
     AdvRkArgs P;
     P.dx = ap->dx; P.dy = ap->dy; P.rdx = 1.0 / ap->dx; P.rdy = 1.0 / ap->dy;
-    P.u = ap->u; P.v = ap->v;
+    P.u = ap->u; P.v = ap->v; P.alpha = ap->scheme == 5 ? ap->alpha : 0.0;
     for (int k = 0; k < 3; k++) P.ca[k] = ca ? ca[k] : 0.0;
     for (int k = 0; k < 4; k++) P.cb[k] = cb ? cb[k] : 0.0;
     P.limiter = ap->limiter;
@@ -279,23 +382,25 @@ int advrk_stage_launch(pyrohip_state *s, int var, const pyrohip_advrk_params *ap
     P.gx = (g.qy + P.oj + RK_TJ - 1) / RK_TJ; P.gy = (g.qx + RK_TI - 1) / RK_TI;
     for (int k = 0; k < 4; k++) P.bc[k] = s->bc[var * 4 + k];
     const dim3 grid(xcd_grid_1d(P.gx, P.gy)), block(RK_THREADS);
-#define ADVRK_GO(SCH, NK, LAST)                                                                       \
-    PYRO_LAUNCH(c, "k_advrk_stage", (k_advrk_stage<SCH, NK, LAST>), grid, block, 0, y, kin, kstride,  \
-                kout, ynew, g, P, dump)
-#define ADVRK_SCHEME(SCH)                                                                             \
+#define ADVRK_GO(SCH, NK, LAST, R)                                                                    \
+    PYRO_LAUNCH(c, "k_advrk_stage", (k_advrk_stage<SCH, NK, LAST, R>), grid, block, 0, y, kin,        \
+                kstride, kout, ynew, g, P, dump)
+#define ADVRK_SCHEME(SCH, R)                                                                          \
     do {                                                                                              \
         if (!last) {                                                                                  \
-            if (nk == 0) ADVRK_GO(SCH, 0, false);                                                     \
-            else if (nk == 1) ADVRK_GO(SCH, 1, false);                                                \
-            else ADVRK_GO(SCH, 2, false);                                                             \
+            if (nk == 0) ADVRK_GO(SCH, 0, false, R);                                                  \
+            else if (nk == 1) ADVRK_GO(SCH, 1, false, R);                                             \
+            else ADVRK_GO(SCH, 2, false, R);                                                          \
         } else {                                                                                      \
-            if (nk == 1) ADVRK_GO(SCH, 1, true);                                                      \
-            else if (nk == 2) ADVRK_GO(SCH, 2, true);                                                 \
-            else ADVRK_GO(SCH, 3, true);                                                              \
+            if (nk == 1) ADVRK_GO(SCH, 1, true, R);                                                   \
+            else if (nk == 2) ADVRK_GO(SCH, 2, true, R);                                              \
+            else ADVRK_GO(SCH, 3, true, R);                                                           \
         }                                                                                             \
     } while (0)
-    if (ap->scheme == 2) ADVRK_SCHEME(2);
-    else ADVRK_SCHEME(4);
+    if (ap->scheme == 2) ADVRK_SCHEME(2, 0);
+    else if (ap->scheme == 4) ADVRK_SCHEME(4, 0);
+    else if (ap->weno_order == 2) ADVRK_SCHEME(5, 2);
+    else ADVRK_SCHEME(5, 3);
 #undef ADVRK_SCHEME
 #undef ADVRK_GO
     PYRO_CHECK_HIP(hipGetLastError());
@@ -333,9 +438,16 @@ int advrk_check(pyrohip_state *s, int var, const pyrohip_advrk_params *ap)
 {
     PYRO_REQUIRE(s && ap, "NULL argument");
     PYRO_REQUIRE(var >= 0 && var < s->nvar, "variable index out of range");
-    PYRO_REQUIRE(s->g.ng == 4, "advection_rk / advection_fv4 are built for ng = 4");
+    PYRO_REQUIRE(s->g.ng == 4, "advection_rk / advection_fv4 / advection_weno are built for ng = 4");
     PYRO_REQUIRE(s->g.nx >= 4 && s->g.ny >= 4, "the grid must be at least as wide as its ghost frame");
-    PYRO_REQUIRE(ap->scheme == 2 || ap->scheme == 4, "scheme must be 2 (advection_rk) or 4 (advection_fv4)");
+    PYRO_REQUIRE(ap->scheme == 2 || ap->scheme == 4 || ap->scheme == 5,
+                 "scheme must be 2 (advection_rk), 4 (advection_fv4) or 5 (advection_weno)");
+    if (ap->scheme == 5) {
+        // (advection_weno/fluxes.py:89: the reference's assert)
+        PYRO_REQUIRE(ap->weno_order == 2 || ap->weno_order == 3, "advection_weno: weno_order must be 2 or 3");
+        PYRO_REQUIRE(ap->alpha >= 0.0 && std::isfinite(ap->alpha),
+                     "advection_weno: alpha must be finite and not negative");
+    }
     PYRO_REQUIRE(ap->limiter >= 0, "negative limiter");
     PYRO_REQUIRE(ap->scheme != 2 || ap->limiter < 10,
                  "advection_rk: limiter >= 10 does not run in the reference (advection_rk/fluxes.py:72)");
@@ -417,9 +529,10 @@ extern "C" int pyrohip_advrk_step(pyrohip_state *s, int var, const pyrohip_advrk
     return pyrohip_advrk_evolve(s, var, ap, method, &dt, 1);
 }
 
-// test hook: the intermediates of stage `stage` of one step from the state as it is -- a_x, a_y,
-// F_x, F_y on the lower faces of every cell, k_s and the stage start: six (qx, qy) host arrays one
-// after the other.  The state is not changed.
+// test hook: the intermediates of stage `stage` of one step from the state as it is -- a_x, a_y
+// (WENO: the reconstructed positive parts, flux_p_r of fvs, in x and y), F_x, F_y on the lower
+// faces of every cell, k_s and the stage start: six (qx, qy) host arrays one after the other.
+// The state is not changed.
 extern "C" int pyrohip_advrk_stage_dump(pyrohip_state *s, int var, const pyrohip_advrk_params *ap,
                                         int method, double dt, int stage, double *host)
 {

@@ -576,7 +576,7 @@ class DeviceState:
                                            C.byref(dt)))
         return dt.value
 
-    # ---- advection_rk / advection_fv4 (csrc/advection_rk.hip) -----------------
+    # ---- advection_rk / advection_fv4 / advection_weno (csrc/advection_rk.hip) ----
     @staticmethod
     def _advrk_method(method):
         from ._lib import RK_METHODS
@@ -605,7 +605,8 @@ class DeviceState:
 
     def advrk_stages(self, n, params, method, dt, stage):
         """(a_x, a_y, F_x, F_y, k_s, stage start) of stage `stage` of one step from the state as
-        it is, (6, qx, qy); the state stays as it is (test hook)"""
+        it is, (6, qx, qy); the state stays as it is (test hook).  Scheme 5: planes 0 and 1 are
+        the reconstructed positive parts of the split flux (flux_p_r) in x and y"""
         m = self._advrk_method(method)
         out = np.zeros((6, self.qx, self.qy))
         with self.ctx.lock:

@@ -1,9 +1,10 @@
-"""developer tool: time per Runge-Kutta step of advection_rk and advection_fv4 (RK4, periodic, the
-solvers' default limiters) at 2048^2 and 4096^2, both builds, and in the same process of the
+"""developer tool: time per Runge-Kutta step of advection_rk, advection_fv4 (the solvers' default
+limiters) and advection_weno (weno_order 3 and 2) -- RK4, periodic -- at 2048^2 and 4096^2, both
+builds, and in the same process of the
 stage-by-stage path (pyrohip_state_lincomb + ghost fill + pyrohip_advrk_rhs per stage, the final
 pyrohip_state_lincomb) that the fused step replaces (GPU box).
 
-    python tools/advrk_time.py [out.json]        # SIZES=2048,4096
+    python tools/advrk_time.py [out.json]        # SIZES=2048,4096 SCHEMES=2,4,5
 
 Event timers around a batch of steps (one pyrohip_advrk_evolve call: no host work between the
 steps), after at least 50 ms of untimed steps (the clocks ramp); best of three batches, all three
@@ -26,6 +27,9 @@ from pyro2_amd.mesh import integration  # noqa: E402
 
 PEAK = 8.0e12      # B/s, HBM3E of the MI355X
 SIZES = [int(s) for s in os.environ.get("SIZES", "2048,4096").split(",")]
+SCHEMES = [int(s) for s in os.environ.get("SCHEMES", "2,4,5").split(",")]
+# (scheme, limiter, weno_order)
+CONFIGS = [c for c in ((2, 2, 0), (4, 1, 0), (5, 0, 3), (5, 0, 2)) if c[0] in SCHEMES]
 METHOD = "RK4"
 CTU_2048_US = 21.3
 ctx = device.Context(0)
@@ -67,9 +71,10 @@ for nx in SIZES:
     per = [["periodic"] * 4]
     cells = float(nx) * nx
     ns = len(integration.b[METHOD])
-    for scheme, lim in ((2, 2), (4, 1)):
+    for scheme, lim, order in CONFIGS:
         for fast in (1, 0):
             P = _lib.AdvRkParams(dx, dx, 1.0, 1.0, lim, scheme, fast)
+            P.weno_order, P.alpha = order, float(np.sqrt(1.0**2 + 1.0**2))
             st = device.DeviceState(ctx, nx, nx, 4, per)
             st.upload(np.ascontiguousarray(dens[:, :, None]))
             ms, every = timed(lambda n: st.advrk_evolve(0, P, METHOD, [dt] * n), nsteps)
@@ -89,14 +94,15 @@ for nx in SIZES:
                     rk.compute_final_update()
             ums, uevery = timed(unfused, max(nsteps // 2, 5))
             del su, rk
-            rec = {"nx": nx, "scheme": scheme, "limiter": lim, "fast_math": fast, "method": METHOD,
+            rec = {"nx": nx, "scheme": scheme, "limiter": lim, "weno_order": order, "fast_math": fast,
+                   "method": METHOD,
                    "us_per_step": 1e3 * ms, "runs_us": [1e3 * m for m in every],
                    "unfused_us_per_step": 1e3 * ums, "unfused_runs_us": [1e3 * m for m in uevery],
                    "hbm_floor_us": floor_us(cells, ns), "gcell_per_s": cells / ms / 1e6,
                    "ctu_advection_2048_us": CTU_2048_US,
                    "density_min_max_sum": [float(out.min()), float(out.max()), float(out.sum())]}
             results.append(rec)
-            print(f"scheme {scheme} lim {lim} nx={nx} fast={fast}: {1e3 * ms:9.2f} us/step "
+            print(f"scheme {scheme} lim {lim} order {order} nx={nx} fast={fast}: {1e3 * ms:9.2f} us/step "
                   f"({cells / ms / 1e6:6.2f} Gcell/s; floor {rec['hbm_floor_us']:.1f} us = "
                   f"{rec['hbm_floor_us'] / (1e3 * ms):.2f} of it)   stage by stage {1e3 * ums:9.2f} us/step "
                   f"(x{ums / ms:.2f})   runs: " + " ".join(f"{1e3 * m:.1f}" for m in every)
