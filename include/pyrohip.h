@@ -301,6 +301,10 @@ int pyrohip_advrk_evolve(pyrohip_state *s, int var, const pyrohip_advrk_params *
    jlo .. jhi + 1 of the interior rows, k_s on the interior.                                   */
 int pyrohip_advrk_stage_dump(pyrohip_state *s, int var, const pyrohip_advrk_params *p, int method,
                              double dt, int stage, double *host);
+/* test hook: out[i] = the bit-faithful WENO kernels' stand-in for the C library's pow(x[i], 2.0)
+   (csrc/libm_pow2.h: square_as_libm_pow), evaluated on the device; x and out are host arrays of n
+   doubles                                                                                      */
+int pyrohip_test_square_as_pow(pyrohip_ctx *ctx, const double *x, size_t n, double *out);
 
 /* ---- compressible ---------------------------------------------------- */
 /* conserved order: density(0) energy(1) x-momentum(2) y-momentum(3)

@@ -570,3 +570,69 @@ def comp_fill_bc_ramp(U, nx, ny, ng, bcs, rp):
     f.restype = None
     f(_p(U), nx, ny, ng, vb.ctypes.data_as(C.POINTER(C.c_int)), _p(rp["x"]),
       C.c_double(rp["cxoff"]), _p(rp["post"]), _p(rp["pre"]), _p(rp["sf_down"]), _p(rp["sf_up"]))
+
+
+# ---- method-of-lines advection (advection_rk, advection_fv4, advection_weno) --------------
+RK_METHODS = {"RK2": 0, "TVD2": 1, "TVD3": 2, "RK4": 3}
+RK_STAGES = {"RK2": 2, "TVD2": 2, "TVD3": 3, "RK4": 4}
+ADVMOL_PLANES = ("start", "a_x", "a_y", "F_x", "F_y", "k")
+
+
+def _ibc(bcs):
+    return np.ascontiguousarray(bc_codes(bcs)).ctypes.data_as(C.POINTER(C.c_int))
+
+
+def advmol_rhs(a, nx, ny, ng, bcs, dx, dy, u, v, scheme, par, alpha=0.0):
+    """fills the ghost cells of the (qx,qy) plane a in place; returns a dict of (qx,qy) planes:
+    the face values a_x, a_y (scheme 5: flux_p_r of every pencil), F_x, F_y and k = -div F.
+    par: the limiter (schemes 2, 4) or weno_order (scheme 5)"""
+    _ck(a)
+    out = {n: np.zeros_like(a) for n in ADVMOL_PLANES[1:]}
+    f = lib().orc_advmol_rhs
+    f.restype = None
+    f(_p(a), nx, ny, ng, _ibc(bcs), C.c_double(dx), C.c_double(dy), C.c_double(u), C.c_double(v),
+      int(scheme), int(par), C.c_double(alpha), *[_p(out[n]) for n in ADVMOL_PLANES[1:]])
+    return out
+
+
+def advmol_step(a, nx, ny, ng, bcs, dx, dy, u, v, scheme, par, method, dt, alpha=0.0, stages=False):
+    """one Runge-Kutta step of mesh/integration.py in place on the (qx,qy) plane a (its ghost
+    frame ends as the fill of the old level).  stages: returns per stage a dict of the planes
+    ADVMOL_PLANES (the stage start after its fill, face values, fluxes, k)"""
+    _ck(a)
+    ns = RK_STAGES[method]
+    dump = np.zeros((ns, 6) + a.shape) if stages else None
+    f = lib().orc_advmol_step
+    f.restype = C.c_int
+    got = f(_p(a), nx, ny, ng, _ibc(bcs), C.c_double(dx), C.c_double(dy), C.c_double(u), C.c_double(v),
+            int(scheme), int(par), C.c_double(alpha), RK_METHODS[method], C.c_double(dt),
+            _p(dump) if stages else None)
+    assert got == ns
+    if stages:
+        return [dict(zip(ADVMOL_PLANES, dump[s])) for s in range(ns)]
+    return None
+
+
+def advnu_step(a, u, v, nx, ny, ng, bcs3, dx, dy, dt, limiter, stages=False):
+    """one step of advection_nonuniform in place on the (qx,qy) plane a.  u, v: the velocity
+    planes as they are before the fill (not changed: the step works on filled copies); bcs3: the
+    boundary types of a, u and v.  stages: returns (a_x, a_y, F_x, F_y), (4, qx, qy)"""
+    _ck(a)
+    uu, vv = np.array(u, dtype=np.float64, order="C"), np.array(v, dtype=np.float64, order="C")
+    bc = np.ascontiguousarray(np.concatenate([bc_codes(b) for b in bcs3]))
+    dump = np.zeros((4,) + a.shape) if stages else None
+    f = lib().orc_advnu_step
+    f.restype = None
+    f(_p(a), _p(uu), _p(vv), nx, ny, ng, bc.ctypes.data_as(C.POINTER(C.c_int)), C.c_double(dx),
+      C.c_double(dy), C.c_double(dt), int(limiter), _p(dump) if stages else None)
+    return dump
+
+
+def pow2(x):
+    """the host C library's pow(x, 2.0), element by element"""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    out = np.empty_like(x)
+    f = lib().orc_pow2
+    f.restype = None
+    f(_p(x), C.c_size_t(x.size), _p(out))
+    return out

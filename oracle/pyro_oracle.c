@@ -27,6 +27,7 @@
  * Python grid attrs: ilo=ng, ihi=ng+nx-1 (inclusive).
  */
 #include <math.h>
+#include <stddef.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -3299,4 +3300,278 @@ int orc_fv4_rhs(double *U, const orc_comp_params *P, double *kout, double *o_Fx,
 #undef U4
 #undef I2
     return rc;
+}
+
+/* ================================================================== */
+/* Method-of-lines advection of a scalar with a constant velocity:     */
+/* advection_rk/fluxes.py:52-100 (scheme 2), advection_fv4/fluxes.py:  */
+/* 52-116 (scheme 4), advection_weno/fluxes.py:6-105 with              */
+/* mesh/reconstruction.py:186-258 (scheme 5), the substep of           */
+/* advection_rk/simulation.py:10-28 and the Runge-Kutta driver of      */
+/* mesh/integration.py:32-129.  One (qx,qy) plane; bc = xl,xr,yl,yr.   */
+/* ================================================================== */
+void orc_pow2(const double *x, size_t n, double *out)
+{
+    for (size_t k = 0; k < n; k++) out[k] = pypow2(x[k]);
+}
+
+/* reconstruction.weno_upwind of q[0 .. 2 order - 2]; q is read with stride qs (negative for the
+   reversed window of flux_m) */
+static double advmol_weno_upwind(const double *q, ptrdiff_t qs, int order)
+{
+    /* the quotients the reference forms: integer arrays divided by 3, 2, 10, 6, 12
+       (reconstruction.py:188-212); order 2 keeps its integer sigma */
+    static const double C3[2] = {1.0 / 3, 2.0 / 3};
+    static const double a3[2][2] = {{3.0 / 2, -1.0 / 2}, {1.0 / 2, 1.0 / 2}};
+    static const double s3[2][2][2] = {{{1, 0}, {-2, 1}}, {{1, 0}, {-2, 1}}};
+    static const double C5[3] = {1.0 / 10, 6.0 / 10, 3.0 / 10};
+    static const double a5[3][3] = {{11.0 / 6, -7.0 / 6, 2.0 / 6}, {2.0 / 6, 5.0 / 6, -1.0 / 6},
+                                    {-1.0 / 6, 5.0 / 6, 2.0 / 6}};
+    static const double s5[3][3][3] = {
+        {{40.0 / 12, 0, 0}, {-124.0 / 12, 100.0 / 12, 0}, {44.0 / 12, -76.0 / 12, 16.0 / 12}},
+        {{16.0 / 12, 0, 0}, {-52.0 / 12, 52.0 / 12, 0}, {20.0 / 12, -52.0 / 12, 16.0 / 12}},
+        {{16.0 / 12, 0, 0}, {-76.0 / 12, 100.0 / 12, 0}, {44.0 / 12, -124.0 / 12, 40.0 / 12}}};
+    const double epsilon = 1e-16;
+    double alpha[3] = {0, 0, 0}, beta[3] = {0, 0, 0}, qst[3] = {0, 0, 0};
+    for (int k = 0; k < order; k++) {
+        for (int l = 0; l < order; l++)
+            for (int m = 0; m <= l; m++) {
+                const double sg = order == 2 ? s3[k][l][m] : s5[k][l][m];
+                beta[k] += sg * q[(order - 1 + k - l) * qs] * q[(order - 1 + k - m) * qs];
+            }
+        alpha[k] = (order == 2 ? C3[k] : C5[k]) / (epsilon + pypow2(beta[k]));
+        for (int l = 0; l < order; l++)
+            qst[k] += (order == 2 ? a3[k][l] : a5[k][l]) * q[(order - 1 + k - l) * qs];
+    }
+    double sum = alpha[0];                      /* np.sum: left to right */
+    for (int k = 1; k < order; k++) sum += alpha[k];
+    double d = 0.0;                             /* np.dot: fused multiply-adds from 0 */
+    for (int k = 0; k < order; k++) d = fma(alpha[k] / sum, qst[k], d);
+    return d;
+}
+
+/* advection_weno/fluxes.fvs of the pencil q[0 .. n) (stride qs): flux (fluxes.py:28-39) and
+   flux_p_r, both with stride qs as well */
+static void advmol_fvs(const double *q, int n, ptrdiff_t qs, int order, double vel, double alpha,
+                       double *flux, double *fpr, double *wk /* 3 n */)
+{
+    double *fp = wk, *fm = wk + n, *fml = wk + 2 * n;
+    for (int i = 0; i < n; i++) {
+        const double f = vel * q[i * qs];
+        flux[i * qs] = f;
+        fp[i] = (f + alpha * q[i * qs]) / 2;
+        fm[i] = (f - alpha * q[i * qs]) / 2;
+        fpr[i * qs] = 0.0;
+        fml[i] = 0.0;
+    }
+    for (int i = order; i < n - order; i++) {
+        fpr[i * qs] = advmol_weno_upwind(fp + i - order, 1, order);
+        fml[i] = advmol_weno_upwind(fm + i + order - 1, -1, order);
+    }
+    for (int i = 1; i < n - 1; i++) flux[i * qs] = fpr[i * qs] + fml[i];
+}
+
+/* fill the ghost cells of a, then the face values (scheme 5: flux_p_r of fvs), the fluxes and
+   k = -div F.  par: the limiter (schemes 2, 4) or weno_order (scheme 5).  Outputs are whole
+   (qx,qy) planes as the reference's scratch arrays hold them; any may be NULL. */
+void orc_advmol_rhs(double *a, int nx, int ny, int ng, const int *bc, double dx, double dy, double u,
+                    double v, int scheme, int par, double alpha, double *o_ax, double *o_ay,
+                    double *o_Fx, double *o_Fy, double *o_k)
+{
+    const int qx = nx + 2 * ng, qy = ny + 2 * ng;
+    const int ilo = ng, ihi = ng + nx - 1, jlo = ng, jhi = ng + ny - 1;
+    const size_t N = (size_t)qx * qy;
+    double *ax = zalloc(N), *ay = zalloc(N), *Fx = zalloc(N), *Fy = zalloc(N);
+#define I2(i, j) ((size_t)(i) * qy + (j))
+    orc_fill_ghost(a, nx, ny, ng, 1, 0, bc);
+    if (scheme == 2) {
+        double *ldx = zalloc(N), *ldy = zalloc(N);
+        orc_limit(a, 1, nx, ny, ng, 1, par, ldx);
+        orc_limit(a, 1, nx, ny, ng, 2, par, ldy);
+        for (int i = ilo - 1; i <= ihi + 1; i++)
+            for (int j = jlo - 1; j <= jhi + 1; j++) {
+                if (u < 0) ax[I2(i, j)] = a[I2(i, j)] - 0.5 * ldx[I2(i, j)];
+                else ax[I2(i, j)] = a[I2(i - 1, j)] + 0.5 * ldx[I2(i - 1, j)];
+                if (v < 0) ay[I2(i, j)] = a[I2(i, j)] - 0.5 * ldy[I2(i, j)];
+                else ay[I2(i, j)] = a[I2(i, j - 1)] + 0.5 * ldy[I2(i, j - 1)];
+            }
+        for (size_t k = 0; k < N; k++) { Fx[k] = u * ax[k]; Fy[k] = v * ay[k]; }
+        free(ldx); free(ldy);
+    } else if (scheme == 4) {
+        if (par == 0) {
+            for (int i = ilo - 1; i <= ihi + 1; i++)
+                for (int j = jlo - 1; j <= jhi + 1; j++) {
+                    ax[I2(i, j)] = 7. / 12. * (a[I2(i - 1, j)] + a[I2(i, j)]) -
+                                   1. / 12. * (a[I2(i - 2, j)] + a[I2(i + 1, j)]);
+                    ay[I2(i, j)] = 7. / 12. * (a[I2(i, j - 1)] + a[I2(i, j)]) -
+                                   1. / 12. * (a[I2(i, j - 2)] + a[I2(i, j + 1)]);
+                }
+        } else {
+            double *al = zalloc(N), *ar = zalloc(N), *wk = zalloc(6 * N);
+            fv4_states(a, qx, qy, ng, 1, al, ar, wk);
+            memcpy(ax, u > 0 ? al : ar, N * 8);
+            fv4_states(a, qx, qy, ng, 2, al, ar, wk);
+            memcpy(ay, v > 0 ? al : ar, N * 8);
+            free(al); free(ar); free(wk);
+        }
+        /* MC Eqs. 18-20: bufx = (0, 1, 0, 0), bufy = (0, 0, 0, 1) */
+        for (int i = ilo; i <= ihi + 1; i++)
+            for (int j = jlo; j <= jhi; j++) {
+                const double cc = ax[I2(i, j)] -
+                                  1. / 24 * (ax[I2(i, j - 1)] - 2 * ax[I2(i, j)] + ax[I2(i, j + 1)]);
+                Fx[I2(i, j)] = u * cc + 1. / 24 * (u * ax[I2(i, j - 1)] - 2 * (u * ax[I2(i, j)]) +
+                                                   u * ax[I2(i, j + 1)]);
+            }
+        for (int i = ilo; i <= ihi; i++)
+            for (int j = jlo; j <= jhi + 1; j++) {
+                const double cc = ay[I2(i, j)] -
+                                  1. / 24 * (ay[I2(i - 1, j)] - 2 * ay[I2(i, j)] + ay[I2(i + 1, j)]);
+                Fy[I2(i, j)] = v * cc + 1. / 24 * (v * ay[I2(i - 1, j)] - 2 * (v * ay[I2(i, j)]) +
+                                                   v * ay[I2(i + 1, j)]);
+            }
+    } else {
+        /* the pencils of the whole array; ax, ay take flux_p_r */
+        const int nmax = qx > qy ? qx : qy;
+        double *wk = zalloc(3 * (size_t)nmax);
+        for (int j = 0; j < qy; j++)
+            advmol_fvs(a + j, qx, qy, par, u, alpha, Fx + j, ax + j, wk);
+        for (int i = 0; i < qx; i++)
+            advmol_fvs(a + I2(i, 0), qy, 1, par, v, alpha, Fy + I2(i, 0), ay + I2(i, 0), wk);
+        /* F_x.v(buf = ng)[1:-1, j] = fvs(...)[1:-1]: the ends of the scratch arrays stay 0 */
+        for (int j = 0; j < qy; j++) Fx[I2(0, j)] = Fx[I2(qx - 1, j)] = 0.0;
+        for (int i = 0; i < qx; i++) Fy[I2(i, 0)] = Fy[I2(i, qy - 1)] = 0.0;
+        free(wk);
+    }
+    if (o_k) {
+        memset(o_k, 0, N * 8);
+        for (int i = ilo; i <= ihi; i++)
+            for (int j = jlo; j <= jhi; j++)
+                o_k[I2(i, j)] = (Fx[I2(i, j)] - Fx[I2(i + 1, j)]) / dx + (Fy[I2(i, j)] - Fy[I2(i, j + 1)]) / dy;
+    }
+#undef I2
+    if (o_ax) memcpy(o_ax, ax, N * 8);
+    if (o_ay) memcpy(o_ay, ay, N * 8);
+    if (o_Fx) memcpy(o_Fx, Fx, N * 8);
+    if (o_Fy) memcpy(o_Fy, Fy, N * 8);
+    free(ax); free(ay); free(Fx); free(Fy);
+}
+
+/* one step of RKIntegrator (method 0 RK2, 1 TVD2, 2 TVD3, 3 RK4) in place on a; returns the
+   number of stages.  dump (may be NULL): per stage six (qx,qy) planes -- the stage start after
+   its fill, the two face-value planes, F_x, F_y, k. */
+int orc_advmol_step(double *a, int nx, int ny, int ng, const int *bc, double dx, double dy, double u,
+                    double v, int scheme, int par, double alpha, int method, double dt, double *dump)
+{
+    static const int NS[4] = {2, 2, 3, 4};
+    static const double TA[4][4][4] = {
+        {{0.0, 0.0}, {0.5, 0.0}},
+        {{0.0, 0.0}, {1.0, 0.0}},
+        {{0.0, 0.0, 0.0}, {1.0, 0.0, 0.0}, {0.25, 0.25, 0.0}},
+        {{0.0, 0.0, 0.0, 0.0}, {0.5, 0.0, 0.0, 0.0}, {0.0, 0.5, 0.0, 0.0}, {0.0, 0.0, 1.0, 0.0}}};
+    static const double TB[4][4] = {{0.0, 1.0}, {0.5, 0.5}, {1. / 6., 1. / 6., 2. / 3.},
+                                    {1. / 6., 1. / 3., 1. / 3., 1. / 6.}};
+    const int qx = nx + 2 * ng, qy = ny + 2 * ng, ns = NS[method];
+    const size_t N = (size_t)qx * qy;
+    double *k[4], *y = zalloc(N);
+    for (int s = 0; s < ns; s++) k[s] = zalloc(N);
+    for (int s = 0; s < ns; s++) {
+        /* get_stage_start: stage 0 is the start itself (its fill lands in a); later stages
+           clone it, add on the interior -- every coefficient, zeros included --, then fill */
+        double *ys = a;
+        if (s > 0) {
+            ys = y;
+            memcpy(y, a, N * 8);
+            for (int m = 0; m < s; m++) {
+                const double c = dt * TA[method][s][m];
+                for (int i = ng; i < ng + nx; i++)
+                    for (int j = ng; j < ng + ny; j++) {
+                        const size_t o = (size_t)i * qy + j;
+                        y[o] += c * k[m][o];
+                    }
+            }
+        }
+        double *d = dump ? dump + (size_t)s * 6 * N : NULL;
+        orc_advmol_rhs(ys, nx, ny, ng, bc, dx, dy, u, v, scheme, par, alpha, d ? d + N : NULL,
+                       d ? d + 2 * N : NULL, d ? d + 3 * N : NULL, d ? d + 4 * N : NULL, k[s]);
+        if (d) {
+            memcpy(d, ys, N * 8);
+            memcpy(d + 5 * N, k[s], N * 8);
+        }
+    }
+    for (int s = 0; s < ns; s++) {                /* compute_final_update: the interior only */
+        const double c = dt * TB[method][s];
+        for (int i = ng; i < ng + nx; i++)
+            for (int j = ng; j < ng + ny; j++) {
+                const size_t o = (size_t)i * qy + j;
+                a[o] += c * k[s][o];
+            }
+    }
+    for (int s = 0; s < ns; s++) free(k[s]);
+    free(y);
+    return ns;
+}
+
+/* ================================================================== */
+/* advection_nonuniform: advective_fluxes.py:1-127, simulation.py:     */
+/* 18-26 (the shifts), :84-108 (evolve).  a, u, v are (qx,qy) planes   */
+/* whose ghost cells are filled here, each by its own boundary types   */
+/* (bc: xl,xr,yl,yr of a, of u, of v); a is advanced in place.  The    */
+/* shift planes are built as initialize() + fill_BC_all() leave them.  */
+/* dump (may be NULL): a_x, a_y, F_x, F_y.                             */
+/* ================================================================== */
+void orc_advnu_step(double *a, double *u, double *v, int nx, int ny, int ng, const int *bc, double dx,
+                    double dy, double dt, int limiter, double *dump)
+{
+    const int qx = nx + 2 * ng, qy = ny + 2 * ng;
+    const int ilo = ng, ihi = ng + nx - 1, jlo = ng, jhi = ng + ny - 1;
+    const size_t N = (size_t)qx * qy;
+    double *shx = zalloc(N), *shy = zalloc(N), *ldx = zalloc(N), *ldy = zalloc(N);
+    double *ax = zalloc(N), *ay = zalloc(N), *Fxt = zalloc(N), *Fyt = zalloc(N), *Fx = zalloc(N),
+           *Fy = zalloc(N);
+#define I2(i, j) ((size_t)(i) * qy + (j))
+    /* the offsets of the velocities as the problem set them (whole arrays), then every
+       variable's fill: an odd reflection negates the offset of its source cell */
+    for (size_t k = 0; k < N; k++) {
+        shx[k] = u[k] > 0 ? -1.0 : 0.0;
+        shy[k] = v[k] > 0 ? -1.0 : 0.0;
+    }
+    orc_fill_ghost(a, nx, ny, ng, 1, 0, bc);
+    orc_fill_ghost(u, nx, ny, ng, 1, 0, bc + 4);
+    orc_fill_ghost(v, nx, ny, ng, 1, 0, bc + 8);
+    orc_fill_ghost(shx, nx, ny, ng, 1, 0, bc + 4);
+    orc_fill_ghost(shy, nx, ny, ng, 1, 0, bc + 8);
+    orc_limit(a, 1, nx, ny, ng, 1, limiter, ldx);
+    orc_limit(a, 1, nx, ny, ng, 2, limiter, ldy);
+    for (int i = ilo - 1; i <= ihi + 1; i++)
+        for (int j = jlo - 1; j <= jhi + 1; j++) {
+            const double uu = u[I2(i, j)], vv = v[I2(i, j)];
+            const double cx = uu * dt / dx, cy = vv * dt / dy;
+            const int sx = (int)shx[I2(i, j)], sy = (int)shy[I2(i, j)];
+            if (uu < 0) ax[I2(i, j)] = a[I2(i + sx, j)] - 0.5 * (1.0 + cx) * ldx[I2(i + sx, j)];
+            else ax[I2(i, j)] = a[I2(i + sx, j)] + 0.5 * (1.0 - cx) * ldx[I2(i + sx, j)];
+            if (vv < 0) ay[I2(i, j)] = a[I2(i, j + sy)] - 0.5 * (1.0 + cy) * ldy[I2(i, j + sy)];
+            else ay[I2(i, j)] = a[I2(i, j + sy)] + 0.5 * (1.0 - cy) * ldy[I2(i, j + sy)];
+        }
+    for (size_t k = 0; k < N; k++) { Fxt[k] = u[k] * ax[k]; Fyt[k] = v[k] * ay[k]; }
+    const double dtdx2 = 0.5 * dt / dx, dtdy2 = 0.5 * dt / dy;
+    for (int i = ilo - 1; i <= ihi + 1; i++)
+        for (int j = jlo - 1; j <= jhi + 1; j++) {
+            const int sx = (int)shx[I2(i, j)], sy = (int)shy[I2(i, j)];
+            Fx[I2(i, j)] = u[I2(i, j)] * (ax[I2(i, j)] - dtdy2 * (Fyt[I2(i + sx, j + 1)] - Fyt[I2(i + sx, j)]));
+            Fy[I2(i, j)] = v[I2(i, j)] * (ay[I2(i, j)] - dtdx2 * (Fxt[I2(i + 1, j + sy)] - Fxt[I2(i, j + sy)]));
+        }
+    const double dtdx = dt / dx, dtdy = dt / dy;
+    for (int i = ilo; i <= ihi; i++)
+        for (int j = jlo; j <= jhi; j++)
+            a[I2(i, j)] = a[I2(i, j)] + dtdx * (Fx[I2(i, j)] - Fx[I2(i + 1, j)]) +
+                          dtdy * (Fy[I2(i, j)] - Fy[I2(i, j + 1)]);
+#undef I2
+    if (dump) {
+        memcpy(dump, ax, N * 8);
+        memcpy(dump + N, ay, N * 8);
+        memcpy(dump + 2 * N, Fx, N * 8);
+        memcpy(dump + 3 * N, Fy, N * 8);
+    }
+    free(shx); free(shy); free(ldx); free(ldy); free(ax); free(ay);
+    free(Fxt); free(Fyt); free(Fx); free(Fy);
 }

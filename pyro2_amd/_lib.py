@@ -194,6 +194,7 @@ _PROTOS = {
     "pyrohip_advrk_step": [_VP, C.c_int, C.POINTER(AdvRkParams), C.c_int, C.c_double],
     "pyrohip_advrk_evolve": [_VP, C.c_int, C.POINTER(AdvRkParams), C.c_int, C.POINTER(C.c_double), C.c_int],
     "pyrohip_advrk_stage_dump": [_VP, C.c_int, C.POINTER(AdvRkParams), C.c_int, C.c_double, C.c_int, _DP],
+    "pyrohip_test_square_as_pow": [_VP, _DP, C.c_size_t, _DP],
     "pyrohip_comp_dt": [_VP, C.POINTER(CompParams), C.c_double, _DP],
     "pyrohip_comp_evolve": [_VP, C.POINTER(CompParams), C.c_double, C.POINTER(DtPolicyC), C.c_int,
                             _IP, _DP],

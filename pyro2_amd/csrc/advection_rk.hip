@@ -554,4 +554,36 @@ extern "C" int pyrohip_advrk_stage_dump(pyrohip_state *s, int var, const pyrohip
         rc = advrk_stages(s, var, ap, tb, dt, s->d + (size_t)var * g.plane, s->work + geom_lead(g), stage, dump);
     return dump_planes_to_host(s, tmp, RK_DUMP_PLANES, rc, e, host);
 }
+
+// test hook: square_as_libm_pow (libm_pow2.h) of n host values, as the bit-faithful WENO kernels
+// evaluate it
+namespace {
+__global__ void k_test_square_as_pow(const double *__restrict__ x, size_t n, double *__restrict__ out)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = square_as_libm_pow(x[i]);
+}
+}  // namespace
+
+extern "C" int pyrohip_test_square_as_pow(pyrohip_ctx *c, const double *x, size_t n, double *out)
+{
+    PYRO_REQUIRE(c && (n == 0 || (x && out)), "NULL argument");
+    PYRO_REQUIRE(n <= ((size_t)1 << 28), "at most 2^28 values in one call");
+    if (n == 0) return 0;
+    DevBuf buf;
+    PYRO_TRY(buf.ensure(2 * n * sizeof(double)));
+    double *dx = (double *)buf.p, *dout = dx + n;
+    hipError_t e = hipMemcpyAsync(dx, x, n * sizeof(double), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        PYRO_LAUNCH(c, "k_test_square_as_pow", k_test_square_as_pow, dim3((unsigned)((n + 255) / 256)), dim3(256),
+                    0, dx, n, dout);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, dout, n * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+    const hipError_t e2 = hipStreamSynchronize(c->stream);
+    buf.release();
+    PYRO_CHECK_HIP(e);
+    PYRO_CHECK_HIP(e2);
+    return 0;
+}
 #endif

@@ -13,10 +13,20 @@
 // products and sums that build fuses is part of the result, so every fma() below is explicit and
 // the unit is compiled without contraction).  The tables are the published ones of that algorithm.
 //
-// Outside 1e-100 < |x| < 1e100, and for |x| = 1, the product stands in: below, the square is lost
-// against the 1e-16 it is added to; the library's other paths (results near 1, subnormal,
-// overflowing) are not repeated.  The recorded runs of tests/golden/advweno_*.npz contain such
-// arguments (the generator counts them and refuses to write a file without any).
+// Range: 1e-100 < |x| < 1.3e154, |x| != 1.  The library leaves its main path where
+// |2 log|x|| >= 512 (|x| above about 1.5e111): there it takes the factor 2^1009 out of the
+// exponential's scale before the last fused multiply-add and multiplies it back in, both exact as
+// long as the square is finite, so the operations below give its bits up to the last binade before
+// overflow.  1.3e154 keeps the scale itself finite (it is for |x| < 2^(512 - 1/512), 1.3390e154).
+// tests/test_advmol_oracle.py holds this function to equality with the host's pow(x, 2.0) on two
+// million arguments over the whole range, both signs.
+//
+// Outside that range, and for |x| = 1, the product stands in: below 1e-100 the square is lost
+// against the 1e-16 it is added to (the library's path for subnormal results is not repeated);
+// at 1.3e154 and above the square is within 1.07 of overflowing or has overflowed (the product and
+// the library agree on inf; for the finite squares between, they differ in about one argument of a
+// thousand, as everywhere).  The recorded runs of tests/golden/advweno_*.npz contain arguments
+// below the range (the generator counts them and refuses to write a file without any).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -222,7 +232,7 @@ static __device__ const unsigned long long kPowExpTab[256] = {   // tail bits, s
 __device__ __forceinline__ double square_as_libm_pow(double x)
 {
     const double ax = fabs(x);      // y = 2 is an even integer: the library takes |x|
-    if (!(ax > 1e-100 && ax < 1e100) || ax == 1.0) return x * x;
+    if (!(ax > 1e-100 && ax < 1.3e154) || ax == 1.0) return x * x;
     const double Ln2hi = 0x1.62e42fefa3800p-1, Ln2lo = 0x1.ef35793c76730p-45;
     const double A0 = -0x1.0000000000000p-1, A1 = -0x1.5555555555560p-1, A2 = 0x1.0000000000006p-1,
                  A3 = 0x1.999999959554ep-1, A4 = -0x1.555555529a47ap-1, A5 = -0x1.2495b9b4845e9p+0,

@@ -110,6 +110,15 @@ class Context:
             out[name] = (int(n), float(ms))
         return out
 
+    def test_square_as_pow(self, x):
+        """csrc/libm_pow2.h's square_as_libm_pow over an array, evaluated on the device (test
+        hook)"""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        out = np.empty_like(x)
+        with self.lock:
+            check(self._l.pyrohip_test_square_as_pow(self.h, dptr(x), x.size, dptr(out)))
+        return out
+
     # ---- multi-GPU plumbing (RCCL) ------------------------------------
     @staticmethod
     def comm_unique_id():

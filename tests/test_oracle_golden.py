@@ -934,3 +934,127 @@ def test_oracle_fv4_rhs_assert():
         V = U.copy()
         V[i, j, n] = v
         assert orc.fv4_rhs(V, P)[0] == rc, (i, j, n)
+
+
+# ------------------------------------------- method-of-lines and nonuniform advection
+ADVMOL_FILES = {"advrk_stages": ("start", "a_x", "a_y", "F_x", "F_y", "k"),
+                "advweno_stages": ("start", "fpr_x", "fpr_y", "F_x", "F_y", "k")}
+
+
+def advmol_case(g, k):
+    """a recorded evolve() of advrk_stages.npz / advweno_stages.npz as the oracle's arguments"""
+    pre = f"c{k}_"
+    m = g[pre + "meta"]
+    c = dict(nx=int(m[0]), ny=int(m[1]), ng=int(m[2]), par=int(m[3]), scheme=int(m[4]), dx=float(m[5]),
+             dy=float(m[6]), u=float(m[7]), v=float(m[8]), ns=int(m[10]), method=str(g[pre + "method"]),
+             bc=[str(b) for b in g[pre + "bc"]], dt=float(g[pre + "dt"]))
+    c["alpha"] = float(m[11]) if c["scheme"] == 5 else 0.0
+    return c
+
+
+def advmol_oracle_step(c, a, stages=False):
+    return orc.advmol_step(a, c["nx"], c["ny"], c["ng"], c["bc"], c["dx"], c["dy"], c["u"], c["v"],
+                           c["scheme"], c["par"], c["method"], c["dt"], alpha=c["alpha"], stages=stages)
+
+
+def advmol_slices(c):
+    """where the device tests compare the planes of a stage: the faces the update reads (the
+    fourth-order fluxes read face averages one face sideways)"""
+    ng, nx, ny = c["ng"], c["nx"], c["ny"]
+    t = 1 if c["scheme"] == 4 else 0
+    return {"start": np.s_[:, :], "a_x": np.s_[ng:ng + nx + 1, ng - t:ng + ny + t],
+            "a_y": np.s_[ng - t:ng + nx + t, ng:ng + ny + 1], "F_x": np.s_[ng:ng + nx + 1, ng:ng + ny],
+            "F_y": np.s_[ng:ng + nx, ng:ng + ny + 1], "k": np.s_[ng:ng + nx, ng:ng + ny]}
+
+
+@pytest.mark.parametrize("k", range(14))
+@pytest.mark.parametrize("name", sorted(ADVMOL_FILES))
+def test_oracle_advmol_stages(golden, name, k):
+    """orc_advmol_step against one recorded evolve() of advection_rk / advection_fv4 /
+    advection_weno: every stage's start with its ghost frame, face values, fluxes and k, and the
+    new level with its ghost frame, bit for bit, from a plane whose ghost cells hold junk"""
+    g = golden(name)
+    assert int(g["ncases"]) == 14
+    c = advmol_case(g, k)
+    a = g[f"c{k}_Uin"].copy()
+    st = advmol_oracle_step(c, a, stages=True)
+    assert len(st) == c["ns"]
+    sl = advmol_slices(c)
+    for s in range(c["ns"]):
+        for key, okey in zip(ADVMOL_FILES[name], orc.ADVMOL_PLANES):
+            assert np.array_equal(st[s][okey][sl[okey]], g[f"c{k}_s{s}_{key}"][sl[okey]]), (s, key)
+    assert np.array_equal(a, g[f"c{k}_new"])
+
+
+def _smooth_to_t1(scheme, par, cfl=0.8, nx=32, ng=4, tmax=1.0):
+    """inputs.smooth to t = 1 as the driver runs it: the Gaussian of advection/problems/smooth.py
+    on the cell centres of mesh/patch.py:124-137 (advection_fv4: preevolve turns them into
+    averages, fv.py:32-39), the time step of advection_rk/simulation.py:30-46 under
+    simulation_null.compute_timestep"""
+    dx = (1.0 - 0.0) / nx
+    q = nx + 2 * ng
+    x = 0.5 * (((np.arange(q) - ng) * dx + 0.0) + ((np.arange(q) + 1.0 - ng) * dx + 0.0))
+    X, Y = np.meshgrid(x, x, indexing="ij")
+    a = np.ascontiguousarray(1.0 + np.exp(-60.0 * ((X - 0.5)**2 + (Y - 0.5)**2)))
+    bc = ["periodic"] * 4
+    u = v = 1.0
+    if scheme == 4:
+        orc.fill_ghost(a, nx, nx, ng, bc)
+        c = a[ng:-ng, ng:-ng]
+        lap = (a[ng - 1:-ng - 1, ng:-ng] - 2 * c + a[ng + 1:q - ng + 1, ng:-ng]) / dx**2 + \
+              (a[ng:-ng, ng - 1:-ng - 1] - 2 * c + a[ng:-ng, ng + 1:q - ng + 1]) / dx**2
+        a[ng:-ng, ng:-ng] = c + dx**2 * lap / 24.0
+    t, n = 0.0, 0
+    while t < tmax:
+        dt = cfl / (max(abs(u), 1e-12) / dx + max(abs(v), 1e-12) / dx)
+        if t + dt > tmax:
+            dt = tmax - t
+        orc.advmol_step(a, nx, nx, ng, bc, dx, dx, u, v, scheme, par, "RK4", dt, alpha=float(np.sqrt(u**2 + v**2)))
+        t += dt
+        n += 1
+    return a[ng:-ng, ng:-ng], n, t
+
+
+@pytest.mark.parametrize("scheme,par,name,key", [(2, 2, "advrk_regress", "s2_"), (4, 2, "advrk_regress", "s4_"),
+                                                 (5, 2, "advweno_regress", "o2_"), (5, 3, "advweno_regress", "o3_")])
+def test_oracle_advmol_regression_smooth(golden, scheme, par, name, key):
+    """the 81 steps of the reference's regression runs (pyro/test.py: advection_rk,
+    advection_fv4, advection_weno `smooth`), bit for bit"""
+    g = golden(name)
+    a, n, t = _smooth_to_t1(scheme, par)
+    nref, tref = (g[key + "meta"][:2]) if scheme == 5 else (g[key + "n"], g[key + "t"])
+    assert (n, t) == (81, 1.0) and (int(nref), float(tref)) == (81, 1.0)
+    assert np.array_equal(a, g[key + "density"])
+
+
+@pytest.mark.parametrize("k", range(7))
+def test_oracle_advnu_stages(golden, k):
+    """orc_advnu_step against one recorded fill_BC_all + evolve() of advection_nonuniform: the
+    whole scratch planes a_x, a_y, F_x, F_y and the new density with its ghost frame, bit for
+    bit, from planes whose ghost cells hold junk; the velocity planes are left alone"""
+    g = golden("advnu_stages")
+    assert int(g["ncases"]) == 7
+    pre = f"c{k}_"
+    m = g[pre + "meta"]
+    nx, ny, ng, lim = (int(x) for x in m[:4])
+    U = g[pre + "Uin"]                       # x-velocity, y-velocity, x-shift, y-shift, density
+    bc = [[str(b) for b in row] for row in g[pre + "bc"]]
+    a, u, v = U[4].copy(), U[0].copy(), U[1].copy()
+    d = orc.advnu_step(a, u, v, nx, ny, ng, [bc[4], bc[0], bc[1]], float(m[4]), float(m[5]),
+                       float(g[pre + "dt"]), lim, stages=True)
+    for n, key in enumerate(("a_x", "a_y", "F_x", "F_y")):
+        assert np.array_equal(d[n], g[pre + key]), key
+    assert np.array_equal(a, g[pre + "new"])
+    assert np.array_equal(u, U[0]) and np.array_equal(v, U[1])
+
+
+def test_oracle_pow2_is_the_library_call():
+    """orc_pow2 is pow(x, 2.0) of this host's C library (math.pow is the same call), not a
+    product the compiler folded it into"""
+    import math
+    rng = np.random.default_rng(5)
+    x = np.concatenate([10.0 ** rng.uniform(-100, 100, 200000) * rng.choice([-1.0, 1.0], 200000),
+                        [0.0, -0.0, 1.0, -1.0, 1e150, 1e-200]])
+    got = orc.pow2(x)
+    assert np.array_equal(got, np.array([math.pow(float(t), 2.0) for t in x]))
+    assert np.count_nonzero(got != x * x) > 0
