@@ -366,6 +366,15 @@ typedef struct {
        step's dt from the CFL minima of the previous launch by the driver's policy
        (simulation_null.py:222-244) -- bit-identical, measured no faster */
     int step_launches;
+    /* compressible.well_balanced of compressible_rk (compressible_rk/fluxes.py:100-108 and
+       :139-148, mesh/reconstruction.py:21-53): 1 = the y slope of the pressure is the limit2
+       slope of the pressure less its hydrostatic part (not flattened) and the y face pressures
+       get that part back, so that a discrete hydrostatic equilibrium stays at rest.  Carried by
+       pyrohip_comp_rk_rhs on the staged kernels only (whatever kernel_set says), with
+       limiter == 1; every other compressible entry point refuses a block that sets it.
+       0 = the plain reconstruction.  The LAST member: a zero-initialised block of an older
+       caller keeps its meaning. */
+    int well_balanced;
 } pyrohip_comp_params;
 
 /* method_compute_timestep (compressible/simulation.py:267-288 +

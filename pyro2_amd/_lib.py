@@ -85,7 +85,7 @@ class CompParams(C.Structure):
                 ("do_sponge", C.c_int), ("sponge_rho_begin", C.c_double),
                 ("sponge_rho_full", C.c_double), ("sponge_timescale", C.c_double),
                 ("heat_rate", C.c_double), ("march_rows", C.c_int), ("fuse_fill", C.c_int),
-                ("step_launches", C.c_int)]
+                ("step_launches", C.c_int), ("well_balanced", C.c_int)]
 
 
 class DtPolicyC(C.Structure):

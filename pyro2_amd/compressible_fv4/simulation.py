@@ -37,6 +37,8 @@ class Simulation(RKSimulation):
         from .. import decomp
         if int(self._rp_opt("gpu.decompose", -1)) == 1 or decomp.active_decomposition(self.rp) is not None:
             msg.fail("ERROR: compressible_fv4 / compressible_sdc run on a single domain (one GPU)")
+        if self._rp_opt("compressible.well_balanced", 0):     # (the reference's solver has no such option)
+            msg.fail("ERROR: compressible.well_balanced is an option of compressible_rk only")
         super().initialize(extra_vars=extra_vars, ng=ng)
         if self._host_source():
             msg.fail("ERROR: compressible_fv4 carries gravity, the sponge and heating profiles "

@@ -2,8 +2,9 @@
 pyro/compressible_rk/simulation.py:8-104: the compressible solver's state,
 problems and boundaries with a method-of-lines update.  Per stage: ghost fill,
 pyrohip_comp_rk_rhs (density floor, primitives, flattening, limited slopes,
-face states, Riemann fluxes, artificial viscosity, flux divergence, gravity and
-sponge sources); stage starts and the final update are
+face states -- with compressible.well_balanced the y pressure slope and face pressures
+of fluxes.py:100-108, :139-148 --, Riemann fluxes, artificial viscosity, flux divergence,
+gravity and sponge sources); stage starts and the final update are
 pyrohip_state_lincomb launches (pyro2_amd/mesh/integration.py)."""
 from ..compressible.simulation import Simulation as CompressibleSimulation
 from ..mesh import integration
@@ -15,10 +16,19 @@ class Simulation(CompressibleSimulation):
     decomposable = False   # (the stages would each need a halo exchange: single domain)
 
     def initialize(self, *, extra_vars=None, ng=4):
-        if self._rp_opt("compressible.well_balanced", 0):
-            msg.fail("ERROR: compressible.well_balanced is not carried by the device path")
+        # reconstruction.py:24-25 (the reference stops there, in its first right-hand side)
+        if self._rp_opt("compressible.well_balanced", 0) and int(self._rp_opt("compressible.limiter", 2)) != 1:
+            msg.fail("well-balanced only works for limiter == 1")
         super().initialize(extra_vars=extra_vars, ng=ng)
         self._rk_scratch = None
+
+    def _params(self):
+        """the compressible parameters and compressible.well_balanced (fluxes.py:103-108, :139-148):
+        with it every right-hand side is the staged kernels' and the step goes stage by stage
+        (pyrohip_comp_rk_can_fuse answers no)"""
+        P = super()._params()
+        P.well_balanced = int(bool(self._rp_opt("compressible.well_balanced", 0)))
+        return P
 
     def substep(self, st, kstate, slot):
         """k of the device state `st` into slot `slot` of `kstate`"""

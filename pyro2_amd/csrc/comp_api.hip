@@ -353,6 +353,8 @@ int pyrohip_comp_evolve(pyrohip_state *s, const pyrohip_comp_params *p, double c
     PYRO_TRY(check_comp(s, p));
     PYRO_REQUIRE(pol && steps_done, "NULL argument");
     PYRO_REQUIRE(max_steps >= 1, "max_steps must be positive");
+    PYRO_REQUIRE(!p->well_balanced, "well_balanced is carried by pyrohip_comp_rk_rhs only (compressible_rk, "
+                                    "stage by stage on the staged kernels)");
     PYRO_REQUIRE(p->kernel_set != 0, "the staged kernel set steps from the host (kernel_set 0)");
     PYRO_REQUIRE(p->riemann >= 0 && p->riemann <= 2, "riemann must be 0 (HLLC), 1 (CGF) or 2 (HLLC_lm)");
     // (a SphericalPolar grid steps on the device where its step is one launch: comp_can_fuse_sph)
@@ -634,6 +636,8 @@ int pyrohip_comp_step(pyrohip_state *s, const pyrohip_comp_params *p, double dt)
 {
     PYRO_TRY(check_comp(s, p));
     PYRO_REQUIRE(dt > 0.0, "dt must be positive");
+    PYRO_REQUIRE(!p->well_balanced, "well_balanced is carried by pyrohip_comp_rk_rhs only (compressible_rk, "
+                                    "stage by stage on the staged kernels)");
     PYRO_REQUIRE(p->kernel_set >= -1 && p->kernel_set <= 2, "kernel_set must be -1 (automatic), 0, 1 or 2");
     PYRO_REQUIRE(p->riemann >= 0 && p->riemann <= 2, "riemann must be 0 (HLLC), 1 (CGF) or 2 (HLLC_lm)");
     int rc;
@@ -735,13 +739,13 @@ int pyrohip_comp_rk_dt(pyrohip_state *s, const pyrohip_comp_params *p, double cf
 // The whole Runge-Kutta step in nstages launches of the row-marching kernel (comp_wave.hip:
 // comp_rk_step_wave)?  Single Cartesian domain, outflow / reflect / periodic sides (the same kind
 // for the four variables: the stage states' ghost cells are read through index maps), no sponge,
-// no heating profile, no host-evaluated source; kernel_set 2 or the library's choice from
-// 2048^2 cells on.
+// no heating profile, no host-evaluated source, no well-balanced reconstruction (the row-marching
+// kernel does not carry it); kernel_set 2 or the library's choice from 2048^2 cells on.
 static bool comp_rk_can_fuse(const pyrohip_state *y, const pyrohip_comp_params *p, const pyrohip_state *k,
                              int nstages)
 {
     if (y->nvar != 4 || y->sph || y->nb_set || y->user_bc || y->ramp_bc || y->heat || y->ext_old ||
-        p->do_sponge || y->g.ng < 4 || nstages < 2 || nstages > 4 || !k || k->nvar < 4 * nstages)
+        p->do_sponge || p->well_balanced || y->g.ng < 4 || nstages < 2 || nstages > 4 || !k || k->nvar < 4 * nstages)
         return false;
     if (!(p->kernel_set == 2 || (p->kernel_set < 0 && wave_kernel_pays(y->g)))) return false;
     for (int sd = 0; sd < 4; sd++) {
@@ -786,6 +790,8 @@ int pyrohip_comp_rk_step(pyrohip_state *y, const pyrohip_comp_params *p, pyrohip
 {
     PYRO_TRY(check_rk(y, p, k, nstages, a, b));
     PYRO_REQUIRE(dt > 0.0, "dt must be positive");
+    PYRO_REQUIRE(!p->well_balanced, "well_balanced is carried by pyrohip_comp_rk_rhs only (compressible_rk, "
+                                    "stage by stage on the staged kernels)");
     PYRO_REQUIRE(comp_rk_can_fuse(y, p, k, nstages),
                  "pyrohip_comp_rk_step: single Cartesian domain, outflow / reflect / periodic sides, no sponge / "
                  "heating / host source, kernel_set 2 or a grid of >= 2048^2 cells (pyrohip_comp_rk_can_fuse; "
@@ -805,6 +811,8 @@ int pyrohip_comp_rk_evolve(pyrohip_state *y, const pyrohip_comp_params *p, pyroh
 {
     PYRO_TRY(check_rk(y, p, k, nstages, a, b));
     PYRO_REQUIRE(pol && steps_done && max_steps >= 1, "NULL argument / max_steps must be positive");
+    PYRO_REQUIRE(!p->well_balanced, "well_balanced is carried by pyrohip_comp_rk_rhs only (compressible_rk, "
+                                    "stage by stage on the staged kernels)");
     PYRO_REQUIRE(comp_rk_can_fuse(y, p, k, nstages),
                  "device-side stepping: compressible_rk needs the conditions of pyrohip_comp_rk_step "
                  "(pyrohip_comp_rk_can_fuse)");
@@ -907,9 +915,15 @@ int pyrohip_comp_rk_rhs(pyrohip_state *y, const pyrohip_comp_params *p, pyrohip_
     if (p->do_sponge)
         PYRO_REQUIRE(p->sponge_rho_begin > p->sponge_rho_full,
                      "sponge_rho_begin must exceed sponge_rho_full (simulation.py:172)");
+    if (p->well_balanced) {
+        // reconstruction.py:24-25; no geometry terms in compressible_rk/fluxes.py anyway
+        PYRO_REQUIRE(p->limiter == 1, "well_balanced only works for limiter == 1");
+        PYRO_REQUIRE(!y->sph && y->nvar == 4, "well_balanced: a 4-variable state on a Cartesian grid");
+    }
     // kernel_set 2, or the library's choice from 2048^2 cells on: one launch of the row-marching
-    // kernel's method-of-lines instance; the staged kernels otherwise (small grids, the sponge)
-    const bool wave = !p->do_sponge && y->nvar == 4 &&
+    // kernel's method-of-lines instance; the staged kernels otherwise (small grids, the sponge, the
+    // well-balanced reconstruction)
+    const bool wave = !p->do_sponge && !p->well_balanced && y->nvar == 4 &&
                       (p->kernel_set == 2 || (p->kernel_set < 0 && wave_kernel_pays(y->g)));
     if (wave)
         return p->fast_math ? fastm::comp_rk_rhs_wave(y, p, k, slot) : exact::comp_rk_rhs_wave(y, p, k, slot);
@@ -921,6 +935,8 @@ int pyrohip_comp_fv4_rhs(pyrohip_state *y, const pyrohip_comp_params *p, pyrohip
 {
     PYRO_TRY(check_comp(y, p));
     PYRO_REQUIRE(y->g.ng == 4, "compressible_fv4 needs ng = 4 (the reference's grid)");
+    PYRO_REQUIRE(!p->well_balanced, "well_balanced is carried by pyrohip_comp_rk_rhs only (compressible_rk, "
+                                    "stage by stage on the staged kernels)");
     PYRO_REQUIRE(!y->sph, "compressible_fv4 has no SphericalPolar geometry terms");
     PYRO_REQUIRE(k && k->ctx == y->ctx, "k state missing or on another context");
     PYRO_REQUIRE(k != y && k->d != y->d,

@@ -995,6 +995,12 @@ int comp_step_sph(pyrohip_state *s, const pyrohip_comp_params *p, double dt)
 // artificial viscosity, then the flux divergence.
 // ===========================================================================
 // R1: face states of the cells of R(1) (the faces of the interior need no more)
+// WB: compressible.well_balanced (fluxes.py:100-108, :139-148 with reconstruction.py:21-53), y only:
+// the limiter sees the pressure less its hydrostatic part, p1 = p - p0 with p0 the discrete
+// balance through the cell's own p (p1 is 0 in the cell itself), the slope is NOT flattened
+// (fluxes.py:107 overwrites xi * limit), and the faces get p0 back with the cell's own density.
+// Reads p and rho at j +- 1 of R(1): inside the ghost cells the limiter reads anyway.
+template <bool WB>
 __global__ __launch_bounds__(256) void k_rk_states(const double *__restrict__ W_,
                                                    double *__restrict__ Wout, Geom g, CP P,
                                                    int gx, int gy)
@@ -1025,8 +1031,24 @@ __global__ __launch_bounds__(256) void k_rk_states(const double *__restrict__ W_
     };
     store_cons(Wout + (size_t)W_XM * pl, pl, k, face(dqx, -1.0));
     store_cons(Wout + (size_t)W_XP * pl, pl, k, face(dqx, 1.0));
-    store_cons(Wout + (size_t)W_YM * pl, pl, k, face(dqy, -1.0));
-    store_cons(Wout + (size_t)W_YP * pl, pl, k, face(dqy, 1.0));
+    if (WB) {
+        // the reference's operation order: 0.5*dy*(rho + rho')*grav is ((0.5*dy)*(rho + rho'))*grav
+        const double *rho = Q, *pr = Q + 3 * pl;
+        const double hdy = 0.5 * P.dy;
+        const double p1p = pr[k + 1] - (pr[k] + (hdy * (rho[k] + rho[k + 1])) * P.grav);
+        const double p1m = pr[k - 1] - (pr[k] - (hdy * (rho[k] + rho[k - 1])) * P.grav);
+        const double ldp = limit2(p1m, 0.0, p1p);    // dl = p1p - 0.0, dr = 0.0 - p1m
+        const double p0h = (hdy * q0[0]) * P.grav;
+        store_cons(Wout + (size_t)W_YM * pl, pl, k,
+                   prim_to_cons(Prim{q0[0] - 0.5 * dqy[0], q0[1] - 0.5 * dqy[1], q0[2] - 0.5 * dqy[2],
+                                     (q0[3] - p0h) - 0.5 * ldp}, P.gamma));
+        store_cons(Wout + (size_t)W_YP * pl, pl, k,
+                   prim_to_cons(Prim{q0[0] + 0.5 * dqy[0], q0[1] + 0.5 * dqy[1], q0[2] + 0.5 * dqy[2],
+                                     (q0[3] + p0h) + 0.5 * ldp}, P.gamma));
+    } else {
+        store_cons(Wout + (size_t)W_YM * pl, pl, k, face(dqy, -1.0));
+        store_cons(Wout + (size_t)W_YP * pl, pl, k, face(dqy, 1.0));
+    }
 }
 
 // R2: Riemann problems (fluxes.py:145-160) + artificial viscosity (:162-168,
@@ -1204,7 +1226,12 @@ int comp_rk_rhs(pyrohip_state *s, const pyrohip_comp_params *p, pyrohip_state *k
     const dim3 gridR1(xcd_grid_1d(gx, gy));
     PYRO_LAUNCH(c, "k_xi", k_xi, gridR1, block, 0, (const double *)W, W + (size_t)W_XI * g.plane, g,
                 P, gx, gy);
-    PYRO_LAUNCH(c, "k_rk_states", k_rk_states, gridR1, block, 0, (const double *)W, W, g, P, gx, gy);
+    if (p->well_balanced)
+        PYRO_LAUNCH(c, "k_rk_states_wb", k_rk_states<true>, gridR1, block, 0, (const double *)W, W, g, P, gx,
+                    gy);
+    else
+        PYRO_LAUNCH(c, "k_rk_states", k_rk_states<false>, gridR1, block, 0, (const double *)W, W, g, P, gx,
+                    gy);
     gx = (g.ny + 1 + 255) / 256; gy = g.nx + 1;
     PYRO_LAUNCH(c, "k_rk_flux", k_rk_flux, dim3(xcd_grid_1d(gx, gy)), block, 0, (const double *)U,
                 (const double *)W, W, g, P, gx, gy);
