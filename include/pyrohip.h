@@ -786,6 +786,62 @@ int pyrohip_lm_proj_update(pyrohip_state *s, pyrohip_mg *mg, double dx, double d
    21-24 u_xint v_xint u_yint v_yint -> host (qx, qy)                         */
 int pyrohip_lm_stage_dump(pyrohip_state *s, int which, double *host);
 
+/* ---- tracer particles (pyro/particles/particles.py:11-364) ---------------- */
+/* A set of massless tracers that lives on the device beside a state.  The
+   capacity is fixed at creation (n of pyrohip_particles_create, at most
+   PYROHIP_PARTICLES_MAX: one workgroup scans the per-workgroup survivor counts);
+   the live count can only shrink (outflow sides drop particles) and stays in
+   device memory.  Host arrays are (n, 2) row-major, x then y, like
+   Particles.get_positions().                                                   */
+typedef struct pyrohip_particles pyrohip_particles;
+#define PYROHIP_PARTICLES_MAX 65536
+enum {
+    PYROHIP_PART_DROP = 0,     /* "outflow", "neumann": the particle leaves     */
+    PYROHIP_PART_PERIODIC = 1, /* "periodic": (hi + c) - lo / (lo + c) - hi      */
+    PYROHIP_PART_MIRROR = 2    /* "reflect-even", "reflect-odd", "dirichlet":    */
+                               /* 2 lo - c / 2 hi - c                            */
+};
+enum {
+    PYROHIP_PART_VEL_PLANES = 0, /* u = plane idx[0], v = plane idx[1]           */
+    PYROHIP_PART_VEL_RATIO = 1   /* u = plane idx[0] / plane idx[2],             */
+                                 /* v = plane idx[1] / plane idx[2] (IEEE        */
+                                 /* division at each of the four corners)        */
+};
+typedef struct pyrohip_particle_params {
+    size_t size;               /* sizeof(pyrohip_particle_params) of the caller */
+    double xmin, xmax, ymin, ymax, dx, dy;   /* Grid2d of the state             */
+    int bc[4];                 /* PYROHIP_PART_*: xlb, xrb, ylb, yrb             */
+    int vel_mode;              /* PYROHIP_PART_VEL_*                             */
+    int idx[3];                /* planes of the state (idx[2]: RATIO only)       */
+} pyrohip_particle_params;
+/* pos, init: (n, 2); init NULL = pos.  Velocities start as 0. */
+int pyrohip_particles_create(pyrohip_ctx *ctx, int n, const double *pos, const double *init,
+                             pyrohip_particles **out);
+/* Releases the set.  Valid after pyrohip_shutdown of its context too (shutdown
+   releases the device memory of every set still alive, the handle stays valid
+   for this call alone).                                                        */
+int pyrohip_particles_destroy(pyrohip_particles *p);
+/* replace the whole set: n <= capacity; init / vel NULL = keep pos / 0 */
+int pyrohip_particles_upload(pyrohip_particles *p, int n, const double *pos, const double *init,
+                             const double *vel);
+/* live count and arrays (room for `capacity` particles each); any pointer may be NULL */
+int pyrohip_particles_download(pyrohip_particles *p, int *n, double *pos, double *init,
+                               double *vel);
+int pyrohip_particles_count(pyrohip_particles *p, int *n);
+/* Particles.update_particles + enforce_particle_boundaries (particles.py:213-327)
+   over dt, operation by operation (never contracted, whatever gpu.fast_math is):
+   bilinear interpolation of the velocity at the old position (:62-86, index rule
+   int(x_idx) with the fraction x_idx % 1), half step, interpolation there, full
+   step from the old position, then the sides xlb, xrb, ylb, yrb in this order;
+   survivors are stored in REVERSED order (the reference rebuilds its dict with
+   popitem()).  The velocity is read from the planes of `s` as they are in device
+   memory, ghost cells included; no ghost fill happens here.  Three launches; what
+   comes back to the host is one error word.  A particle whose 2 x 2 stencil does
+   not lie inside the (qx, qy) array (NaN / infinite positions included) is never
+   read for: the call returns PYROHIP_ERR_STATE and the set is the one before it. */
+int pyrohip_particles_advance(pyrohip_particles *p, pyrohip_state *s,
+                              const pyrohip_particle_params *params, double dt);
+
 /* ---- multi-GPU: x-slab decomposition, one process per GPU, RCCL -------- */
 #define PYROHIP_UNIQUE_ID_BYTES 128
 int pyrohip_comm_unique_id(char *out_id /* PYROHIP_UNIQUE_ID_BYTES */);

@@ -95,6 +95,22 @@ class DtPolicyC(C.Structure):
                 ("t", C.c_double), ("dt_old", C.c_double), ("n", C.c_longlong)]
 
 
+# pyrohip_particle_params: boundary kinds and velocity modes (include/pyrohip.h)
+PART_DROP, PART_PERIODIC, PART_MIRROR = range(3)
+PART_BC_CODE = {"outflow": PART_DROP, "neumann": PART_DROP, "periodic": PART_PERIODIC,
+                "reflect-even": PART_MIRROR, "reflect-odd": PART_MIRROR, "dirichlet": PART_MIRROR}
+PART_VEL_PLANES, PART_VEL_RATIO = range(2)
+PARTICLES_MAX = 65536
+
+
+class ParticleParams(C.Structure):
+    """pyrohip_particle_params (include/pyrohip.h); `size` first"""
+    _fields_ = [("size", C.c_size_t),
+                ("xmin", C.c_double), ("xmax", C.c_double), ("ymin", C.c_double), ("ymax", C.c_double),
+                ("dx", C.c_double), ("dy", C.c_double),
+                ("bc", C.c_int * 4), ("vel_mode", C.c_int), ("idx", C.c_int * 3)]
+
+
 _DP = C.POINTER(C.c_double)
 _IP = C.POINTER(C.c_int)
 _VP = C.c_void_p
@@ -249,6 +265,12 @@ _PROTOS = {
     "pyrohip_mg_rows_kmax": [_VP, C.c_int, _IP],
     "pyrohip_mg_diag_rows": [_VP, C.c_int, C.c_int, _DP],
     "pyrohip_mg_save_old": [_VP],
+    "pyrohip_particles_create": [_VP, C.c_int, _DP, _DP, C.POINTER(_VP)],
+    "pyrohip_particles_destroy": [_VP],
+    "pyrohip_particles_upload": [_VP, C.c_int, _DP, _DP, _DP],
+    "pyrohip_particles_download": [_VP, _IP, _DP, _DP, _DP],
+    "pyrohip_particles_count": [_VP, _IP],
+    "pyrohip_particles_advance": [_VP, _VP, C.POINTER(ParticleParams), C.c_double],
 }
 
 EXPORTS = sorted(list(_PROTOS) + ["pyrohip_last_error", "pyrohip_backend"])

@@ -70,6 +70,8 @@ UNITS = [
     ("swe.hip", "swe", ["-ffp-contract=off", "-DPYRO_FAST=0"]),
     ("swe.hip", "swe_fast", ["-ffp-contract=fast", "-DPYRO_FAST=1", "-fno-honor-nans"]),
     ("comm.hip", "comm", ["-ffp-contract=off"]),
+    # tracer particles: ONE build, never contracted (positions are bit-identical whatever gpu.fast_math says)
+    ("particles.hip", "particles", ["-ffp-contract=off"]),
 ]
 
 

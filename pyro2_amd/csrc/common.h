@@ -103,6 +103,24 @@ struct pyrohip_ctx {
     // rows they have left (comp_wave.hip: wave_prio_feedback); [SIMD of the chip][wavefront slot], tagged per launch
     pyro::DevBuf prio_board;
     unsigned launch_seq = 0;
+    // tracer particle sets alive on this context (ctx.hip: particles_alloc / particles_release;
+    // pyrohip_shutdown releases the device memory of those still here)
+    std::vector<pyrohip_particles *> psets;
+};
+
+// A tracer particle set (particles.hip).  ONE device allocation, made and freed in ctx.hip:
+//   doubles  2 buffers x {pos, init, vel} x (cap, 2)      the live set is buffer `cur`
+//            candidates {pos, vel} x (cap, 2)             of the advance in flight, by old slot
+//   ints     keep[cap], wg_count[nwg], wg_off[nwg], count[2], err
+// count[b] is the live count of buffer b; an advance reads count[cur] and writes count[cur ^ 1].
+struct pyrohip_particles {
+    pyrohip_ctx *ctx = nullptr;   // nullptr: the context was shut down, the device memory is gone
+    int cap = 0, nwg = 0;
+    int cur = 0;
+    void *mem = nullptr;
+    double *buf[2] = {nullptr, nullptr};   // pos at +0, init at +2 cap, vel at +4 cap
+    double *cand = nullptr;                // pos at +0, vel at +2 cap
+    int *keep = nullptr, *wg_count = nullptr, *wg_off = nullptr, *count = nullptr, *err = nullptr;
 };
 
 namespace pyro {
@@ -396,6 +414,11 @@ int evolve_begin(pyrohip_state *s, const pyrohip_dt_policy *pol, double cfl, dou
 // enqueue the copy of one plane (laid out like the state's) into a (qx, qy) host array; the
 // caller synchronises
 int plane_to_host(pyrohip_state *s, const double *dev_plane, double *host);
+// ---- a particle set's device memory: allocated and released here only ----
+// the handle with its one allocation for `cap` particles, registered with the context
+int particles_alloc(pyrohip_ctx *c, int cap, pyrohip_particles **out);
+// frees the device memory (if the context still lives), unregisters and deletes the handle
+int particles_release(pyrohip_particles *p);
 
 // boundary types a kernel can apply as an index map while it loads (stencil.h: bc_map)
 inline bool bc_is_index_map(int b, bool allow_odd)

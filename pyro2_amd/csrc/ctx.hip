@@ -352,6 +352,60 @@ int plane_to_host(pyrohip_state *s, const double *dev_plane, double *host)
     return 0;
 }
 
+// ---------------------------------------------------------------------------
+// a tracer particle set's device memory (common.h)
+// ---------------------------------------------------------------------------
+int particles_alloc(pyrohip_ctx *c, int cap, pyrohip_particles **out)
+{
+    const int nwg = (cap + 255) / 256;
+    const size_t nd = (size_t)16 * cap, ni = (size_t)cap + 2 * (size_t)nwg + 3;
+    pyrohip_particles *p = new pyrohip_particles();
+    const size_t bytes = nd * sizeof(double) + ni * sizeof(int);
+    hipError_t e = hipMalloc(&p->mem, bytes);
+    if (e == hipSuccess) {
+        e = hipMemsetAsync(p->mem, 0, bytes, c->stream);
+        if (e != hipSuccess) (void)hipFree(p->mem);
+    }
+    if (e != hipSuccess) {
+        delete p;
+        set_error(std::string("particles_alloc: ") + hipGetErrorString(e));
+        return (int)e;
+    }
+    p->ctx = c; p->cap = cap; p->nwg = nwg;
+    p->buf[0] = (double *)p->mem;
+    p->buf[1] = p->buf[0] + (size_t)6 * cap;
+    p->cand = p->buf[0] + (size_t)12 * cap;
+    p->keep = (int *)(p->buf[0] + nd);
+    p->wg_count = p->keep + cap;
+    p->wg_off = p->wg_count + nwg;
+    p->count = p->wg_off + nwg;
+    p->err = p->count + 2;
+    c->psets.push_back(p);
+    *out = p;
+    return 0;
+}
+
+static void particles_free_mem(pyrohip_particles *p)
+{
+    if (p->mem) (void)hipFree(p->mem);
+    p->mem = nullptr; p->ctx = nullptr;
+    p->buf[0] = p->buf[1] = p->cand = nullptr;
+    p->keep = p->wg_count = p->wg_off = p->count = p->err = nullptr;
+}
+
+int particles_release(pyrohip_particles *p)
+{
+    if (pyrohip_ctx *c = p->ctx) {
+        (void)hipSetDevice(c->device);
+        (void)hipStreamSynchronize(c->stream);
+        for (size_t k = 0; k < c->psets.size(); k++)
+            if (c->psets[k] == p) { c->psets.erase(c->psets.begin() + k); break; }
+        particles_free_mem(p);
+    }
+    delete p;
+    return 0;
+}
+
 }  // namespace pyro
 
 using namespace pyro;
@@ -399,6 +453,10 @@ int pyrohip_shutdown(pyrohip_ctx *c)
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     pyrohip_comm_destroy(c);
+    // particle sets still alive: their device memory goes with the context, the handles stay
+    // valid for pyrohip_particles_destroy (a Python object collected after the context closed)
+    for (pyrohip_particles *p : c->psets) particles_free_mem(p);
+    c->psets.clear();
     c->staging.release();
     c->reduce.release();
     c->prio_board.release();

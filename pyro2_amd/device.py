@@ -974,3 +974,74 @@ class DeviceMG:
         self._call("pyrohip_mg_solve", rtol, int(max_cycles), C.byref(nc),
                    C.byref(res), C.byref(rel))
         return nc.value, res.value, rel.value
+
+
+class DeviceParticles:
+    """a tracer particle set on the device (pyrohip_particles_*): current and initial
+    positions and the last velocities of up to `capacity` particles, (n, 2) arrays on the host"""
+
+    def __init__(self, ctx, pos, init=None):
+        self.ctx = ctx
+        self._l = ctx._l
+        pos = np.ascontiguousarray(pos, dtype=np.float64).reshape(-1, 2)
+        init = pos if init is None else np.ascontiguousarray(init, dtype=np.float64).reshape(-1, 2)
+        assert init.shape == pos.shape
+        self.capacity = len(pos)
+        self.h = C.c_void_p()
+        with ctx.lock:
+            check(self._l.pyrohip_particles_create(ctx.h, self.capacity, dptr(pos), dptr(init),
+                                                   C.byref(self.h)))
+
+    def __del__(self):
+        # (valid after the context closed as well: shutdown released the device memory, the
+        # library keeps the handle for this call)
+        try:
+            if self.h:
+                self._l.pyrohip_particles_destroy(self.h)
+                self.h = C.c_void_p()
+        except Exception:
+            pass
+
+    def upload(self, pos, init=None, vel=None):
+        """replace the set (at most `capacity` particles)"""
+        a = [None if x is None else np.ascontiguousarray(x, dtype=np.float64).reshape(-1, 2)
+             for x in (pos, init, vel)]
+        n = len(a[0])
+        assert all(x is None or len(x) == n for x in a)
+        null = C.POINTER(C.c_double)()
+        with self.ctx.lock:
+            check(self._l.pyrohip_particles_upload(self.h, n, *[null if x is None or n == 0 else dptr(x)
+                                                                for x in a]))
+
+    def download(self):
+        """(pos, init, vel) of the live particles"""
+        out = [np.empty((self.capacity, 2)) for _ in range(3)]
+        n = C.c_int()
+        with self.ctx.lock:
+            check(self._l.pyrohip_particles_download(self.h, C.byref(n), *[dptr(x) for x in out]))
+        return tuple(x[:n.value].copy() for x in out)
+
+    def count(self):
+        n = C.c_int()
+        with self.ctx.lock:
+            check(self._l.pyrohip_particles_count(self.h, C.byref(n)))
+        return n.value
+
+    def advance(self, state, grid, bc_kinds, mode, indices, dt):
+        """one update over dt with the velocity in `state` (pyrohip_particles_advance).
+        grid: anything with xmin, xmax, ymin, ymax, dx, dy; bc_kinds: the four particle
+        boundary names (xlb, xrb, ylb, yrb); mode: "planes" (indices iu, iv) or "ratio"
+        (indices inum_x, inum_y, iden)"""
+        P = _lib.ParticleParams()
+        P.size = C.sizeof(_lib.ParticleParams)
+        P.xmin, P.xmax, P.ymin, P.ymax = (float(grid.xmin), float(grid.xmax), float(grid.ymin),
+                                          float(grid.ymax))
+        P.dx, P.dy = float(grid.dx), float(grid.dy)
+        for k, b in enumerate(bc_kinds):
+            P.bc[k] = _lib.PART_BC_CODE[b] if isinstance(b, str) else int(b)
+        P.vel_mode = {"planes": _lib.PART_VEL_PLANES, "ratio": _lib.PART_VEL_RATIO}[mode]
+        assert len(indices) == (3 if mode == "ratio" else 2)
+        for k, n in enumerate(indices):
+            P.idx[k] = int(n)
+        with self.ctx.lock:
+            check(self._l.pyrohip_particles_advance(self.h, state.h, C.byref(P), float(dt)))

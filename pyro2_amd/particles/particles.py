@@ -16,10 +16,18 @@ expression by expression, so positions agree with pyro's bit for bit:
     the ORDER of the particles reverses at every update -- kept, because the
     order is what `get_positions()` and the output file show.
 
-Particles are a host-side diagnostic of O(100) points.  The velocity field is
-passed in by the solver (constant for advection) or taken from the state's
-derived "velocity" (downloaded from the device once per step, only when
-particles are enabled).
+The particles have two homes.  `update_particles(dt, u, v)` with host arrays
+(the advection solvers: a constant velocity field, and user code) is the NumPy
+path above.  Where the velocity comes out of the evolving state -- stored
+x-/y-velocity planes, or momenta over density / height --
+`update_particles_device` runs the same arithmetic in three HIP launches beside
+the solver's step (csrc/particles.hip, pyrohip_particles_advance): the state is
+never downloaded for the tracers, and the positions are the same bit for bit.
+`pos`, `init` and `vel` are properties over a host copy and a device copy
+(device.DeviceParticles) with validity flags: the set is downloaded only when
+somebody looks (get_positions, write_particles, ...), and uploaded again after
+the host copy was ASSIGNED (io_pyro.read, the host update).  Writing into an
+array a property handed out does not reach the device: assign the array back.
 """
 import numpy as np
 
@@ -72,6 +80,9 @@ class Particles:
     def __init__(self, sim_data, bc, n_particles, particle_generator="grid",
                  pos_array=None, init_array=None):
         self.sim_data, self.bc = sim_data, bc
+        self._dev = None                  # device.DeviceParticles, made by the first device update
+        self._host_valid, self._dev_valid = True, False
+        self._pos = self._init = self._vel = np.zeros((0, 2))
         self.pos = np.zeros((0, 2))
         self.init = np.zeros((0, 2))
         self.vel = np.zeros((0, 2))
@@ -92,6 +103,49 @@ class Particles:
         self._dedupe()
         self.vel = np.zeros_like(self.pos)
 
+    # ---- host copy <-> device copy -----------------------------------------
+    def _host(self):
+        if not self._host_valid:
+            self._pos, self._init, self._vel = self._dev.download()
+            self._host_valid = True
+
+    def _assign(self, name, value):
+        self._host()                      # the other two arrays must be current
+        setattr(self, name, value)
+        self._dev_valid = False
+
+    pos = property(lambda self: (self._host(), self._pos)[1],
+                   lambda self, a: self._assign("_pos", a))
+    init = property(lambda self: (self._host(), self._init)[1],
+                    lambda self, a: self._assign("_init", a))
+    vel = property(lambda self: (self._host(), self._vel)[1],
+                   lambda self, a: self._assign("_vel", a))
+
+    def _device(self, ctx):
+        """the DeviceParticles holding the current set (uploads after the host copy was assigned)"""
+        if not self._dev_valid:
+            pos, init, vel = self._pos, self._init, self._vel
+            if len(vel) != len(pos):
+                vel = np.zeros_like(pos)
+            from .. import device
+            if self._dev is None or self._dev.ctx is not ctx or not self._dev.ctx.h or \
+                    self._dev.capacity < len(pos):
+                self._dev = device.DeviceParticles(ctx, pos, init)
+            self._dev.upload(pos, init, vel)
+            self._dev_valid = True
+        return self._dev
+
+    def update_particles_device(self, dt, state, mode, indices):
+        """update_particles + enforce_particle_boundaries on the device, with the velocity read
+        from the planes of `state` (device.DeviceState) as they are, ghost cells included.
+        mode "planes": indices (iu, iv); "ratio": (inum_x, inum_y, iden), u = U[inum_x] / U[iden]"""
+        if self._host_valid and len(self._pos) == 0:
+            return                        # nothing left to move
+        myg, bc = self.sim_data.grid, self.bc
+        dev = self._device(state.ctx)
+        dev.advance(state, myg, (bc.xlb, bc.xrb, bc.ylb, bc.yrb), mode, indices, dt)
+        self._host_valid = False
+
     # pyro keys its dict by the initial position: a second particle with the
     # same initial position replaces the first (keeping the first one's slot)
     def _dedupe(self):
@@ -108,7 +162,9 @@ class Particles:
 
     @property
     def n_particles(self):
-        return len(self.pos)
+        if not self._host_valid:
+            return self._dev.count()      # (4 bytes instead of the set)
+        return len(self._pos)
 
     @property
     def particles(self):

@@ -108,7 +108,7 @@ class NullSimulation:
     def __str__(self):
         return f"pyro Simulation:\n  solver: {self.solver_name}\n  problem: {self.problem_name}\n"
 
-    # ---- tracer particles (pyro/particles; host-side diagnostic) ---------
+    # ---- tracer particles (pyro/particles) --------------------------------
     def setup_particles(self, bc):
         """particles.do_particles = 1: seed the tracers the way every solver's
         initialize() does (e.g. advection/simulation.py:30-33)"""
@@ -122,17 +122,48 @@ class NullSimulation:
 
     def advance_particles(self, u=None, v=None):
         """move the tracers over self.dt with the cell-centred velocity: the
-        arrays given, else the stored x-/y-velocity, else the derived
-        "velocity" (read from the device once, only when particles exist)"""
+        arrays given (host path), else the velocity in the evolving state --
+        on the device where _device_particle_source() finds it there, else
+        on the host from the stored x-/y-velocity or the derived "velocity"
+        (which downloads the state)"""
         if self.particles is None:
             return
         cc = self.cc_data
         if u is None and v is None:
+            src = self._device_particle_source()
+            if src is not None:
+                # device_state() carries out a pending ghost fill / upload, as the host
+                # path's read of the data would; the state itself is only read
+                self.particles.update_particles_device(self.dt, cc.device_state(), *src)
+                return
             if "x-velocity" in cc.names:
                 u, v = cc.get_var_readonly("x-velocity"), cc.get_var_readonly("y-velocity")
             else:
                 u, v = cc.get_var_readonly("velocity")
         self.particles.update_particles(self.dt, u, v)
+
+    def _device_particle_source(self):
+        """(mode, plane indices) of the tracers' velocity in the state when they can be
+        advanced on the device (gpu.device_particles, boundary kinds the kernel knows,
+        stored velocities or momenta over density / height), else None"""
+        from . import _lib
+        ps, names = self.particles, self.cc_data.names
+        if self._rp_opt("gpu.device_particles", 1) != 1 or ps.bc is None:
+            return None
+        if any(b not in _lib.PART_BC_CODE for b in (ps.bc.xlb, ps.bc.xrb, ps.bc.ylb, ps.bc.yrb)):
+            return None
+        if ps.n_particles > _lib.PARTICLES_MAX:     # (beyond one scanning workgroup: host path)
+            return None
+        if "x-velocity" in names:
+            if "y-velocity" not in names:
+                return None
+            return "planes", (names.index("x-velocity"), names.index("y-velocity"))
+        if "x-momentum" in names and "y-momentum" in names:
+            for den in ("density", "height"):
+                if den in names:
+                    return "ratio", (names.index("x-momentum"), names.index("y-momentum"),
+                                     names.index(den))
+        return None
 
     def finished(self):
         return self.cc_data.t >= self.tmax or self.n >= self.max_steps
