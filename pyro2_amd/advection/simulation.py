@@ -85,21 +85,9 @@ class Simulation(NullSimulation):
         over the grid (csrc/advection.hip: k_adv_multi).  Returns the time steps taken."""
         tm = self.tc.timer("evolve")
         tm.begin()
-        t0, n0 = self.cc_data.t, self.n
-        dts = []
-        while len(dts) < nsteps and not self.finished():
-            keep = (getattr(self, "dt", None), getattr(self, "dt_old", None))
-            self.compute_timestep()
-            if not self.dt > 0.0:
-                # no positive step to hand to the device: undo this policy call (t, n were not
-                # advanced for it) and let the driver take the step singly, like the reference
-                self.dt, self.dt_old = keep
-                break
-            dts.append(float(self.dt))
-            self.cc_data.t += self.dt       # as evolve() does
-            self.n += 1
+        n0 = self.n
+        dts = self._plan_timesteps(nsteps, lambda dt: dt > 0.0)
         if dts:
-            self.cc_data.t, self.n = t0, n0
             g = self.cc_data.grid
             st = self.cc_data.device_state(fuse_fill=True)
             self.cc_data.take_pending_fill()     # every step of the call fills

@@ -128,21 +128,9 @@ class Simulation(NullSimulation):
         tm.begin()
         cc = self.cc_data
         cc.fill_BC_all()                         # (the time step looks at filled ghost cells)
-        t0, n0 = cc.t, self.n
-        dts = []
-        while len(dts) < nsteps and not self.finished():
-            keep = (getattr(self, "dt", None), getattr(self, "dt_old", None))
-            self.compute_timestep()
-            if not (self.dt > 0.0 and np.isfinite(self.dt)):
-                # no usable step to hand to the device: undo this policy call and let the
-                # driver take the step singly, like the reference
-                self.dt, self.dt_old = keep
-                break
-            dts.append(float(self.dt))
-            cc.t += self.dt                      # as evolve() does
-            self.n += 1
+        n0 = self.n
+        dts = self._plan_timesteps(nsteps, lambda dt: dt > 0.0 and np.isfinite(dt))
         if dts:
-            cc.t, self.n = t0, n0
             g = cc.grid
             uv = self._velocities() if self.particles is not None else None
             st = cc.device_state(fuse_fill=True)

@@ -140,21 +140,8 @@ class Simulation(AdvectionSimulation):
         tm = self.tc.timer("evolve")
         tm.begin()
         cc = self.cc_data
-        t0, n0 = cc.t, self.n
-        dts = []
-        while len(dts) < nsteps and not self.finished():
-            keep = (getattr(self, "dt", None), getattr(self, "dt_old", None))
-            self.compute_timestep()
-            if not (self.dt > 0.0 and np.isfinite(self.dt)):
-                # no usable step to hand to the device: undo this policy call and let the
-                # driver take the step singly, like the reference
-                self.dt, self.dt_old = keep
-                break
-            dts.append(float(self.dt))
-            cc.t += self.dt                      # as evolve() does
-            self.n += 1
+        dts = self._plan_timesteps(nsteps, lambda dt: dt > 0.0 and np.isfinite(dt))
         if dts:
-            cc.t, self.n = t0, n0
             st = cc.device_state(fuse_fill=True)
             cc.take_pending_fill()
             try:

@@ -60,6 +60,8 @@ UNITS = [
     ("comp_fv4.hip", "fv4_exact", ["-ffp-contract=off", "-DPYRO_FAST=0"]),
     ("comp_fv4.hip", "fv4_fast", ["-ffp-contract=fast", "-DPYRO_FAST=1"]),
     ("comp_api.hip", "comp_api", ["-ffp-contract=off"]),
+    # the device-side run protocol: the small kernels between two steps and their host side
+    ("evolve.hip", "evolve", ["-ffp-contract=off"]),
     ("multigrid.hip", "multigrid", ["-ffp-contract=off"]),
     ("mg_march.hip", "mg_march", ["-ffp-contract=off", "-mllvm", "-pragma-unroll-threshold=200000"]),
     # ... its instances with a tail (MGMarch::tail) in units of their own: minutes each

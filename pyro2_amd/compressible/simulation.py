@@ -12,7 +12,7 @@ hse / ambient user boundaries.
 import numpy as np
 
 from .. import device
-from .._lib import BC_CODE, PyroHipError
+from .._lib import BC_CODE
 from ..mesh import boundary as bnd
 from ..simulation_null import NullSimulation, bc_setup, grid_setup
 from ..util import msg
@@ -280,36 +280,13 @@ class Simulation(NullSimulation):
         """up to nsteps of fill_BC_all + compute_timestep + evolve on the device without
         a host round trip per step; the driver's dt policy (simulation_null.py:222-244)
         runs in a kernel.  Returns the time steps taken."""
-        from ..decomp import DtPolicy
-        rp = self.rp
-        pol = DtPolicy(self.tmax, rp.get_param("driver.init_tstep_factor"),
-                       rp.get_param("driver.max_dt_change"), rp.get_param("driver.fix_dt"))
-        pol.t, pol.n = float(self.cc_data.t), int(self.n)
-        pol.dt_old = float(getattr(self, "dt_old", -1.e33))
-        tm = self.tc.timer("evolve")
-        tm.begin()
-        st = self._device_state()
-        try:
+        def call(st, pol, cfl, n):
             if self.cc_data.slab is not None:     # COLLECTIVE
-                dts = self._slab().evolve(pol, float(rp.get_param("driver.cfl")), int(nsteps),
-                                          params=self._params())
-            else:
-                dts = st.comp_evolve(self._params(), float(rp.get_param("driver.cfl")), pol, int(nsteps))
-        except PyroHipError as e:
-            # the library's own fusability rules (e.g. a SphericalPolar grid too small for the
-            # tile kernel, mixed boundary kinds on a side) are stricter than can_evolve_many's:
-            # a refusal before the first step means "step singly", which the staged set can
-            if "device-side stepping:" not in str(e) or pol.n != int(self.n):
-                raise
-            self._device_stepping_refused = True
-            dts = []
-        finally:
-            self.cc_data.device_modified()
-            self.cc_data.t, self.n, self.dt_old = pol.t, pol.n, pol.dt_old
-        if len(dts):
-            self.dt = float(dts[-1])
-        tm.end()
-        return dts
+                return self._slab().evolve(pol, cfl, n, params=self._params())
+            return st.comp_evolve(self._params(), cfl, pol, n)
+        # (refusable: e.g. a SphericalPolar grid too small for the tile kernel, mixed boundary
+        # kinds on a side -- the staged set can step those)
+        return self._evolve_by_device_policy(nsteps, self._device_state, call, refusable=True)
 
     def clean_state(self, U):
         """density floor on a host array (the device step applies it itself)"""

@@ -114,30 +114,13 @@ class Simulation(CompressibleSimulation):
         return self._rk_fusable(self._device_state(), method)
 
     def evolve_many(self, nsteps):
-        from .._lib import PyroHipError
-        from ..decomp import DtPolicy
-        rp = self.rp
-        pol = DtPolicy(self.tmax, rp.get_param("driver.init_tstep_factor"),
-                       rp.get_param("driver.max_dt_change"), rp.get_param("driver.fix_dt"))
-        pol.t, pol.n = float(self.cc_data.t), int(self.n)
-        pol.dt_old = float(getattr(self, "dt_old", -1.e33))
-        method = rp.get_param("compressible.temporal_method")
-        tm = self.tc.timer("evolve")
-        tm.begin()
-        st = self._device_state()
-        self.cc_data.take_pending_fill()
-        try:
-            dts = st.comp_rk_evolve(self._params(), self._rk_scratch[1], integration.a[method],
-                                    integration.b[method], float(rp.get_param("driver.cfl")), pol, int(nsteps))
-        except PyroHipError as e:
-            if "device-side stepping:" not in str(e) or pol.n != int(self.n):
-                raise
-            self._device_stepping_refused = True
-            dts = []
-        finally:
-            self.cc_data.device_modified()
-            self.cc_data.t, self.n, self.dt_old = pol.t, pol.n, pol.dt_old
-        if len(dts):
-            self.dt = float(dts[-1])
-        tm.end()
-        return dts
+        method = self.rp.get_param("compressible.temporal_method")
+
+        def start():
+            st = self._device_state()
+            self.cc_data.take_pending_fill()
+            return st
+        return self._evolve_by_device_policy(
+            nsteps, start, lambda st, pol, cfl, n: st.comp_rk_evolve(
+                self._params(), self._rk_scratch[1], integration.a[method], integration.b[method], cfl, pol, n),
+            refusable=True)

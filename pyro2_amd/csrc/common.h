@@ -226,7 +226,7 @@ struct StepScalars {
 // The driver's compute_timestep (simulation_null.py:222-244) for a run that advances on the
 // device: ends the previous step (t, n), decides whether the next one runs (t < tmax, state
 // still valid) and derives its dt from the CFL minimum `cmin` of the state the previous step
-// left.  ONE thread calls it: k_dt_policy (comp_api.hip) between two steps, or the last
+// left.  ONE thread calls it: k_dt_policy (evolve.hip) between two steps, or the last
 // wavefront of the row-marching step kernel to finish (comp_wave.hip: one launch per step).
 // IEEE operations in the reference's order, never contracted.
 __device__ inline void dt_policy_apply(StepScalars *S, double cmin, bool invalid, double *dts,
@@ -334,7 +334,7 @@ struct pyrohip_state {
     int nb_lo = -1, nb_hi = -1;
     bool nb_set = false, halo_pending = false;
     // the ghost frame of the OTHER buffer already holds this step's boundary fill (written
-    // together with this buffer's by k_fill_frame2, comp_api.hip): the step need not copy it
+    // together with this buffer's by k_fill_frame2, evolve.hip): the step need not copy it
     bool frame_prefilled = false;
     // ... or the next launch of the row-marching kernel is the whole step (pyrohip_comp_evolve):
     // it reads ghost cells through the boundary rules and ends with the dt policy (StepPolicy)
@@ -411,6 +411,52 @@ int state_alt(pyrohip_state *s);
 // uploads H.
 int evolve_begin(pyrohip_state *s, const pyrohip_dt_policy *pol, double cfl, double dx, double dy,
                  int max_steps, StepScalars *H);
+
+// ---- the device-side run protocol (evolve.hip) ----
+// 256-thread pieces of a state's ghost frame: the 2 ng full ghost rows in pieces of 256 columns,
+// then the ghost columns of the interior rows, 256 / (2 ng) rows per piece (k_fill_frame2 and the
+// solvers' frame copies: one workgroup per piece)
+inline int frame_pieces(const Geom &g)
+{
+    const int rows_per_piece = 256 / (2 * g.ng);
+    return 2 * g.ng * ((g.qy + 255) / 256) + (g.nx + rows_per_piece - 1) / rows_per_piece;
+}
+// can k_fill_frame2 fill the state's ghost cells (index maps on every side of the four variables, a
+// second buffer)?  halo_ok: x sides that are cuts of a slab pass; sph_ok: a SphericalPolar grid passes
+bool frame_fill_ok(const pyrohip_state *s, bool halo_ok = false, bool sph_ok = false);
+// one call of a solver's stepping loop
+struct EvolveRun {
+    pyrohip_state *s = nullptr;
+    int max_steps = 0;
+    StepScalars H;                    // host copy: uploaded by evolve_open, read back by evolve_close
+    StepScalars *d_scal = nullptr;    // what the policy kernels work on: s->d_scal (one launch per step: StepPolicy::S)
+    bool min_cached = false;          // the call starts from the minimum the last one left (d_scal->min0)
+    const double *dmin = nullptr;     // device: the CFL minimum the next policy call takes ...
+    const double *pend = nullptr;     // ... after reducing the last step's partials into it, if it left any
+    int npend = 0;
+    int cfl_kind = 0;                 // pyrohip_state::cfl_kind / cfl_par of the minimum the run leaves
+    double cfl_par[3] = {0.0, 0.0, 0.0};
+    bool halo_ok = false, sph_ok = false;     // what frame_fill_ok lets pass in this run
+    // the step just launched may have left its CFL partials for the next policy call (pyrohip_state::pend_part)
+    void take_pending() { pend = s->pend_part; npend = s->pend_n; s->pend_part = nullptr; }
+};
+// open: evolve_begin, the cached-minimum decision (global_min: on a context that reduces the CFL
+// minimum over its ranks only a global one is kept, and only if every rank kept its own), the upload
+// of r.H and the reset of the positivity flag
+int evolve_open(EvolveRun &r, pyrohip_state *s, const pyrohip_dt_policy *pol, double cfl, int cfl_kind, double cfl_a,
+                double dx, double dy, int max_steps, bool global_min);
+// first step: ghost fill (frame: by k_fill_frame2 with the other buffer's frame where frame_fill_ok),
+// then -- behind the solver's CFL minimum of the state as handed over -- the policy
+int evolve_fill(EvolveRun &r, bool frame, bool *frame_done);
+int evolve_policy(EvolveRun &r, int m);
+// between two steps: fill + policy of step m in one launch (frame, where frame_fill_ok); else the
+// plain fill (fill: unless the step fills itself) and the policy.  *frame_done: the other buffer's
+// ghost frame is written
+int evolve_between(EvolveRun &r, int m, bool frame, bool fill, bool *frame_done);
+// close: closing policy, the one read-back, buffer parity, the final state's ghost frame (framed: the
+// step kernels work on filled frames; one_launch: they wrote none), the cached minimum, pol, the verdict
+int evolve_close(EvolveRun &r, pyrohip_dt_policy *pol, int *steps_done, double *dts_out, bool framed,
+                 bool one_launch);
 // enqueue the copy of one plane (laid out like the state's) into a (qx, qy) host array; the
 // caller synchronises
 int plane_to_host(pyrohip_state *s, const double *dev_plane, double *host);

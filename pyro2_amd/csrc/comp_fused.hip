@@ -781,9 +781,7 @@ void fused_copy_frame(pyrohip_state *s)
 {
     pyrohip_ctx *c = s->ctx;
     const Geom &g = s->g;
-    const int rows_per_block = 256 / (2 * g.ng);
-    const int nblk = 2 * g.ng * ((g.qy + 255) / 256) + (g.nx + rows_per_block - 1) / rows_per_block;
-    hipLaunchKernelGGL(k_copy_frame4, dim3(nblk), dim3(256), 0, c->stream,
+    hipLaunchKernelGGL(k_copy_frame4, dim3(frame_pieces(g)), dim3(256), 0, c->stream,
                        (const double *)s->d, s->alt_base + geom_lead(g), g);
 }
 

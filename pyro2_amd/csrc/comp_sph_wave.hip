@@ -677,7 +677,7 @@ int comp_step_wave_sph_ex(pyrohip_state *s, const pyrohip_comp_params *p, double
                 (const double *)Uin, Uout, g, P, G, s->d_flag, part, S);
     PYRO_CHECK_HIP(hipGetLastError());
     // the ghost frame of the new buffer: the old (filled) ghost cells, unless the fill before this
-    // step of a device-side run has written both frames (comp_api.hip: k_fill_frame2)
+    // step of a device-side run has written both frames (evolve.hip: k_fill_frame2)
     const bool frame_done = s->frame_prefilled;
     s->frame_prefilled = false;
     const double *dmin;

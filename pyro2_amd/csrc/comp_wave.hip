@@ -1054,7 +1054,7 @@ __global__ __launch_bounds__(64, WAVE_MINW) void k_ctu_wave(const double *__rest
 static int wave_rows(int nx, int ncb, int slots)
 {
     // (round 6: strips down to 8 rows -- grids of 1024^2 ... 1792^2 cells fill the slots with ONE round of
-    // 10- to 28-row strips and pass the tile kernel that way: comp_api.hip: wave_kernel_pays_ctu)
+    // 10- to 28-row strips and pass the tile kernel that way: comp_api.hip: takes_wave_kernel_ctu)
     if (nx <= 32) return nx;
     long best_cost = -1;
     int best = 32;
@@ -1242,7 +1242,7 @@ int comp_step_wave_ex(pyrohip_state *s, const pyrohip_comp_params *p, double dt,
         // the two launches one after the other: the boundary launch held 586 of 2048 wavefront
         // slots for a whole strip time.)
         // old ghost frame -> new buffer, BEFORE the halos land in it (device-side stepping: the
-        // fill before this step has written it already, comp_api.hip: k_fill_frame2)
+        // fill before this step has written it already, evolve.hip: k_fill_frame2)
         if (!s->frame_prefilled) fused_copy_frame(s);
         s->frame_prefilled = false;
         hipStream_t bs = nullptr;
@@ -1309,7 +1309,7 @@ int comp_step_wave_ex(pyrohip_state *s, const pyrohip_comp_params *p, double dt,
     }
     const double *dmin;
     // (device-side stepping: the fill before this step may have written the new buffer's ghost
-    // frame already, comp_api.hip: k_fill_frame2)
+    // frame already, evolve.hip: k_fill_frame2)
     const bool frame_done = post || s->frame_prefilled;
     s->frame_prefilled = false;
     PYRO_TRY(fused_tail(s, part, nwg, frame_done, &dmin, S != nullptr));
@@ -1423,7 +1423,7 @@ int comp_rk_step_wave(pyrohip_state *s, const pyrohip_comp_params *p, pyrohip_st
     // stage 0: the state itself, ghost cells filled in memory (they stay the state's "stale"
     // ghost cells after the step, like the reference's), density floor in place
     // (a device-side run has filled the frames of both buffers with the launch of its dt policy:
-    // comp_api.hip: k_fill_frame2_policy)
+    // evolve.hip: k_fill_frame2_policy)
     const bool prefilled = s->frame_prefilled;
     s->frame_prefilled = false;
     if (!prefilled) PYRO_TRY(pyrohip_fill_bc(s, -1));

@@ -910,8 +910,8 @@ int swe_step_wave(pyrohip_state *s, double dx, double dy, double grav, int limit
                 (const double *)s->d, Uout, g, P, S, part);
     if (!frame_done) {
         // the ghost frame is carried over (the reference updates the interior in place)
-        const int fb = 2 * g.ng * ((g.qy + 255) / 256) + (g.nx + 256 / (2 * g.ng) - 1) / (256 / (2 * g.ng));
-        hipLaunchKernelGGL(k_sw_copy_frame, dim3(fb), dim3(256), 0, c->stream, (const double *)s->d, Uout, g);
+        hipLaunchKernelGGL(k_sw_copy_frame, dim3(frame_pieces(g)), dim3(256), 0, c->stream, (const double *)s->d,
+                           Uout, g);
     }
     PYRO_CHECK_HIP(hipGetLastError());
     double *old_base = s->base;       // the buffers change places
@@ -942,13 +942,6 @@ namespace swf {    // the contracted unit (swe_fast)
 int swe_step_wave(pyrohip_state *, double, double, double, int, int, double, const StepScalars *, double *,
                   int *, bool);
 }
-// (comp_api.hip: the small launches of a device-side run)
-int launch_fill_frame2(pyrohip_state *s, bool *done);
-int launch_dt_policy(pyrohip_ctx *c, StepScalars *S, const double *cflmin, const int *flag, double *dts,
-                     int slot, int final_call, const double *part, int nparts, double *minout);
-int launch_fill_frame2_policy(pyrohip_state *s, StepScalars *S, const double *cflmin, const int *flag, double *dts,
-                              int slot, const double *part, int nparts, double *minout, bool *merged);
-int restore_frame_after_inactive(pyrohip_state *s, int steps, int max_steps, bool halo_ok, bool sph_ok);
 #endif
 }  // namespace pyro
 
@@ -1050,10 +1043,9 @@ int pyrohip_swe_step(pyrohip_state *s, double dx, double dy, double grav, int li
 }
 
 // Up to max_steps iterations of the swe driver loop (pyro_sim.py:241-281 with swe/simulation.py:
-// 143-193: ghost fill, CFL time step, evolve) without a host round trip per step -- as
-// pyrohip_comp_evolve: the ghost fill (both buffers' frames in one launch where the boundaries
-// are outflow / reflect / periodic), the driver's dt policy in a kernel on the CFL minimum the
-// previous step's wavefronts left, the one-launch step kernel.  One synchronisation at the end.
+// 143-193: ghost fill, CFL time step, evolve) without a host round trip per step: the run
+// protocol of DESIGN.md 3.6.1 (evolve.hip) around the one-launch step kernel, whose wavefronts
+// leave the CFL partials the next policy call reduces.
 int pyrohip_swe_evolve(pyrohip_state *s, double dx, double dy, double grav, int limiter, int riemann,
                        int fast_math, double cfl, pyrohip_dt_policy *pol, int max_steps,
                        int *steps_done, double *dts_out)
@@ -1069,45 +1061,26 @@ int pyrohip_swe_evolve(pyrohip_state *s, double dx, double dy, double grav, int 
         PYRO_REQUIRE(bc_is_index_map(s->bc[k], true),
                      "device-side stepping: outflow / reflect / periodic boundaries only");
     pyrohip_ctx *c = s->ctx;
-    StepScalars H;
-    PYRO_TRY(evolve_begin(s, pol, cfl, dx, dy, max_steps, &H));
     PYRO_TRY(state_alt(s));     // (k_fill_frame2 writes the second buffer's frame)
-    // (the CFL minimum the previous call's last step left, where nothing touched the state since:
-    // pyrohip_comp_evolve)
-    const bool min_cached = cfl_min_cached(s, 2, grav, dx, dy);
-    H.min0 = min_cached ? s->next_cfl_min : 0.0;
-    PYRO_CHECK_HIP(hipMemcpyAsync(s->d_scal, &H, sizeof(H), hipMemcpyHostToDevice, c->stream));
-    PYRO_CHECK_HIP(hipStreamSynchronize(c->stream));      // H is on this stack frame
-    PYRO_CHECK_HIP(hipMemsetAsync(s->d_flag, 0, sizeof(int), c->stream));
+    EvolveRun r;
+    PYRO_TRY(evolve_open(r, s, pol, cfl, 2, grav, dx, dy, max_steps, false));
     // one partial per wavefront of the step kernel (46 978 at 16384^2, 128 820 at 32768^2 on 256
     // CUs), sized BEFORE the first launch: growing the buffer later would move what dmin points at
     const size_t nunits = (size_t)swx::swe_wave_units(s->g, c->num_cus);
     PYRO_TRY(c->reduce.ensure(sw_reduce_doubles(nunits) * sizeof(double)));
     double *part = (double *)c->reduce.p;
-    const double *dmin = nullptr;
-    const double *pend = nullptr;
-    int npend = 0, rc = 0;
+    int rc = 0;
     for (int m = 0; m < max_steps && rc == 0; m++) {
-        bool frame_done = false, merged = false;
-        if (m > 0) {       // ghost frames of both buffers + the dt policy in one launch (comp_api.hip)
-            rc = launch_fill_frame2_policy(s, s->d_scal, dmin, s->d_flag, s->d_dts, m, pend, npend,
-                                           const_cast<double *>(dmin), &merged);
-            if (rc) break;
-            frame_done = merged;
-        }
-        if (!merged) {
-        rc = launch_fill_frame2(s, &frame_done);          // pyro_sim.py:250: fill_BC_all
-        if (rc) break;
+        bool frame_done = false;
         if (m == 0) {      // the CFL minimum of the state as handed over (whole array, filled)
-            if (min_cached) dmin = &s->d_scal->min0;
-            else rc = sw_cfl_min_device(s, dx, dy, grav, &dmin, nunits);
+            rc = evolve_fill(r, true, &frame_done);          // pyro_sim.py:250: fill_BC_all
             if (rc) break;
-        }
-        // (later steps: the policy kernel takes the minimum of the step kernel's partials itself)
-        rc = launch_dt_policy(c, s->d_scal, dmin, s->d_flag, s->d_dts, m, 0, pend, npend,
-                              const_cast<double *>(dmin));
+            if (r.min_cached) r.dmin = &s->d_scal->min0;
+            else rc = sw_cfl_min_device(s, dx, dy, grav, &r.dmin, nunits);
+            if (rc == 0) rc = evolve_policy(r, 0);
+        } else
+            rc = evolve_between(r, m, true, true, &frame_done);
         if (rc) break;
-        }
         int np = 0;
         rc = fast_math ? swf::swe_step_wave(s, dx, dy, grav, limiter, riemann, 0.0, s->d_scal, part, &np, frame_done)
                        : swx::swe_step_wave(s, dx, dy, grav, limiter, riemann, 0.0, s->d_scal, part, &np, frame_done);
@@ -1115,37 +1088,11 @@ int pyrohip_swe_evolve(pyrohip_state *s, double dx, double dy, double grav, int 
             set_error("pyrohip_swe_evolve: the step kernel left more CFL partials than were sized for");
             rc = PYROHIP_ERR_ARG;
         }
-        pend = part; npend = np;
+        r.pend = part; r.npend = np;    // (held here, not in the state: the kernel's own buffer)
     }
     PYRO_TRY(rc);
-    PYRO_TRY(launch_dt_policy(c, s->d_scal, dmin, s->d_flag, s->d_dts, max_steps, 1, pend, npend,
-                              const_cast<double *>(dmin)));
-    char *hb = (char *)c->reduce_host;                       // 256 pinned bytes
-    PYRO_CHECK_HIP(hipMemcpyAsync(hb, s->d_scal, sizeof(StepScalars), hipMemcpyDeviceToHost, c->stream));
-    PYRO_CHECK_HIP(hipMemcpyAsync(hb + sizeof(StepScalars) + 8, dmin, sizeof(double),
-                                  hipMemcpyDeviceToHost, c->stream));
-    if (dts_out)
-        PYRO_CHECK_HIP(hipMemcpyAsync(dts_out, s->d_dts, (size_t)max_steps * sizeof(double),
-                                      hipMemcpyDeviceToHost, c->stream));
-    PYRO_CHECK_HIP(hipStreamSynchronize(c->stream));
-    memcpy(&H, hb, sizeof(H));
-    const double lastmin = *(double *)(hb + sizeof(StepScalars) + 8);
-    // max_steps swaps were made; the last state that advanced sits H.steps swaps from the start
-    if ((max_steps - H.steps) % 2) {
-        double *old_base = s->base;
-        s->base = s->alt_base;
-        s->alt_base = old_base;
-        s->d = s->base + geom_lead(s->g);
-    }
-    PYRO_TRY(restore_frame_after_inactive(s, H.steps, max_steps, false, false));
-    // the minimum of the last launch belongs to the state only if that launch advanced it
-    s->next_cfl_min = (H.steps == max_steps && !H.dead) ? lastmin : -1.0;
-    s->cfl_kind = 2;
-    s->cfl_par[0] = grav; s->cfl_par[1] = dx; s->cfl_par[2] = dy;
-    s->ghost_by_rules = false;
-    pol->t = H.t; pol->dt_old = H.dt_old; pol->n = H.n;
-    *steps_done = H.steps;
-    return 0;
+    // (no swe kernel raises the positivity flag: the verdict is always "valid")
+    return evolve_close(r, pol, steps_done, dts_out, true, false);
 }
 
 // stage: 0 Uxl0 1 Uxr0 2 Uyl0 3 Uyr0 (face states before the transverse

@@ -309,19 +309,9 @@ class DeviceState:
     def swe_evolve(self, dx, dy, grav, limiter, riemann, cfl, policy, max_steps, fast_math=0):
         """up to max_steps swe steps with the driver's dt policy on the device (as comp_evolve);
         returns the dt of the steps taken"""
-        from ._lib import DtPolicyC
         r = self.SWE_RIEMANN[riemann] if isinstance(riemann, str) else int(riemann)
-        pc = DtPolicyC(policy.tmax, policy.f0, policy.mx, policy.fix, policy.t, policy.dt_old,
-                       policy.n)
-        done = C.c_int()
-        dts = np.empty(int(max_steps))
-        with self.ctx.lock:
-            rc = self._l.pyrohip_swe_evolve(self.h, float(dx), float(dy), float(grav), int(limiter), r,
-                                            int(fast_math), float(cfl), C.byref(pc), int(max_steps),
-                                            C.byref(done), dptr(dts))
-        policy.t, policy.dt_old, policy.n = pc.t, pc.dt_old, int(pc.n)
-        check(rc)
-        return dts[:done.value]
+        return self._evolve(policy, max_steps, lambda *tail: self._l.pyrohip_swe_evolve(
+            self.h, float(dx), float(dy), float(grav), int(limiter), r, int(fast_math), float(cfl), *tail))
 
     def swe_stage(self, name):
         names = ("Uxl0", "Uxr0", "Uyl0", "Uyr0", "FxT", "FyT", "Fx", "Fy")
@@ -679,40 +669,35 @@ class DeviceState:
             check(self._l.pyrohip_comp_rk_step(self.h, C.byref(params), kstate.h, float(dt), len(b),
                                                dptr(a), dptr(b)))
 
-    def comp_rk_evolve(self, params, kstate, a, b, cfl, policy, max_steps):
-        """up to max_steps compressible_rk steps with the driver's dt policy on the device
-        (as comp_evolve); returns the dt of the steps taken"""
-        from ._lib import DtPolicyC
-        a = np.ascontiguousarray(a, dtype=np.float64)
-        b = np.ascontiguousarray(b, dtype=np.float64)
-        pc = DtPolicyC(policy.tmax, policy.f0, policy.mx, policy.fix, policy.t, policy.dt_old,
-                       policy.n)
+    def _evolve(self, policy, max_steps, call):
+        """one device-side run: call(pol, max_steps, steps_done, dts_out) is the
+        library's entry point with its leading arguments bound; `policy` is advanced in place,
+        also when the run ends on an invalid state"""
+        pc = _lib.DtPolicyC(policy.tmax, policy.f0, policy.mx, policy.fix, policy.t, policy.dt_old,
+                            policy.n)
         done = C.c_int()
         dts = np.empty(int(max_steps))
         with self.ctx.lock:
-            rc = self._l.pyrohip_comp_rk_evolve(self.h, C.byref(params), kstate.h, len(b), dptr(a), dptr(b),
-                                                float(cfl), C.byref(pc), int(max_steps), C.byref(done),
-                                                dptr(dts))
+            rc = call(C.byref(pc), int(max_steps), C.byref(done), dptr(dts))
         policy.t, policy.dt_old, policy.n = pc.t, pc.dt_old, int(pc.n)
         _check_run(rc, dts[:done.value])
         return dts[:done.value]
+
+    def comp_rk_evolve(self, params, kstate, a, b, cfl, policy, max_steps):
+        """up to max_steps compressible_rk steps with the driver's dt policy on the device
+        (as comp_evolve); returns the dt of the steps taken"""
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        return self._evolve(policy, max_steps, lambda *tail: self._l.pyrohip_comp_rk_evolve(
+            self.h, C.byref(params), kstate.h, len(b), dptr(a), dptr(b), float(cfl), *tail))
 
     def comp_evolve(self, params, cfl, policy, max_steps):
         """up to max_steps single_steps (ghost fill, dt policy, evolve) without a host
         round trip per step.  `policy`: an object with tmax, f0 (init_tstep_factor), mx
         (max_dt_change), fix, t, dt_old, n (decomp.DtPolicy / helpers.DtPolicy); it is
         advanced in place.  Returns the dt of the steps taken."""
-        from ._lib import DtPolicyC
-        pc = DtPolicyC(policy.tmax, policy.f0, policy.mx, policy.fix, policy.t, policy.dt_old,
-                       policy.n)
-        done = C.c_int()
-        dts = np.empty(int(max_steps))
-        with self.ctx.lock:
-            rc = self._l.pyrohip_comp_evolve(self.h, C.byref(params), float(cfl), C.byref(pc),
-                                             int(max_steps), C.byref(done), dptr(dts))
-        policy.t, policy.dt_old, policy.n = pc.t, pc.dt_old, int(pc.n)
-        _check_run(rc, dts[:done.value])
-        return dts[:done.value]
+        return self._evolve(policy, max_steps, lambda *tail: self._l.pyrohip_comp_evolve(
+            self.h, C.byref(params), float(cfl), *tail))
 
     STAGES = {"q": 0, "xi": 1, "XM": 2, "XP": 3, "YM": 4, "YP": 5, "FxT": 6,
               "FyT": 7, "Fx": 8, "Fy": 9}

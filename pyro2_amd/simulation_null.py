@@ -203,6 +203,59 @@ class NullSimulation:
         if self.cc_data.t + self.dt > self.tmax:
             self.dt = self.tmax - self.cc_data.t
 
+    def _evolve_by_device_policy(self, nsteps, start, call, refusable=False):
+        """evolve_many of the solvers whose dt policy runs in a kernel: up to
+        nsteps of fill_BC_all + compute_timestep + evolve without a host round trip per step.
+        start() -> device state (and what the solver does first); call(state, policy, cfl,
+        nsteps) -> the time steps taken.  refusable: the library's own rules for device-side
+        stepping are stricter than can_evolve_many's -- a refusal before the first step means
+        "step singly from now on"."""
+        from ._lib import PyroHipError
+        from .decomp import DtPolicy
+        rp = self.rp
+        pol = DtPolicy(self.tmax, rp.get_param("driver.init_tstep_factor"),
+                       rp.get_param("driver.max_dt_change"), rp.get_param("driver.fix_dt"))
+        pol.t, pol.n = float(self.cc_data.t), int(self.n)
+        pol.dt_old = float(getattr(self, "dt_old", -1.e33))
+        tm = self.tc.timer("evolve")
+        tm.begin()
+        st = start()
+        try:
+            dts = call(st, pol, float(rp.get_param("driver.cfl")), int(nsteps))
+        except PyroHipError as e:
+            if not refusable or "device-side stepping:" not in str(e) or pol.n != int(self.n):
+                raise
+            self._device_stepping_refused = True
+            dts = []
+        finally:
+            self.cc_data.device_modified()
+            self.cc_data.t, self.n, self.dt_old = pol.t, pol.n, pol.dt_old
+        if len(dts):
+            self.dt = float(dts[-1])
+        tm.end()
+        return dts
+
+    def _plan_timesteps(self, nsteps, usable):
+        """evolve_many of the solvers whose CFL step is closed-form: the driver's policy gives the
+        dt sequence of up to nsteps iterations beforehand -- computed by the very methods the
+        single step uses; t and n are left where they were.  usable(dt): the solver's own test."""
+        cc = self.cc_data
+        t0, n0 = cc.t, self.n
+        dts = []
+        while len(dts) < nsteps and not self.finished():
+            keep = (getattr(self, "dt", None), getattr(self, "dt_old", None))
+            self.compute_timestep()
+            if not usable(self.dt):
+                # no usable step to hand to the device: undo this policy call (t, n were not
+                # advanced for it) and let the driver take the step singly, like the reference
+                self.dt, self.dt_old = keep
+                break
+            dts.append(float(self.dt))
+            cc.t += self.dt                      # as evolve() does
+            self.n += 1
+        cc.t, self.n = t0, n0
+        return dts
+
     def preevolve(self):
         pass
 

@@ -126,28 +126,16 @@ class Simulation(NullSimulation):
         return not any(cc._has_host_bc(n) for n in cc.names)
 
     def evolve_many(self, nsteps):
-        from ..decomp import DtPolicy
-        rp = self.rp
-        pol = DtPolicy(self.tmax, rp.get_param("driver.init_tstep_factor"),
-                       rp.get_param("driver.max_dt_change"), rp.get_param("driver.fix_dt"))
-        pol.t, pol.n = float(self.cc_data.t), int(self.n)
-        pol.dt_old = float(getattr(self, "dt_old", -1.e33))
-        tm = self.tc.timer("evolve")
-        tm.begin()
-        cc, g = self.cc_data, self.cc_data.grid
-        st = cc.device_state()
-        cc.take_pending_fill()
-        try:
-            dts = st.swe_evolve(g.dx, g.dy, rp.get_param("swe.grav"), rp.get_param("swe.limiter"),
-                                rp.get_param("swe.riemann"), float(rp.get_param("driver.cfl")), pol,
-                                int(nsteps), fast_math=self._fast_math())
-        finally:
-            cc.device_modified()
-            cc.t, self.n, self.dt_old = pol.t, pol.n, pol.dt_old
-        if len(dts):
-            self.dt = float(dts[-1])
-        tm.end()
-        return dts
+        rp, cc, g = self.rp, self.cc_data, self.cc_data.grid
+
+        def start():
+            st = cc.device_state()
+            cc.take_pending_fill()
+            return st
+        return self._evolve_by_device_policy(
+            nsteps, start, lambda st, pol, cfl, n: st.swe_evolve(
+                g.dx, g.dy, rp.get_param("swe.grav"), rp.get_param("swe.limiter"), rp.get_param("swe.riemann"),
+                cfl, pol, n, fast_math=self._fast_math()))
 
     def dovis(self):
         import matplotlib.pyplot as plt

@@ -428,7 +428,7 @@ def test_comp_evolve_global_minimum_every_step(dev, golden, kset):
                                  ("outflow", "reflect", "reflect", "outflow")])
 def test_comp_evolve_wave_fill_and_frame(dev, golden, bcs, launches):
     """device-side stepping with the row-marching kernel.  launches = 3: one launch fills the
-    ghost cells of the state AND writes the other buffer's ghost frame (comp_api.hip:
+    ghost cells of the state AND writes the other buffer's ghost frame (evolve.hip:
     k_fill_frame2; corners through the x rule and then the y rule), the policy kernel takes the
     minimum of the wavefronts' CFL partials itself (the default).  launches = 1: the step kernel
     is the ONLY launch of a step -- it reads ghost cells through the boundary rules (index maps,
@@ -457,6 +457,36 @@ def test_comp_evolve_wave_fill_and_frame(dev, golden, bcs, launches):
             dts += list(s.comp_evolve(P, cfl, pol, c))
         assert dts == list(dref), chunks
         assert np.array_equal(s.download(), Uref), chunks
+
+
+@pytest.mark.parametrize("launches", [1, 3])
+@pytest.mark.parametrize("cut", [2, 3])
+def test_comp_evolve_wave_tmax_inside_a_call(dev, golden, launches, cut):
+    """tmax ends the run INSIDE a call of the row-marching loop: the iterations behind the last
+    step that advanced are inactive (an even and an odd number of them: cut 3 and 2), and what
+    they leave -- buffer parity, the ghost frame of the final state -- must be what single steps
+    to the same tmax leave: dt sequence, pol.t and the WHOLE array, ghost frame and corners
+    included, bit for bit"""
+    from helpers import DtPolicy
+    g = golden("comp_sedov_64_020")
+    meta = g["meta"]
+    ic = np.nan_to_num(g["ic"]).copy()
+    rng = np.random.default_rng(3)
+    ic[:, :, 2] += 1.e-3 * rng.standard_normal(ic.shape[:2])
+    ic[:, :, 3] += 1.e-3 * rng.standard_normal(ic.shape[:2])
+    bcs = ["reflect", "outflow", "periodic", "periodic"]
+    kw = dict(kernel_set=2, march_rows=13)
+    _, dref, _ = device_comp_run(dev, ic, meta, bcs, 0.1, 7, **kw)
+    tmax = float(np.sum(dref[:cut])) + 0.3 * float(dref[cut])
+    Uref, dt_ref, t_ref = device_comp_run(dev, ic, meta, bcs, tmax, 100, **kw)
+    P, cfl = dev_params(meta, step_launches=launches, **kw)
+    s = comp_state(dev, 64, 64, bcs)
+    s.upload(ic)
+    pol = DtPolicy(tmax)
+    dts = list(s.comp_evolve(P, cfl, pol, 2)) + list(s.comp_evolve(P, cfl, pol, 5))
+    assert dts == list(dt_ref)
+    assert pol.t == tmax == t_ref
+    assert np.array_equal(s.download(), Uref)
 
 
 @pytest.mark.parametrize("kset", [0, 1, 2])
