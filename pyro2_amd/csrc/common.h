@@ -106,6 +106,10 @@ struct pyrohip_ctx {
     // tracer particle sets alive on this context (ctx.hip: particles_alloc / particles_release;
     // pyrohip_shutdown releases the device memory of those still here)
     std::vector<pyrohip_particles *> psets;
+    // multigrid.hip: the dynamic-LDS limits of its kernels are set on this device; the phase
+    // clocks of a traced launch (developer aid, pyrohip_mg_tuning.trace)
+    bool mg_attrs_set = false;
+    pyro::DevBuf mg_trace;
 };
 
 // A tracer particle set (particles.hip).  ONE device allocation, made and freed in ctx.hip:

@@ -460,6 +460,7 @@ int pyrohip_shutdown(pyrohip_ctx *c)
     c->staging.release();
     c->reduce.release();
     c->prio_board.release();
+    c->mg_trace.release();
     if (c->reduce_host) (void)hipHostFree(c->reduce_host);
     (void)hipEventDestroy(c->ev0);
     (void)hipEventDestroy(c->ev1);

@@ -77,7 +77,8 @@ struct pyrohip_mg {
     // apron doubles, which is free while most CUs idle).  Measured per V-cycle at
     // 512^2 / 2048^2 / 4096^2 (tools/mg_ab.sh): 5 everywhere 309 / 700 / 1590 us,
     // 10 up to 512^2 284 / 668 / 1529, 10 up to 1024^2 286 / 714 / 1578.
-    int kmax_small = 10, kmax_small_tuned = 10;
+    int kmax_small = 10;
+    bool small_fusion = true;     // ... unless set_smoother(20 + k) switched it off
     int nsmall = 512;
     // levels >= march_min^2 (0: none): the row-marching smoother (mg_march.hip), cut into
     // at most march_waves wavefronts (pyrohip_mg_set_tuning: the tests exercise the kernel
@@ -2129,13 +2130,187 @@ static int mg_smooth_colour_launches(pyrohip_mg *m, int level, int nsmooth)
 
 static int mg_zero(pyrohip_mg *m, int level, int var);
 
-// can the prolongation of level-1's correction ride on the first smoothing
-// launch of `level`?  (wide tile kernel only)
-static bool mg_prolong_fusable(pyrohip_mg *m, int level, int nsmooth)
+// ---- the launch plan ---------------------------------------------------------------------------
+// Which kernel smooths a level, with how many iterations per launch and what a launch carries,
+// is decided HERE and nowhere else: mg_smooth_tiles executes the plan, the V-cycle, the solve
+// loop and the row-window calls ask it.
+enum MGRoute {
+    MGR_COLOURS,         // one launch per colour (smoother 0, or nothing to smooth)
+    MGR_VC,              // variable / general coefficients: one launch per colour
+    MGR_COARSE_KERNEL,   // a V-cycle from this level down is ONE launch (k_mg_coarse_vcycle); a
+                         // smoothing call on its own: as MGR_SINGLE_TILE
+    MGR_SINGLE_TILE,     // the whole level in one workgroup's LDS, all iterations in one launch
+    MGR_TILES            // MGPlan::launches
+};
+enum MGKernel { MGK_MARCH, MGK_BAND, MGK_WIDE };   // mg_march.hip, k_mg_smooth_band, k_mg_smooth_tile
+
+struct MGLaunch {
+    MGKernel kernel;
+    int K;                       // red-black iterations
+    bool pow2; int edge;         // coefficients powers of two; the band kernel's EDGE instance
+    bool prolong; int tail;      // adds the coarser level's correction while loading; MGMarch::tail
+    int TJ, ncs, CR, nchunks, CR_side, nchunks_side;   // MGK_MARCH: the cut (MGMarch)
+    int TI, ntj, ntiles;         // MGK_BAND / MGK_WIDE: the tiles (MGTile), with TJ
+};
+
+struct MGPlan {
+    MGRoute route;
+    std::vector<MGLaunch> launches;   // MGR_TILES, in order
+    bool loads_zero;      // the first launch can take v = 0 while loading: no memset
+    bool pingpong;        // the first launch reads v and writes v2: the buffer it read survives
+    bool fuses_prolong;   // ... and can add the prolonged correction on the way
+    int can_tail;         // of the tail asked for: what the finishing launch can carry (bit mask 1 | 2)
+    int rows_k;           // pyrohip_mg_rows_kmax
+};
+
+// the marching launch's row chunks: as many wavefronts as the device holds at once, not one more
+// (two per SIMD at 256 registers: a wavefront too many would run alone after all the others); the
+// parts that end at the top boundary start up to mgm_align rows lower (mg_march.hip: mgm_part),
+// so the last chunk is made that much shorter.  M: n, code, rows, cv and tail set; -> usable
+static bool mg_march_cut(const pyrohip_mg *m, MGMarch &M, int MK)
+{
+    const int nrows = M.row1 - M.row0 + 1;
+    const int slots = m->march_waves > 0 ? m->march_waves : 8 * (m->ctx->num_cus > 0 ? m->ctx->num_cus : 256);
+    const int pad = (M.code[0] != PYROHIP_BC_PERIODIC && M.row1 == M.n) ? mgm_align(MK) : 0;
+    M.TJ = mgm_tj(MK, M.tail); M.ncs = (M.n + M.TJ - 1) / M.TJ;
+    const bool sides = M.code[2] != PYROHIP_BC_PERIODIC && M.ncs >= 3 && m->march_side > 1.0 &&
+                       M.row0 == 1 && M.row1 == M.n;
+    auto chunks = [&](int rows, int least, int &cr) {   // chunks of about `rows` rows -> count
+        cr = rows < least ? least : rows;
+        if (M.tail) cr += cr & 1;                     // whole coarse rows
+        return (nrows + cr - 1) / cr;
+    };
+    M.nchunks_side = 0; M.CR_side = 0;
+    for (int nch = slots / M.ncs > 2 ? slots / M.ncs : 2; nch >= 2; nch--) {
+        M.nchunks = chunks((nrows + pad + nch - 1) / nch, m->march_minrows, M.CR);
+        if (!sides) break;
+        // a wavefront of a side strip needs march_side times as long per row: fewer rows
+        const int steps = M.CR + 6 * MK;              // apron below and above, 2K steps to drain
+        M.nchunks_side = chunks((int)(steps / m->march_side) - 6 * MK, 8, M.CR_side);
+        if ((M.ncs - 2) * M.nchunks + 2 * M.nchunks_side <= slots || nch == 2) break;
+    }
+    return mg_march_usable(M, MK);
+}
+
+// the plan of `nsmooth` iterations on rows [row0, row1] of `level`, the first launch asked to add
+// the prolonged correction (`prolong`), the last to carry `tail`; exact_k > 0: that many
+// iterations per launch wherever a kernel holds them (row windows), not what the tuning says.
+// Launches nothing, writes nothing.
+static MGPlan mg_plan(const pyrohip_mg *m, int level, int nsmooth, int row0, int row1, bool prolong,
+                      int tail, int exact_k)
 {
     const MGLevel &L = m->lev[level];
-    return !m->vc && m->smoother != 0 && nsmooth > 0 && level > 0 &&
-           (L.n + 2) * (L.n + 2) > MGS_CELLS;
+    const int nrows = row1 - row0 + 1;
+    const MGBC bc = make_bc(m, level, true);
+    const bool hom = !(bc.val[0] || bc.val[1] || bc.val[2] || bc.val[3]);
+    const bool single = (L.n + 2) * (L.n + 2) <= MGS_CELLS;   // whole level in one tile
+    MGPlan P;
+    P.route = m->vc ? MGR_VC
+              : m->smoother == 0 ? MGR_COLOURS
+              : (m->coarse_kernel && level <= MGC_TOP) ? MGR_COARSE_KERNEL
+              : nsmooth <= 0 ? MGR_COLOURS
+              : single ? MGR_SINGLE_TILE : MGR_TILES;
+    P.loads_zero = nsmooth > 0 && (P.route == MGR_TILES || P.route == MGR_COARSE_KERNEL);
+    P.pingpong = P.route == MGR_TILES;
+    P.fuses_prolong = P.route == MGR_TILES && level > 0;   // (wide, band and marching kernels)
+    P.can_tail = 0;
+    // the large levels: the row-marching smoother (mg_march.hip), the ten iterations of a
+    // V-cycle leg in one launch
+    const int MK = 10;
+    const bool march_level = !single && hom && m->march_min > 0 && L.n >= m->march_min;
+    // iterations a tile launch holds; levels up to nsmall^2 live in L2 / Infinity Cache and are
+    // launch-latency bound: as many per launch as the 32-row region allows
+    int kmax = exact_k > 0 ? (exact_k < MGW_KMAX ? exact_k : MGW_KMAX)
+                           : ((m->kmax >= 1 && m->kmax <= MGW_KMAX) ? m->kmax : MGW_KMAX);
+    const int ksmall = exact_k > 0 ? (exact_k > MGW_KMAX ? exact_k : 0) : (m->small_fusion ? m->kmax_small : 0);
+    if (L.n <= m->nsmall && ksmall > kmax) kmax = ksmall;
+    // ten iterations (a whole V-cycle leg) in one row-window launch: the row-marching kernel on
+    // the large levels (windows: no ghost value 0, rows not periodic), the band kernel with its
+    // deep apron on the small ones; five in between
+    bool cst = false;
+    for (int s = 0; s < 4; s++) cst = cst || bc.code[s] == PYROHIP_BC_CONST;
+    const bool march_rows = march_level && !cst && L.n >= 2 * MGM_COLS && bc.code[0] != PYROHIP_BC_PERIODIC;
+    const bool small10 = L.n <= m->nsmall && m->kmax_small >= 10;
+    P.rows_k = (m->vc || m->smoother == 0) ? 0 : ((march_rows || small10) ? 10 : MGW_KMAX);
+    if (P.route != MGR_TILES) return P;
+
+    const double xc = m->beta / (L.dx * L.dx), yc = m->beta / (L.dx * L.dx);   // as MGTile
+    const bool pow2 = mg_pow2(xc, yc, m->alpha + 2.0 * xc + 2.0 * yc, m->allow_pow2);
+    // the band kernel's EDGE instance (ghost values synthesised at the physical sides) wherever
+    // a tile can touch one.  0: no physical side; 1: mirror ghosts (+-own value); 2: value-0
+    // ghosts among them
+    int edge = (bc.code[0] != PYROHIP_BC_PERIODIC || bc.code[2] != PYROHIP_BC_PERIODIC) ? 1 : 0;
+    for (int sd = 0; sd < 4; sd++)
+        if (bc.code[sd] == PYROHIP_BC_CONST || (edge && m->band_genedge)) edge = 2;
+    const bool whole = row0 == 1 && row1 == L.n;
+    int left = nsmooth;
+    MGLaunch X{};
+    X.pow2 = pow2; X.edge = edge;
+    while (march_level && left >= MK) {
+        X.kernel = MGK_MARCH; X.K = MK;
+        X.prolong = prolong && P.launches.empty();
+        MGMarch M{};
+        M.n = L.n; M.row0 = row0; M.row1 = row1;
+        for (int s = 0; s < 4; s++) M.code[s] = bc.code[s];
+        M.cv = X.prolong ? m->lev[level - 1].v : nullptr;
+        // what rides on the launch that finishes the call (mg_march.h: MGMarch::tail)
+        M.tail = (left == MK && whole && m->march_tail) ? tail : 0;
+        if (M.tail == 1 && !(level > 0 && !X.prolong)) M.tail = 0;
+        if (M.tail == 2 && !(X.prolong && level == m->nlevels - 1)) M.tail = 0;
+        bool ok = M.tail != 0 && mg_march_cut(m, M, MK);
+        if (ok) P.can_tail |= M.tail;
+        // (the sums need the solution before the cycle: the first launch of a solve cycle left it)
+        if (M.tail == 2 && !m->old_captured) ok = false;
+        if (!ok) { M.tail = 0; ok = mg_march_cut(m, M, MK); }   // without the tail, then
+        if (!ok) break;
+        X.tail = M.tail; X.TJ = M.TJ; X.ncs = M.ncs; X.CR = M.CR; X.nchunks = M.nchunks;
+        X.CR_side = M.CR_side; X.nchunks_side = M.nchunks_side;
+        P.launches.push_back(X);
+        left -= MK;
+    }
+    X.tail = 0;
+    // measured per V-cycle at 2048^2 / 4096^2 (tools/mg_ab.sh): band kernel up to
+    // 1024^2: 625 / 1497 us, up to 2048^2: 611 / 1485, everywhere: 615 / 1501
+    // (the band kernel: homogeneous boundaries)
+    X.kernel = (L.n <= m->band_maxn && hom) ? MGK_BAND : MGK_WIDE;
+    while (left > 0) {
+        X.K = left < kmax ? left : kmax;
+        X.prolong = prolong && P.launches.empty();
+        X.TI = MGW_RI - 4 * X.K; X.TJ = MGW_LP - 4 * X.K;
+        X.ntj = (L.n + X.TJ - 1) / X.TJ;
+        // Small levels: a launch lasts as long as ONE workgroup needs for its
+        // region (2K sweeps over up to 64 x 128 cells on one CU), while most of
+        // the 256 CUs idle.  Shorter tiles (fewer region rows per workgroup,
+        // more workgroups) cut that latency; the extra apron rows are free here.
+        const int target = m->small_tiles >= 0 ? m->small_tiles : MG_SMALL_TILES_DEFAULT;
+        if (target > 0) {
+            const int want = (target + X.ntj - 1) / X.ntj;
+            int ti = (nrows + want - 1) / want;
+            if (ti < 4) ti = 4;
+            if (ti < X.TI) X.TI = ti;
+        }
+        X.ntiles = ((nrows + X.TI - 1) / X.TI) * X.ntj;
+        P.launches.push_back(X);
+        left -= X.K;
+    }
+    return P;
+}
+
+// a V-cycle leg on the whole level, with all that may ride on it (the up leg's prolongation and sums)
+static MGPlan mg_leg_plan(const pyrohip_mg *m, int level)
+{
+    return mg_plan(m, level, m->nsmooth, 1, m->lev[level].n, true, 2, 0);
+}
+
+// workgroups of a sum over `nrows` rows of an n-wide level: a workgroup covers 256 columns of a
+// row, as many across as a row has such pieces (16 across on a 2048^2 level left half of them
+// idle: 31 -> 21 us), ~2048 in all on the large levels (512 workgroups with long dependent sums:
+// 84 us for the 4096^2 level, 1.6 TB/s)
+static dim3 mg_sum_grid(int n, int nrows)
+{
+    const int gx = n >= 4096 ? 16 : (n >= 256 ? n / 256 : 1);
+    const int gy = nrows >= 64 ? (2048 / gx < nrows ? 2048 / gx : nrows) : 1;
+    return dim3(gx, gy);
 }
 
 // a smoothing launch read L.v and wrote L.v2: L.v2 is the solution now.  The first such
@@ -2157,202 +2332,136 @@ static void mg_swap_solution(pyrohip_mg *m, int level)
         L.v2 = read;
 }
 
-static int mg_smooth_tiles(pyrohip_mg *m, int level, int nsmooth, bool prolong = false,
-                           int row0 = 1, int row1 = -1, int *nlaunch = nullptr, int tail = 0)
+// once per context (device): the kernels' dynamic LDS above the default limit; the clocks of a
+// traced launch (developer aid; 32 for the band kernel, 16 for the coarse one)
+static int mg_launch_setup(pyrohip_mg *m, long long **trace)
 {
-    MGLevel &L = m->lev[level];
-    m->tail_done = 0;
-    if (row1 < 0) row1 = L.n;
-    const int nrows = row1 - row0 + 1;
-    int launches = 0;
+    *trace = nullptr;
 #ifndef PYRO_EMU
-    static bool attr_set = false;
-    if (!attr_set) {
-        PYRO_CHECK_HIP(hipFuncSetAttribute((const void *)k_mg_smooth_tile<256, 0>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)MGS_LDS));
-        PYRO_CHECK_HIP(hipFuncSetAttribute((const void *)k_mg_smooth_tile<MGW_NT, MGW_LP>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)MGW_LDS));
-        PYRO_CHECK_HIP(hipFuncSetAttribute((const void *)k_mg_smooth_tile<MGW_NT, MGW_LP, true>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)MGW_LDS));
-        const void *bands[] = {
+    pyrohip_ctx *c = m->ctx;
+    if (!c->mg_attrs_set) {
+        const void *fns[] = {
+            (const void *)k_mg_smooth_tile<MGW_NT, MGW_LP>, (const void *)k_mg_smooth_tile<MGW_NT, MGW_LP, true>,
 #define MGB_INST(P2, E) (const void *)k_mg_smooth_band<P2, E, false, 4>, (const void *)k_mg_smooth_band<P2, E, true, 4>
             MGB_INST(false, 0), MGB_INST(false, 1), MGB_INST(false, 2), MGB_INST(true, 0), MGB_INST(true, 1), MGB_INST(true, 2)
 #undef MGB_INST
         };
-        for (const void *fn : bands)
-            PYRO_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)MGW_LDS));
-        attr_set = true;
+        for (const void *fn : fns)
+            PYRO_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MGW_LDS));
+        PYRO_CHECK_HIP(hipFuncSetAttribute((const void *)k_mg_smooth_tile<256, 0>,
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)MGS_LDS));
+        PYRO_CHECK_HIP(hipFuncSetAttribute((const void *)k_mg_coarse_vcycle,
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)MGC_LDS));
+        c->mg_attrs_set = true;
     }
+    if (m->trace) {
+        PYRO_TRY(c->mg_trace.ensure(32 * sizeof(long long)));
+        *trace = (long long *)c->mg_trace.p;
+    }
+#else
+    (void)m;
 #endif
+    return 0;
+}
+
+// executes mg_plan: the launches, the buffers they trade, what they carried
+static int mg_smooth_tiles(pyrohip_mg *m, int level, int nsmooth, bool prolong = false,
+                           int row0 = 1, int row1 = -1, int *nlaunch = nullptr, int tail = 0,
+                           int exact_k = 0)
+{
+    MGLevel &L = m->lev[level];
+    m->tail_done = 0;
+    if (row1 < 0) row1 = L.n;
+    const MGPlan P = mg_plan(m, level, nsmooth, row0, row1, prolong, tail, exact_k);
+    PYRO_REQUIRE(nsmooth > 0 && (P.route == MGR_TILES || P.route == MGR_SINGLE_TILE || P.route == MGR_COARSE_KERNEL),
+                 "internal: not a call for the tile smoother");
     MGTile A;
+    PYRO_TRY(mg_launch_setup(m, &A.trace));
     A.f = L.f; A.n = L.n; A.pitch = L.pitch; A.dx = L.dx;
     A.xc = m->beta / (L.dx * L.dx);
     A.yc = m->beta / (L.dx * L.dx);
     A.denom = m->alpha + 2.0 * A.xc + 2.0 * A.yc;
     A.rdenom = 1.0 / A.denom;
     A.kx = A.xc * A.rdenom; A.ky = A.yc * A.rdenom;
-    const bool pow2 = mg_pow2(A.xc, A.yc, A.denom, m->allow_pow2);
     A.bc = make_bc(m, level, true);
-    A.single = ((L.n + 2) * (L.n + 2) <= MGS_CELLS) ? 1 : 0;   // whole level in one tile
-    A.cv = nullptr; A.cpitch = 0;
-    if (prolong) { A.cv = m->lev[level - 1].v; A.cpitch = m->lev[level - 1].pitch; }
+    A.single = P.route == MGR_TILES ? 0 : 1;
+    A.cv = prolong ? m->lev[level - 1].v : nullptr;
+    A.cpitch = prolong ? m->lev[level - 1].pitch : 0;
     A.vin_zero = 0;
     A.row0 = row0; A.row1 = row1;
-    A.trace = nullptr;
-#ifndef PYRO_EMU
-    const bool tracing = m->trace;
-    static long long *d_trace = nullptr;
-    if (tracing) {
-        if (!d_trace) PYRO_CHECK_HIP(hipMalloc((void **)&d_trace, 32 * sizeof(long long)));
-        A.trace = d_trace;
-    }
-#endif
     if (m->v_is_zero[level]) {
         if (A.single) PYRO_TRY(mg_zero(m, level, 0));   // generic variant: materialise
         else A.vin_zero = 1;
         m->v_is_zero[level] = false;
     }
-    int kmax = (m->kmax >= 1 && m->kmax <= MGW_KMAX) ? m->kmax : MGW_KMAX;
-    // levels up to 1024^2 live in L2 / Infinity Cache and are launch-latency
-    // bound: fuse as many iterations per launch as the 32-row region allows
-    if (L.n <= m->nsmall && m->kmax_small > kmax) kmax = m->kmax_small;
-    int left = nsmooth;
-    // the large levels: the row-marching smoother (mg_march.hip), the ten iterations of a
-    // V-cycle leg in one launch
-    const int march_min = m->march_min, march_waves = m->march_waves;
-    const bool hom_bc = !(A.bc.val[0] || A.bc.val[1] || A.bc.val[2] || A.bc.val[3]);
-    while (!A.single && hom_bc && march_min > 0 && L.n >= march_min) {
-        const int MK = 10;
-        if (left < MK) break;
-        MGMarch M;
-        M.vin = L.v; M.f = L.f; M.vout = L.v2; M.n = L.n; M.pitch = L.pitch;
-        M.xc = A.xc; M.yc = A.yc; M.denom = A.denom; M.rdenom = A.rdenom; M.kx = A.kx; M.ky = A.ky;
-        for (int s = 0; s < 4; s++) M.code[s] = A.bc.code[s];
-        M.cv = A.cv; M.cpitch = A.cpitch; M.vin_zero = A.vin_zero;
-        M.row0 = row0; M.row1 = row1;
-        // what rides on the launch that finishes the call (mg_march.h: MGMarch::tail)
-        M.tail = (left == MK && row0 == 1 && row1 == L.n && m->march_tail) ? tail : 0;
-        if (M.tail == 1 && !(level > 0 && !M.cv)) M.tail = 0;
-        if (M.tail == 2 && !(m->old_captured && M.cv && level == m->nlevels - 1)) M.tail = 0;
-        M.alpha = m->alpha; M.beta = m->beta; M.dx2 = L.dx * L.dx; M.rdx2 = 1.0 / M.dx2; M.small = 1.e-16;
-        M.cf = nullptr; M.cfpitch = 0; M.old = nullptr; M.partial = nullptr;
-        // row chunks: as many wavefronts as the device holds at once, not one more (two per
-        // SIMD at 256 registers: a wavefront too many would run alone after all the others); the
-        // parts that end at the top boundary start up to mgm_align rows lower (mg_march.hip:
-        // mgm_part), so the last chunk is made that much shorter
-        const int slots = march_waves > 0 ? march_waves : 8 * (m->ctx->num_cus > 0 ? m->ctx->num_cus : 256);
-        const int pad = (M.code[0] != PYROHIP_BC_PERIODIC && row1 == L.n) ? mgm_align(MK) : 0;
-        auto cut = [&]() {
-            M.TJ = mgm_tj(MK, M.tail); M.ncs = (L.n + M.TJ - 1) / M.TJ;
-            const bool sides = M.code[2] != PYROHIP_BC_PERIODIC && M.ncs >= 3 && m->march_side > 1.0 &&
-                               row0 == 1 && row1 == L.n;
-            auto chunks = [&](int rows, int least, int &cr) {   // chunks of about `rows` rows -> count
-                cr = rows < least ? least : rows;
-                if (M.tail) cr += cr & 1;                     // whole coarse rows
-                return (nrows + cr - 1) / cr;
-            };
-            M.nchunks_side = 0; M.CR_side = 0;
-            for (int nch = slots / M.ncs > 2 ? slots / M.ncs : 2; nch >= 2; nch--) {
-                M.nchunks = chunks((nrows + pad + nch - 1) / nch, m->march_minrows, M.CR);
-                if (!sides) break;
-                // a wavefront of a side strip needs march_side times as long per row: fewer rows
-                const int steps = M.CR + 6 * MK;              // apron below and above, 2K steps to drain
-                M.nchunks_side = chunks((int)(steps / m->march_side) - 6 * MK, 8, M.CR_side);
-                if ((M.ncs - 2) * M.nchunks + 2 * M.nchunks_side <= slots || nch == 2) break;
-            }
-            return mg_march_usable(M, MK);
-        };
-        bool ok = cut();
-        if (!ok && M.tail) { M.tail = 0; ok = cut(); }       // without the tail, then
-        if (!ok) break;
-        if (M.tail == 1) { M.cf = m->lev[level - 1].f; M.cfpitch = m->lev[level - 1].pitch; }
-        if (M.tail == 2) {
-            const int nb = mg_march_blocks(M);
-            PYRO_TRY(m->ctx->reduce.ensure((2 * (size_t)nb + 4) * sizeof(double)));
-            M.old = nullptr; M.partial = (double *)m->ctx->reduce.p;
-            m->diag_nb = nb; m->diag_part = M.partial;
-        }
-        PYRO_TRY(mg_march_launch(m->ctx, M, pow2, MK));
-        m->tail_done = M.tail;
-        m->n_tail[M.tail]++;
-        launches++;
-        mg_swap_solution(m, level);
-        left -= MK;
-        A.cv = nullptr; A.vin_zero = 0;
-    }
-    while (left > 0) {
-        const int K = A.single ? left : (left < kmax ? left : kmax);
-        A.K = K;
+    if (A.single) {
+        A.K = nsmooth;
         A.vin = L.v; A.vout = L.v2;
-        if (A.single) {
-            A.TI = L.n; A.TJ = L.n; A.ntj = 1; A.ntiles = 1;
-            PYRO_LAUNCH(m->ctx, "k_mg_smooth_tile", (k_mg_smooth_tile<256, 0>), dim3(1), dim3(256),
-                        MGS_LDS, A);
-        } else {
-            A.TI = MGW_RI - 4 * K; A.TJ = MGW_LP - 4 * K;
-            A.ntj = (L.n + A.TJ - 1) / A.TJ;
-            // Small levels: a launch lasts as long as ONE workgroup needs for its
-            // region (2K sweeps over up to 64 x 128 cells on one CU), while most of
-            // the 256 CUs idle.  Shorter tiles (fewer region rows per workgroup,
-            // more workgroups) cut that latency; the extra apron rows are free here.
-            const int target = m->small_tiles >= 0 ? m->small_tiles : MG_SMALL_TILES_DEFAULT;
-            if (target > 0) {
-                const int want = (target + A.ntj - 1) / A.ntj;
-                int ti = (nrows + want - 1) / want;
-                if (ti < 4) ti = 4;
-                if (ti < A.TI) A.TI = ti;
+        A.TI = L.n; A.TJ = L.n; A.ntj = 1; A.ntiles = 1;
+        PYRO_LAUNCH(m->ctx, "k_mg_smooth_tile", (k_mg_smooth_tile<256, 0>), dim3(1), dim3(256),
+                    MGS_LDS, A);
+        double *t = L.v; L.v = L.v2; L.v2 = t;
+        if (nlaunch) *nlaunch = 1;
+        return 0;
+    }
+    for (const MGLaunch &X : P.launches) {
+        if (X.kernel == MGK_MARCH) {
+            MGMarch M;
+            M.vin = L.v; M.f = L.f; M.vout = L.v2; M.n = L.n; M.pitch = L.pitch;
+            M.xc = A.xc; M.yc = A.yc; M.denom = A.denom; M.rdenom = A.rdenom; M.kx = A.kx; M.ky = A.ky;
+            for (int s = 0; s < 4; s++) M.code[s] = A.bc.code[s];
+            M.cv = A.cv; M.cpitch = A.cpitch; M.vin_zero = A.vin_zero;
+            M.row0 = row0; M.row1 = row1;
+            M.TJ = X.TJ; M.ncs = X.ncs; M.CR = X.CR; M.nchunks = X.nchunks;
+            M.CR_side = X.CR_side; M.nchunks_side = X.nchunks_side;
+            M.tail = X.tail;
+            M.alpha = m->alpha; M.beta = m->beta; M.dx2 = L.dx * L.dx; M.rdx2 = 1.0 / M.dx2; M.small = 1.e-16;
+            M.cf = nullptr; M.cfpitch = 0; M.old = nullptr; M.partial = nullptr;
+            if (M.tail == 1) { M.cf = m->lev[level - 1].f; M.cfpitch = m->lev[level - 1].pitch; }
+            if (M.tail == 2) {
+                const int nb = mg_march_blocks(M);
+                PYRO_TRY(m->ctx->reduce.ensure((2 * (size_t)nb + 4) * sizeof(double)));
+                M.partial = (double *)m->ctx->reduce.p;
+                m->diag_nb = nb; m->diag_part = M.partial;
             }
-            const int nti = (nrows + A.TI - 1) / A.TI;
-            A.ntiles = nti * A.ntj;
-            // measured per V-cycle at 2048^2 / 4096^2 (tools/mg_ab.sh): band kernel up to
-            // 1024^2: 625 / 1497 us, up to 2048^2: 611 / 1485, everywhere: 615 / 1501
-            const bool band = L.n <= m->band_maxn;
-            // the band kernel: homogeneous boundaries; its EDGE instance (ghost values
-            // synthesised at the physical sides) wherever a tile can touch one
-            const bool hom = !(A.bc.val[0] || A.bc.val[1] || A.bc.val[2] || A.bc.val[3]);
-            // 0: no physical side; 1: mirror ghosts (+-own value); 2: value-0 ghosts among them
-            const bool gen_edge = m->band_genedge;
-            int edge = (A.bc.code[0] != PYROHIP_BC_PERIODIC || A.bc.code[2] != PYROHIP_BC_PERIODIC) ? 1 : 0;
-            for (int sd = 0; sd < 4; sd++)
-                if (A.bc.code[sd] == PYROHIP_BC_CONST || (edge && gen_edge)) edge = 2;
-            if (band && hom) {
+            PYRO_TRY(mg_march_launch(m->ctx, M, X.pow2, X.K));
+            m->tail_done = M.tail;
+            m->n_tail[M.tail]++;
+        } else {
+            A.K = X.K;
+            A.vin = L.v; A.vout = L.v2;
+            A.TI = X.TI; A.TJ = X.TJ; A.ntj = X.ntj; A.ntiles = X.ntiles;
+            if (X.kernel == MGK_BAND) {
                 using BandT = void (*)(MGTile);
 #define MGB_ROW(P2, E) {k_mg_smooth_band<P2, E, false, 4>, k_mg_smooth_band<P2, E, true, 4>}
                 static const BandT inst[2][3][2] = {{MGB_ROW(false, 0), MGB_ROW(false, 1), MGB_ROW(false, 2)},
                                                     {MGB_ROW(true, 0), MGB_ROW(true, 1), MGB_ROW(true, 2)}};
 #undef MGB_ROW
-                PYRO_LAUNCH(m->ctx, "k_mg_smooth_band", inst[pow2 ? 1 : 0][edge][A.cv ? 1 : 0],
+                PYRO_LAUNCH(m->ctx, "k_mg_smooth_band", inst[X.pow2 ? 1 : 0][X.edge][A.cv ? 1 : 0],
                             dim3(A.ntiles), dim3(1024), MGW_LDS, A);
             }
-            else if (pow2)
+            else if (X.pow2)
                 PYRO_LAUNCH(m->ctx, "k_mg_smooth_tile", (k_mg_smooth_tile<MGW_NT, MGW_LP, true>),
                             dim3(A.ntiles), dim3(MGW_NT), MGW_LDS, A);
             else
                 PYRO_LAUNCH(m->ctx, "k_mg_smooth_tile", (k_mg_smooth_tile<MGW_NT, MGW_LP>),
                             dim3(A.ntiles), dim3(MGW_NT), MGW_LDS, A);
-        }
 #ifndef PYRO_EMU
-        if (tracing && !A.single) {
-            long long h[32];
-            PYRO_CHECK_HIP(hipMemcpy(h, d_trace, sizeof(h), hipMemcpyDeviceToHost));
-            fprintf(stderr, "band trace n=%d K=%d tiles=%d prolong=%d: stage %lld ghosts0 %lld passes", L.n, K,
-                    A.ntiles, A.cv != nullptr, h[1] - h[0], h[2] - h[1]);
-            for (int s = 1; s <= 2 * K; s++) fprintf(stderr, " %lld", h[2 + s] - h[1 + s]);
-            fprintf(stderr, " store %lld total %lld\n", h[23] - h[2 + 2 * K], h[23] - h[0]);
-        }
+            if (A.trace) {
+                long long h[32];
+                PYRO_CHECK_HIP(hipMemcpy(h, A.trace, sizeof(h), hipMemcpyDeviceToHost));
+                fprintf(stderr, "band trace n=%d K=%d tiles=%d prolong=%d: stage %lld ghosts0 %lld passes", L.n, X.K,
+                        A.ntiles, A.cv != nullptr, h[1] - h[0], h[2] - h[1]);
+                for (int s = 1; s <= 2 * X.K; s++) fprintf(stderr, " %lld", h[2 + s] - h[1 + s]);
+                fprintf(stderr, " store %lld total %lld\n", h[23] - h[2 + 2 * X.K], h[23] - h[0]);
+            }
 #endif
-        if (A.single) { double *t = L.v; L.v = L.v2; L.v2 = t; }
-        else mg_swap_solution(m, level);
-        launches++;
-        left -= K;
+        }
+        mg_swap_solution(m, level);
         A.cv = nullptr;   // only the first launch carries the prolongation
         A.vin_zero = 0;
     }
-    if (nlaunch) *nlaunch = launches;
+    if (nlaunch) *nlaunch = (int)P.launches.size();
     return 0;
 }
 
@@ -2383,7 +2492,7 @@ static int mg_smooth(pyrohip_mg *m, int level, int nsmooth, bool corners = true,
             }
         return 0;
     }
-    if (m->smoother == 0 || nsmooth <= 0) {
+    if (m->smoother == 0 || nsmooth <= 0) {              // (MGR_COLOURS; nothing to smooth)
         PYRO_TRY(mg_fill(m, level, 0));                   // MG.py:565
         return nsmooth > 0 ? mg_smooth_colour_launches(m, level, nsmooth) : 0;
     }
@@ -2462,11 +2571,7 @@ static int mg_sumsq(pyrohip_mg *m, const double *a, const double *b, int level, 
 {
     pyrohip_ctx *c = m->ctx;
     MGLevel &L = m->lev[level];
-    // ~2048 workgroups on the large levels, as many across as a row has pieces of 256 columns
-    // (512 workgroups with long dependent sums: 84 us for the 4096^2 level, 1.6 TB/s)
-    const int gx = L.n >= 4096 ? 16 : (L.n >= 256 ? L.n / 256 : 1);
-    const int gy = L.n >= 64 ? (2048 / gx < L.n ? 2048 / gx : L.n) : 1;
-    dim3 grid(gx, gy), block(256);
+    const dim3 grid = mg_sum_grid(L.n, L.n), block(256);
     const int nb = grid.x * grid.y;
     PYRO_TRY(c->reduce.ensure((nb + 2) * sizeof(double)));
     double *part = (double *)c->reduce.p;
@@ -2484,16 +2589,8 @@ static int mg_sumsq(pyrohip_mg *m, const double *a, const double *b, int level, 
 
 static int mg_coarse_vcycle(pyrohip_mg *m, int top)
 {
-#ifndef PYRO_EMU
-    static bool attr_set = false;
-    if (!attr_set) {
-        PYRO_CHECK_HIP(hipFuncSetAttribute((const void *)k_mg_coarse_vcycle,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)MGC_LDS));
-        attr_set = true;
-    }
-#endif
     MGCoarse A;
+    PYRO_TRY(mg_launch_setup(m, &A.trace));
     for (int l = 0; l <= MGC_TOP; l++) {
         MGLevel &L = m->lev[l <= top ? l : top];
         A.v[l] = L.v; A.f[l] = L.f; A.r[l] = L.r; A.pitch[l] = L.pitch; A.dx[l] = L.dx;
@@ -2509,21 +2606,12 @@ static int mg_coarse_vcycle(pyrohip_mg *m, int top)
     for (int l = 0; l <= top; l++)
         if (m->v_is_zero[l]) { A.zero_mask |= 1u << l; m->v_is_zero[l] = false; }
     A.bc = make_bc(m, top, true);
-    A.trace = nullptr;
-#ifndef PYRO_EMU
-    const bool tracing = m->trace;
-    static long long *d_trace = nullptr;
-    if (tracing) {
-        if (!d_trace) PYRO_CHECK_HIP(hipMalloc((void **)&d_trace, 16 * sizeof(long long)));
-        A.trace = d_trace;
-    }
-#endif
     PYRO_LAUNCH(m->ctx, "k_mg_coarse_vcycle", k_mg_coarse_vcycle, dim3(1), dim3(MGC_NT), MGC_LDS,
                 A);
 #ifndef PYRO_EMU
-    if (tracing) {
+    if (A.trace) {
         long long h[16];
-        PYRO_CHECK_HIP(hipMemcpy(h, d_trace, sizeof(h), hipMemcpyDeviceToHost));
+        PYRO_CHECK_HIP(hipMemcpy(h, A.trace, sizeof(h), hipMemcpyDeviceToHost));
         fprintf(stderr, "mgc trace (cycles): stage %lld | down", h[1] - h[0]);
         for (int k = 2; k < 2 + top; k++) fprintf(stderr, " %lld", h[k] - h[k - 1]);
         fprintf(stderr, " | bottom %lld | up", h[8] - h[1 + top]);
@@ -2537,8 +2625,8 @@ static int mg_coarse_vcycle(pyrohip_mg *m, int top)
 
 static int mg_vcycle(pyrohip_mg *m, int level)
 {
-    if (!m->vc && m->smoother != 0 && m->coarse_kernel && level <= MGC_TOP)
-        return mg_coarse_vcycle(m, level);
+    const MGPlan P = mg_leg_plan(m, level);
+    if (P.route == MGR_COARSE_KERNEL) return mg_coarse_vcycle(m, level);
     if (level > 0) {
         // inside solve() nobody reads r: residual and restriction ride on the smoothing launch
         const bool no_r = m->lazy_r && m->in_solve;
@@ -2561,7 +2649,7 @@ static int mg_vcycle(pyrohip_mg *m, int level)
             PYRO_TRY(mg_restrict(m, level));              // :731-732
         }
         PYRO_TRY(mg_vcycle(m, level - 1));                // :735
-        const bool fuse = mg_prolong_fusable(m, level, m->nsmooth);
+        const bool fuse = P.fuses_prolong;
         if (!fuse) PYRO_TRY(mg_prolong_add(m, level));    // :745-748 (else: while staging below)
         if (m->smoother == 0 || m->vc) PYRO_TRY(mg_fill(m, level, 0));   // :751 (tile smoother: on load)
         const bool diag = m->diag_req && level == m->nlevels - 1;
@@ -2670,7 +2758,7 @@ int pyrohip_mg_set_helmholtz(pyrohip_mg *m, double alpha, double beta)
 int pyrohip_mg_get_tuning(pyrohip_mg *m, pyrohip_mg_tuning *t)
 {
     PYRO_REQUIRE(m && t, "NULL argument");
-    t->kmax = m->kmax; t->kmax_small = m->kmax_small_tuned; t->nsmall = m->nsmall;
+    t->kmax = m->kmax; t->kmax_small = m->kmax_small; t->nsmall = m->nsmall;
     t->march_min = m->march_min; t->march_waves = m->march_waves; t->march_side = m->march_side;
     t->march_minrows = m->march_minrows; t->fuse_res_restrict = m->fuse_res_restrict;
     t->lazy_residual = m->lazy_r ? 1 : 0; t->allow_pow2 = m->allow_pow2 ? 1 : 0;
@@ -2687,8 +2775,7 @@ int pyrohip_mg_set_tuning(pyrohip_mg *m, const pyrohip_mg_tuning *t)
     PYRO_REQUIRE(t->kmax >= 1 && t->kmax <= MGW_KMAX, "kmax: 1..5 iterations per tile launch");
     PYRO_REQUIRE(t->kmax_small >= 0 && t->kmax_small <= 10, "kmax_small: 0..10");
     PYRO_REQUIRE(t->speculate >= 0 && t->speculate <= 2, "speculate: 0, 1 or 2");
-    m->kmax = t->kmax; m->kmax_small_tuned = t->kmax_small; m->nsmall = t->nsmall;
-    if (m->kmax_small != 0) m->kmax_small = t->kmax_small;      // (0: switched off by set_smoother)
+    m->kmax = t->kmax; m->kmax_small = t->kmax_small; m->nsmall = t->nsmall;
     m->march_min = t->march_min; m->march_waves = t->march_waves; m->march_side = t->march_side;
     m->march_minrows = t->march_minrows; m->fuse_res_restrict = t->fuse_res_restrict;
     m->lazy_r = t->lazy_residual != 0; m->allow_pow2 = t->allow_pow2 != 0;
@@ -2713,9 +2800,10 @@ int pyrohip_mg_set_smoother(pyrohip_mg *m, int kind)
     PYRO_REQUIRE(kind >= 0 && kind <= 25, "smoother must be 0, 1, 10+kmax or 20+kmax");
     // 10 + k selects the tile smoother with k fused iterations (tuning knob)
     // 20 + k: the same without the single-workgroup coarse V-cycle kernel
+    // ... and without the deeper fusion on the small levels
     m->coarse_kernel = 1;
-    m->kmax_small = m->kmax_small_tuned;
-    if (kind >= 20) { m->smoother = 1; m->kmax = kind - 20; m->coarse_kernel = 0; m->kmax_small = 0; }
+    m->small_fusion = kind < 20;
+    if (kind >= 20) { m->smoother = 1; m->kmax = kind - 20; m->coarse_kernel = 0; }
     else if (kind >= 10) { m->smoother = 1; m->kmax = kind - 10; }
     else m->smoother = kind;
     return 0;
@@ -2829,16 +2917,7 @@ int pyrohip_mg_rows_kmax(pyrohip_mg *m, int level, int *k)
 {
     MG_CHECK_LEVEL(m, level);
     PYRO_REQUIRE(k, "NULL argument");
-    const MGLevel &L = m->lev[level];
-    // ten iterations (a whole V-cycle leg) in one launch: the row-marching kernel on the
-    // large levels, the band kernel with its deep apron on the small ones; five in between
-    const bool hom = !(level == m->nlevels - 1 && (m->bcval[0] || m->bcval[1] || m->bcval[2] || m->bcval[3]));
-    bool cst = false;
-    for (int s = 0; s < 4; s++) cst = cst || m->bc[s] == PYROHIP_BC_CONST;
-    const bool march = hom && !cst && m->march_min > 0 && L.n >= m->march_min && L.n >= 2 * MGM_COLS &&
-                       m->bc[0] != PYROHIP_BC_PERIODIC;
-    const bool small10 = L.n <= m->nsmall && m->kmax_small_tuned >= 10;
-    *k = (m->vc || m->smoother == 0) ? 0 : ((march || small10) ? 10 : MGW_KMAX);
+    *k = mg_leg_plan(m, level).rows_k;
     return 0;
 }
 
@@ -2857,13 +2936,8 @@ int pyrohip_mg_smooth_rows(pyrohip_mg *m, int level, int nsweeps, int row0, int 
     PYRO_REQUIRE(!prolong || level > 0, "no coarser level to prolong from");
     // exactly `nsweeps` iterations in ONE launch (no halo exchange could happen between
     // two launches of a split call): the tuning values do not apply to row windows
-    const int ks = m->kmax_small, km = m->kmax;
-    m->kmax_small = nsweeps > MGW_KMAX ? nsweeps : 0;
-    m->kmax = nsweeps > MGW_KMAX ? MGW_KMAX : nsweeps;
     int nl = 0;
-    const int rc = mg_smooth_tiles(m, level, nsweeps, prolong != 0, row0, row1, &nl);
-    m->kmax_small = ks;
-    m->kmax = km;
+    const int rc = mg_smooth_tiles(m, level, nsweeps, prolong != 0, row0, row1, &nl, 0, nsweeps);
     PYRO_REQUIRE(rc != 0 || nl == 1, "the window is too short for one launch of that many iterations");
     m->corners_stale[level] = true;
     PYRO_CHECK_HIP(hipGetLastError());
@@ -2883,9 +2957,7 @@ int pyrohip_mg_diag_rows(pyrohip_mg *m, int row0, int row1, double *sums)
     MGLevel &F = m->lev[Lf];
     PYRO_REQUIRE(row0 >= 1 && row1 <= F.n && row0 <= row1, "rows outside the level");
     const int nrows = row1 - row0 + 1;
-    const int gx = F.n >= 4096 ? 16 : (F.n >= 256 ? F.n / 256 : 1);
-    const int gy = nrows >= 64 ? (2048 / gx < nrows ? 2048 / gx : nrows) : 1;
-    const dim3 grid(gx, gy), block(256);
+    const dim3 grid = mg_sum_grid(F.n, nrows), block(256);
     const int nb = grid.x * grid.y;
     PYRO_TRY(c->reduce.ensure((2 * nb + 4) * sizeof(double)));
     double *part = (double *)c->reduce.p;
@@ -2972,10 +3044,7 @@ int pyrohip_mg_set_rows(pyrohip_mg *m, int level, int var, int i0, int ni, const
 int pyrohip_mg_mark_zero(pyrohip_mg *m, int level)
 {
     MG_CHECK_LEVEL(m, level);
-    MGLevel &L = m->lev[level];
-    if (!m->vc && m->smoother != 0 && m->nsmooth > 0 &&
-        ((L.n + 2) * (L.n + 2) > MGS_CELLS || (m->coarse_kernel && level <= MGC_TOP)))
-        m->v_is_zero[level] = true;
+    if (mg_leg_plan(m, level).loads_zero) m->v_is_zero[level] = true;
     else
         PYRO_TRY(mg_zero(m, level, 0));
     return 0;
@@ -3133,13 +3202,12 @@ int pyrohip_mg_solve(pyrohip_mg *m, double rtol, int max_cycles, int *num_cycles
     // the solution before the first cycle, for its relative change -- unless the cycle's first
     // smoothing launch leaves it behind anyway (capture_old: the finest level's launches read
     // one buffer and write another; 87 us of copy per solve at 4096^2)
-    const bool first_launch_keeps_old = !m->vc && m->smoother != 0 && m->nsmooth > 0 && Lf > MGC_TOP &&
-                                        (F.n + 2) * (F.n + 2) > MGS_CELLS;
+    const MGPlan PF = mg_leg_plan(m, Lf);
+    const bool first_launch_keeps_old = PF.pingpong;
     if (!first_launch_keeps_old)
         PYRO_CHECK_HIP(hipMemcpyAsync(m->old_phi, F.v, fbytes, hipMemcpyDeviceToDevice, c->stream));
     // (the fourth buffer: wherever a cycle's sums may ride on the marching launch)
-    if (first_launch_keeps_old && m->lazy_r && m->march_tail && m->march_min > 0 && F.n >= m->march_min &&
-        !m->older) {
+    if (m->lazy_r && (PF.can_tail & 2) && !m->older) {
         const Geom gf = make_geom(F.n, F.n, 1);
         PYRO_CHECK_HIP(hipMalloc((void **)&m->older_base, (gf.plane + 16) * sizeof(double)));
         PYRO_CHECK_HIP(hipMemsetAsync(m->older_base, 0, (gf.plane + 16) * sizeof(double), c->stream));
@@ -3154,11 +3222,7 @@ int pyrohip_mg_solve(pyrohip_mg *m, double rtol, int max_cycles, int *num_cycles
         for (int l = 0; l < Lf; l++) {                    // :658-659 (zero the coarse solutions)
             // levels the wide tile smoother visits first: no memset (hipMemset runs
             // at ~270 GB/s: 123 us for the 2048^2 level), the staging takes v = 0
-            const MGLevel &Lc = m->lev[l];
-            const bool lazy = !m->vc && m->smoother != 0 && m->nsmooth > 0 &&
-                              ((Lc.n + 2) * (Lc.n + 2) > MGS_CELLS ||
-                               (m->coarse_kernel && l <= MGC_TOP));   // staged as 0 there
-            if (lazy) m->v_is_zero[l] = true;
+            if (mg_leg_plan(m, l).loads_zero) m->v_is_zero[l] = true;   // staged as 0 there
             else PYRO_TRY(mg_zero(m, l, 0));
         }
         m->in_solve = true;
@@ -3183,11 +3247,7 @@ int pyrohip_mg_solve(pyrohip_mg *m, double rtol, int max_cycles, int *num_cycles
             return 0;
         }
         // fused: relative change, old <- v (unless captured), residual and its norm in one pass
-        // a workgroup covers 256 columns of a row: as many workgroups across as the row has such
-        // pieces (16 across on a 2048^2 level left half of them idle: 31 -> 21 us), ~2048 in all
-        const int gx = F.n >= 4096 ? 16 : (F.n >= 256 ? F.n / 256 : 1);
-        const int gy = F.n >= 64 ? (2048 / gx < F.n ? 2048 / gx : F.n) : 1;
-        const dim3 grid(gx, gy), block(256);
+        const dim3 grid = mg_sum_grid(F.n, F.n), block(256);
         const int nb = m->diag_done ? m->diag_nb : grid.x * grid.y;
         PYRO_TRY(c->reduce.ensure((2 * nb + 4) * sizeof(double)));
         double *part = (double *)c->reduce.p;

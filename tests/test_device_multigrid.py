@@ -790,3 +790,308 @@ def test_mg_solve_speculation_with_tails(dev, nx):
                 assert a == b, spec
             else:
                 assert np.array_equal(a, b), spec
+
+
+# ---- which kernel smooths a level, and with how many launches ---------------------------------
+_D4, _P4 = ("dirichlet",) * 4, ("periodic",) * 4
+_MIX = ("neumann", "dirichlet", "periodic", "periodic")
+_LID = ("dirichlet", "dirichlet", "dirichlet", "moving_lid")       # one side with the constant-value code
+_MARCH = dict(march_min=256, march_waves=24)                       # the marching kernel on a 256^2 level
+_S7, _S10, _S20, _VC, _Z0, _Z2 = "smooth7", "smooth10", "smooth20", "vcycle", "solve_spec0", "solve_spec2"
+_ALL = (_S7, _S10, _S20, _VC, _Z0, _Z2)
+# name -> (nx, boundaries, tuning on top of nsmall=128, set_smoother kind or None, extra, calls).
+# (Every call on the cheap configurations; on the 256^2 ones, which the emulator takes a second
+# per V-cycle for, the calls whose launches that configuration decides differently.)
+_PLAN_CASES = {
+    "d64": (64, _D4, {}, None, None, _ALL),
+    "d128": (128, _D4, dict(march_min=0), None, None, (_S7, _S10, _S20, _VC, _Z0)),
+    "d128_k25": (128, _D4, dict(march_min=0), 25, None, (_S7, _S10, _VC, _Z2)),
+    "p128": (128, _P4, dict(march_min=0), None, None, (_S7, _S10, _S20, _VC)),
+    "mix128": (128, _MIX, dict(march_min=0), None, None, (_S7, _S10, _S20, _VC)),
+    "lid128": (128, _LID, dict(march_min=0), None, None, (_S7, _S10, _S20, _VC)),
+    "d256": (256, _D4, dict(march_min=0), None, None, (_S7, _S10, _VC)),
+    "p256": (256, _P4, dict(march_min=0), None, None, (_S10, _VC)),
+    "mix256": (256, _MIX, dict(march_min=0), None, None, (_S7, _VC)),
+    "d256_march": (256, _D4, _MARCH, None, None, (_S7, _S10, _S20, _VC, _Z2)),
+    "d256_march_notail": (256, _D4, dict(_MARCH, march_tail=0), None, None, (_VC, _Z0)),
+    "d256_march_eager": (256, _D4, dict(_MARCH, lazy_residual=0), None, None, (_Z0,)),
+    "d256_march_k0": (256, _D4, _MARCH, 0, None, _ALL),
+    "d256_march_k1": (256, _D4, _MARCH, 1, None, (_S7, _S10)),
+    "d256_march_k13": (256, _D4, _MARCH, 13, None, (_S7, _S20, _VC)),
+    "d256_march_k25": (256, _D4, _MARCH, 25, None, (_S7, _VC)),
+    "p256_march": (256, _P4, _MARCH, None, None, (_S10, _S20, _Z2)),
+    "mix256_march": (256, _MIX, _MARCH, None, None, (_S10, _Z0)),
+    "bcval256_march": (256, _D4, _MARCH, None, "bcval", (_S7, _Z2)),
+    "lid256_march": (256, _LID, _MARCH, None, None, (_S10, _S20)),
+    "vc128": (128, _D4, dict(march_min=0), None, "coeffs", _ALL),
+    "vc256_march": (256, _D4, _MARCH, None, "coeffs", _ALL),
+}
+
+
+def _plan_observe(dev, name):
+    """what the launch decisions of one configuration look like from outside: the kernels and
+    launch counts of each call, the marching launches that carried a tail, rows_kmax of every
+    level, and the kernel a whole-level row window of that many iterations goes to"""
+    nx, bcs, tun, kind, extra, calls = _PLAN_CASES[name]
+    rng = np.random.default_rng(nx)
+    v0 = rng.standard_normal((nx + 2, nx + 2))
+    f0 = rng.standard_normal((nx + 2, nx + 2))
+    alpha, beta = (0.3, -1.1) if bcs == _P4 else (0.0, -1.0)
+    m = device.DeviceMG(dev, nx, bcs=bcs, alpha=alpha, beta=beta, tuning=dict(nsmall=128, **tun))
+    L = m.nlevels - 1
+    if kind is not None:
+        m.set_smoother(kind)
+    if extra == "bcval":
+        m.set_bcval(0, np.linspace(0.5, 1.5, nx + 2))
+    if extra == "coeffs":
+        x = (np.arange(nx + 2) - 0.5) / nx
+        m.set_coeffs(2.0 + np.cos(2 * np.pi * x)[:, None] * np.cos(2 * np.pi * x)[None, :], ("neumann",) * 4)
+
+    def launches():
+        return {k: n for k, (n, _) in dev.prof_report().items()}
+    seen = {}
+    dev.prof_report()
+    dev.prof_enable(True)
+    try:
+        for call in calls:
+            if call.startswith("smooth") or call == _VC:
+                m.set(L, 0, v0)
+                m.set(L, 1, f0)
+                if call == _VC:
+                    m.vcycle()
+                else:
+                    m.smooth(L, int(call[6:]))
+            else:
+                m.set_tuning(speculate=int(call[-1]))
+                m.zero(L, 0)
+                m.set(L, 1, f0)
+                m.init_rhs_norm()
+                nc, _, _ = m.solve(rtol=1e-11, max_cycles=4)
+                assert nc == 4                      # (so that the counts do not hang on the data)
+            seen[call] = launches()
+        seen["tails"] = m.tail_counts()
+        seen["rows_kmax"] = [m.rows_kmax(l) for l in range(m.nlevels)]
+        # row windows (levels above 64^2): that many iterations in ONE launch, tuning untouched
+        rows = {}
+        for l in range(m.nlevels):
+            k, n = seen["rows_kmax"][l], 2 ** (l + 1)
+            if k > 0 and n > 64:
+                before = m.get_tuning()
+                m.smooth_rows(l, k, 1, n)
+                assert m.get_tuning() == before, (name, l)
+                rep = launches()
+                assert list(rep.values()) == [1], (name, l, rep)
+                rows[n] = next(iter(rep))
+        seen["rows"] = rows
+    finally:
+        dev.prof_enable(False)
+        dev.prof_report()
+    return seen
+
+
+# recorded from the commit BEFORE the launch decisions moved into mg_plan (csrc/multigrid.hip)
+_PLAN_EXPECTED = {'bcval256_march': {'rows': {128: 'k_mg_smooth_band', 256: 'k_mg_smooth_tile'},
+                    'rows_kmax': [10, 10, 10, 10, 10, 10, 10, 5],
+                    'smooth7': {'k_mg_smooth_tile': 2},
+                    'solve_spec2': {'k_mg_coarse_vcycle': 4,
+                                    'k_mg_residual_restrict': 8,
+                                    'k_mg_smooth_band': 8,
+                                    'k_mg_smooth_tile': 16,
+                                    'k_mg_solve_diag': 4},
+                    'tails': (0, 0)},
+ 'd128': {'rows': {128: 'k_mg_smooth_band'},
+          'rows_kmax': [10, 10, 10, 10, 10, 10, 10],
+          'smooth10': {'k_mg_smooth_band': 1},
+          'smooth20': {'k_mg_smooth_band': 2},
+          'smooth7': {'k_mg_smooth_band': 1},
+          'solve_spec0': {'k_mg_coarse_vcycle': 4,
+                          'k_mg_residual_restrict': 4,
+                          'k_mg_smooth_band': 8,
+                          'k_mg_solve_diag': 4},
+          'tails': (0, 0),
+          'vcycle': {'k_mg_coarse_vcycle': 1, 'k_mg_residual_restrict': 1, 'k_mg_smooth_band': 2}},
+ 'd128_k25': {'rows': {128: 'k_mg_smooth_band'},
+              'rows_kmax': [10, 10, 10, 10, 10, 10, 10],
+              'smooth10': {'k_mg_smooth_band': 2},
+              'smooth7': {'k_mg_smooth_band': 2},
+              'solve_spec2': {'k_mg_prolong_add': 20,
+                              'k_mg_residual_restrict': 24,
+                              'k_mg_smooth_band': 16,
+                              'k_mg_smooth_tile': 44,
+                              'k_mg_solve_diag': 4},
+              'tails': (0, 0),
+              'vcycle': {'k_mg_prolong_add': 5,
+                         'k_mg_residual_restrict': 6,
+                         'k_mg_smooth_band': 4,
+                         'k_mg_smooth_tile': 11}},
+ 'd256': {'rows': {128: 'k_mg_smooth_band', 256: 'k_mg_smooth_band'},
+          'rows_kmax': [10, 10, 10, 10, 10, 10, 10, 5],
+          'smooth10': {'k_mg_smooth_band': 2},
+          'smooth7': {'k_mg_smooth_band': 2},
+          'tails': (0, 0),
+          'vcycle': {'k_mg_coarse_vcycle': 1, 'k_mg_residual_restrict': 2, 'k_mg_smooth_band': 6}},
+ 'd256_march': {'rows': {128: 'k_mg_smooth_band', 256: 'k_mg_smooth_march'},
+                'rows_kmax': [10, 10, 10, 10, 10, 10, 10, 10],
+                'smooth10': {'k_mg_smooth_march': 1},
+                'smooth20': {'k_mg_smooth_march': 2},
+                'smooth7': {'k_mg_smooth_band': 2},
+                'solve_spec2': {'k_mg_coarse_vcycle': 4,
+                                'k_mg_residual_restrict': 4,
+                                'k_mg_smooth_band': 8,
+                                'k_mg_smooth_march': 8},
+                'tails': (4, 4),
+                'vcycle': {'k_mg_coarse_vcycle': 1,
+                           'k_mg_residual_restrict': 2,
+                           'k_mg_smooth_band': 2,
+                           'k_mg_smooth_march': 2}},
+ 'd256_march_eager': {'rows': {128: 'k_mg_smooth_band', 256: 'k_mg_smooth_march'},
+                      'rows_kmax': [10, 10, 10, 10, 10, 10, 10, 10],
+                      'solve_spec0': {'k_mg_coarse_vcycle': 4,
+                                      'k_mg_residual_restrict': 8,
+                                      'k_mg_smooth_band': 8,
+                                      'k_mg_smooth_march': 8,
+                                      'k_mg_solve_diag': 4},
+                      'tails': (0, 0)},
+ 'd256_march_k0': {'rows': {},
+                   'rows_kmax': [0, 0, 0, 0, 0, 0, 0, 0],
+                   'smooth10': {'k_mg_smooth': 20},
+                   'smooth20': {'k_mg_smooth': 40},
+                   'smooth7': {'k_mg_smooth': 14},
+                   'solve_spec0': {'k_mg_prolong_add': 28,
+                                   'k_mg_residual_restrict': 28,
+                                   'k_mg_smooth': 1520,
+                                   'k_mg_solve_diag': 4},
+                   'solve_spec2': {'k_mg_prolong_add': 28,
+                                   'k_mg_residual_restrict': 28,
+                                   'k_mg_smooth': 1520,
+                                   'k_mg_solve_diag': 4},
+                   'tails': (0, 0),
+                   'vcycle': {'k_mg_prolong_add': 7, 'k_mg_residual_restrict': 7, 'k_mg_smooth': 380}},
+ 'd256_march_k1': {'rows': {128: 'k_mg_smooth_band', 256: 'k_mg_smooth_march'},
+                   'rows_kmax': [10, 10, 10, 10, 10, 10, 10, 10],
+                   'smooth10': {'k_mg_smooth_march': 1},
+                   'smooth7': {'k_mg_smooth_band': 2},
+                   'tails': (0, 0)},
+ 'd256_march_k13': {'rows': {128: 'k_mg_smooth_band', 256: 'k_mg_smooth_march'},
+                    'rows_kmax': [10, 10, 10, 10, 10, 10, 10, 10],
+                    'smooth20': {'k_mg_smooth_march': 2},
+                    'smooth7': {'k_mg_smooth_band': 3},
+                    'tails': (0, 0),
+                    'vcycle': {'k_mg_coarse_vcycle': 1,
+                               'k_mg_residual_restrict': 2,
+                               'k_mg_smooth_band': 2,
+                               'k_mg_smooth_march': 2}},
+ 'd256_march_k25': {'rows': {128: 'k_mg_smooth_band', 256: 'k_mg_smooth_march'},
+                    'rows_kmax': [10, 10, 10, 10, 10, 10, 10, 10],
+                    'smooth7': {'k_mg_smooth_band': 2},
+                    'tails': (0, 0),
+                    'vcycle': {'k_mg_prolong_add': 5,
+                               'k_mg_residual_restrict': 7,
+                               'k_mg_smooth_band': 4,
+                               'k_mg_smooth_march': 2,
+                               'k_mg_smooth_tile': 11}},
+ 'd256_march_notail': {'rows': {128: 'k_mg_smooth_band', 256: 'k_mg_smooth_march'},
+                       'rows_kmax': [10, 10, 10, 10, 10, 10, 10, 10],
+                       'solve_spec0': {'k_mg_coarse_vcycle': 4,
+                                       'k_mg_residual_restrict': 8,
+                                       'k_mg_smooth_band': 8,
+                                       'k_mg_smooth_march': 8,
+                                       'k_mg_solve_diag': 4},
+                       'tails': (0, 0),
+                       'vcycle': {'k_mg_coarse_vcycle': 1,
+                                  'k_mg_residual_restrict': 2,
+                                  'k_mg_smooth_band': 2,
+                                  'k_mg_smooth_march': 2}},
+ 'd64': {'rows': {},
+         'rows_kmax': [10, 10, 10, 10, 10, 10],
+         'smooth10': {'k_mg_smooth_tile': 1},
+         'smooth20': {'k_mg_smooth_tile': 1},
+         'smooth7': {'k_mg_smooth_tile': 1},
+         'solve_spec0': {'k_mg_coarse_vcycle': 4, 'k_mg_solve_diag': 4},
+         'solve_spec2': {'k_mg_coarse_vcycle': 4, 'k_mg_solve_diag': 4},
+         'tails': (0, 0),
+         'vcycle': {'k_mg_coarse_vcycle': 1}},
+ 'lid128': {'rows': {128: 'k_mg_smooth_band'},
+            'rows_kmax': [10, 10, 10, 10, 10, 10, 10],
+            'smooth10': {'k_mg_smooth_band': 1},
+            'smooth20': {'k_mg_smooth_band': 2},
+            'smooth7': {'k_mg_smooth_band': 1},
+            'tails': (0, 0),
+            'vcycle': {'k_mg_coarse_vcycle': 1, 'k_mg_residual_restrict': 1, 'k_mg_smooth_band': 2}},
+ 'lid256_march': {'rows': {128: 'k_mg_smooth_band', 256: 'k_mg_smooth_band'},
+                  'rows_kmax': [10, 10, 10, 10, 10, 10, 10, 5],
+                  'smooth10': {'k_mg_smooth_band': 2},
+                  'smooth20': {'k_mg_smooth_band': 4},
+                  'tails': (0, 0)},
+ 'mix128': {'rows': {128: 'k_mg_smooth_band'},
+            'rows_kmax': [10, 10, 10, 10, 10, 10, 10],
+            'smooth10': {'k_mg_smooth_band': 1},
+            'smooth20': {'k_mg_smooth_band': 2},
+            'smooth7': {'k_mg_smooth_band': 1},
+            'tails': (0, 0),
+            'vcycle': {'k_mg_coarse_vcycle': 1, 'k_mg_residual_restrict': 1, 'k_mg_smooth_band': 2}},
+ 'mix256': {'rows': {128: 'k_mg_smooth_band', 256: 'k_mg_smooth_band'},
+            'rows_kmax': [10, 10, 10, 10, 10, 10, 10, 5],
+            'smooth7': {'k_mg_smooth_band': 2},
+            'tails': (0, 0),
+            'vcycle': {'k_mg_coarse_vcycle': 1, 'k_mg_residual_restrict': 2, 'k_mg_smooth_band': 6}},
+ 'mix256_march': {'rows': {128: 'k_mg_smooth_band', 256: 'k_mg_smooth_march'},
+                  'rows_kmax': [10, 10, 10, 10, 10, 10, 10, 10],
+                  'smooth10': {'k_mg_smooth_march': 1},
+                  'solve_spec0': {'k_mg_coarse_vcycle': 4,
+                                  'k_mg_residual_restrict': 4,
+                                  'k_mg_smooth_band': 8,
+                                  'k_mg_smooth_march': 8},
+                  'tails': (4, 4)},
+ 'p128': {'rows': {128: 'k_mg_smooth_band'},
+          'rows_kmax': [10, 10, 10, 10, 10, 10, 10],
+          'smooth10': {'k_mg_smooth_band': 1},
+          'smooth20': {'k_mg_smooth_band': 2},
+          'smooth7': {'k_mg_smooth_band': 1},
+          'tails': (0, 0),
+          'vcycle': {'k_mg_coarse_vcycle': 1, 'k_mg_residual_restrict': 1, 'k_mg_smooth_band': 2}},
+ 'p256': {'rows': {128: 'k_mg_smooth_band', 256: 'k_mg_smooth_band'},
+          'rows_kmax': [10, 10, 10, 10, 10, 10, 10, 5],
+          'smooth10': {'k_mg_smooth_band': 2},
+          'tails': (0, 0),
+          'vcycle': {'k_mg_coarse_vcycle': 1, 'k_mg_residual_restrict': 2, 'k_mg_smooth_band': 6}},
+ 'p256_march': {'rows': {128: 'k_mg_smooth_band', 256: 'k_mg_smooth_band'},
+                'rows_kmax': [10, 10, 10, 10, 10, 10, 10, 5],
+                'smooth10': {'k_mg_smooth_march': 1},
+                'smooth20': {'k_mg_smooth_march': 2},
+                'solve_spec2': {'k_mg_coarse_vcycle': 4,
+                                'k_mg_residual_restrict': 4,
+                                'k_mg_smooth_band': 8,
+                                'k_mg_smooth_march': 8},
+                'tails': (4, 4)},
+ 'vc128': {'rows': {},
+           'rows_kmax': [0, 0, 0, 0, 0, 0, 0],
+           'smooth10': {'k_vc_smooth': 20},
+           'smooth20': {'k_vc_smooth': 40},
+           'smooth7': {'k_vc_smooth': 14},
+           'solve_spec0': {'k_mg_prolong_add': 24, 'k_mg_restrict': 24, 'k_vc_smooth': 1360},
+           'solve_spec2': {'k_mg_prolong_add': 24, 'k_mg_restrict': 24, 'k_vc_smooth': 1360},
+           'tails': (0, 0),
+           'vcycle': {'k_mg_prolong_add': 6, 'k_mg_restrict': 6, 'k_vc_smooth': 340}},
+ 'vc256_march': {'rows': {},
+                 'rows_kmax': [0, 0, 0, 0, 0, 0, 0, 0],
+                 'smooth10': {'k_vc_smooth': 20},
+                 'smooth20': {'k_vc_smooth': 40},
+                 'smooth7': {'k_vc_smooth': 14},
+                 'solve_spec0': {'k_mg_prolong_add': 28, 'k_mg_restrict': 28, 'k_vc_smooth': 1520},
+                 'solve_spec2': {'k_mg_prolong_add': 28, 'k_mg_restrict': 28, 'k_vc_smooth': 1520},
+                 'tails': (0, 0),
+                 'vcycle': {'k_mg_prolong_add': 7, 'k_mg_restrict': 7, 'k_vc_smooth': 380}}}
+
+
+@pytest.mark.parametrize("name", sorted(_PLAN_CASES))
+def test_mg_launch_plan_pinned(dev, name):
+    """the host side decides, per level, which kernel smooths it (single tile, band, wide tile,
+    row march, coarse V-cycle kernel, colour launches), how many iterations ride on a launch and
+    what else the launch carries.  The kernels and launch counts of smooth(7 / 10 / 20), a
+    V-cycle and four-cycle solves (waiting and launching ahead), the tails carried,
+    rows_kmax() of every level and the kernel of a row window are pinned to what the code did
+    before the one-place decision (mg_plan) replaced its scattered copies: the counts are host
+    decisions, the same on every device"""
+    seen = _plan_observe(dev, name)
+    assert seen == _PLAN_EXPECTED[name]
