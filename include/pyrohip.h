@@ -843,6 +843,46 @@ int pyrohip_particles_count(pyrohip_particles *p, int *n);
 int pyrohip_particles_advance(pyrohip_particles *p, pyrohip_state *s,
                               const pyrohip_particle_params *params, double dt);
 
+/* ---- tracer particles inside the device-side stepping loops ----
+   pyrohip_comp_evolve / pyrohip_comp_rk_evolve / pyrohip_swe_evolve with a particle set that
+   rides along: behind every step that advanced the state the set is advanced over that
+   step's dt -- read from device memory -- by the three launches of
+   pyrohip_particles_advance in their run-protocol forms, with the velocity planes and the
+   ghost frame the single-step path reads (the state after the step, ghost cells = the
+   boundary fill of the state before it).  Nothing of the set visits the host during the
+   run; its error word comes back with the run's one closing read-back.  The result --
+   positions, initial positions, velocities, order, live count, and the state, t, n, dt_old
+   -- is bit-identical to max_steps x (step, pyrohip_particles_advance).  Iterations that do
+   not advance the state (past tmax, after the run has ended) leave the set alone, order
+   included.  particles NULL: exactly the call without _p (pparams is not read).
+   Single Cartesian domain: a set on a slab of a decomposed run (pyrohip_state_set_neighbours)
+   or on a SphericalPolar grid is PYROHIP_ERR_ARG.  pyrohip_comp_evolve_p runs the three
+   launches per step whatever p->step_launches says (the one-launch steps write no ghost cell);
+   pyrohip_swe_evolve_p with fast_math = 1 takes every step's CFL minimum the way pyrohip_swe_dt
+   does (the contracted step kernel's own is an ulp away) and leaves no cached minimum behind.
+   Errors, all PYROHIP_ERR_STATE with steps_done = the steps BEFORE the failing one:
+     - invalid state at step k: as without _p for the state; the set is the one after the
+       steps_done steps that advanced, in the order it then had;
+     - a particle of step k's advance whose 2 x 2 stencil leaves the array (NaN / infinite
+       positions included): the message names the particles; the state AND the set are those
+       after steps_done steps and the policy stands there.  (The single-step path leaves the
+       state advanced once more than t / n say; here they stay consistent.)              */
+int pyrohip_comp_evolve_p(pyrohip_state *s, const pyrohip_comp_params *p, double cfl,
+                          pyrohip_dt_policy *policy, int max_steps, int *steps_done,
+                          double *dts_out, pyrohip_particles *particles,
+                          const pyrohip_particle_params *pparams);
+int pyrohip_comp_rk_evolve_p(pyrohip_state *y, const pyrohip_comp_params *p,
+                             pyrohip_state *k, int nstages, const double *a,
+                             const double *b, double cfl, pyrohip_dt_policy *policy,
+                             int max_steps, int *steps_done, double *dts_out,
+                             pyrohip_particles *particles,
+                             const pyrohip_particle_params *pparams);
+int pyrohip_swe_evolve_p(pyrohip_state *s, double dx, double dy, double grav, int limiter,
+                         int riemann, int fast_math, double cfl, pyrohip_dt_policy *policy,
+                         int max_steps, int *steps_done, double *dts_out,
+                         pyrohip_particles *particles,
+                         const pyrohip_particle_params *pparams);
+
 /* ---- multi-GPU: x-slab decomposition, one process per GPU, RCCL -------- */
 #define PYROHIP_UNIQUE_ID_BYTES 128
 int pyrohip_comm_unique_id(char *out_id /* PYROHIP_UNIQUE_ID_BYTES */);

@@ -271,6 +271,12 @@ _PROTOS = {
     "pyrohip_particles_download": [_VP, _IP, _DP, _DP, _DP],
     "pyrohip_particles_count": [_VP, _IP],
     "pyrohip_particles_advance": [_VP, _VP, C.POINTER(ParticleParams), C.c_double],
+    "pyrohip_comp_evolve_p": [_VP, C.POINTER(CompParams), C.c_double, C.POINTER(DtPolicyC), C.c_int,
+                              _IP, _DP, _VP, C.POINTER(ParticleParams)],
+    "pyrohip_comp_rk_evolve_p": [_VP, C.POINTER(CompParams), _VP, C.c_int, _DP, _DP, C.c_double,
+                                 C.POINTER(DtPolicyC), C.c_int, _IP, _DP, _VP, C.POINTER(ParticleParams)],
+    "pyrohip_swe_evolve_p": [_VP, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_double,
+                             C.POINTER(DtPolicyC), C.c_int, _IP, _DP, _VP, C.POINTER(ParticleParams)],
 }
 
 EXPORTS = sorted(list(_PROTOS) + ["pyrohip_last_error", "pyrohip_backend"])

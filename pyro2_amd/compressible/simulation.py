@@ -252,11 +252,13 @@ class Simulation(NullSimulation):
 
     def can_evolve_many(self):
         """may the driver hand several steps at once to the device
-        (pyrohip_comp_evolve)?  Standard boundary types, no sponge, no tracer particles,
-        a fused kernel set, nothing watching the data (a SphericalPolar grid: its one-launch
-        step, i.e. no heating profile either)."""
+        (pyrohip_comp_evolve)?  Standard boundary types, no sponge, tracer particles only
+        where the device advances them (Cartesian grid), a fused kernel set, nothing watching
+        the data (a SphericalPolar grid: its one-launch step, i.e. no heating profile either)."""
         cc = self.cc_data
-        if self.particles is not None or self._host_source():
+        if self._host_source():
+            return False
+        if self.particles is not None and (cc.grid.coord_type != 0 or self._device_particle_source() is None):
             return False
         if cc.grid.coord_type != 0 and self._heating() is not None:
             return False
@@ -280,10 +282,10 @@ class Simulation(NullSimulation):
         """up to nsteps of fill_BC_all + compute_timestep + evolve on the device without
         a host round trip per step; the driver's dt policy (simulation_null.py:222-244)
         runs in a kernel.  Returns the time steps taken."""
-        def call(st, pol, cfl, n):
-            if self.cc_data.slab is not None:     # COLLECTIVE
+        def call(st, pol, cfl, n, particles):
+            if self.cc_data.slab is not None:     # COLLECTIVE (no tracers: setup_particles refuses them)
                 return self._slab().evolve(pol, cfl, n, params=self._params())
-            return st.comp_evolve(self._params(), cfl, pol, n)
+            return st.comp_evolve(self._params(), cfl, pol, n, particles=particles)
         # (refusable: e.g. a SphericalPolar grid too small for the tile kernel, mixed boundary
         # kinds on a side -- the staged set can step those)
         return self._evolve_by_device_policy(nsteps, self._device_state, call, refusable=True)

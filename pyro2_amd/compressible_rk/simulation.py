@@ -103,8 +103,10 @@ class Simulation(CompressibleSimulation):
 
     def can_evolve_many(self):
         """batches of steps on the device (pyrohip_comp_rk_evolve): where the one-call step runs,
-        nothing watches the data, no tracer particles"""
-        if self.particles is not None or self.cc_data._views_alive():
+        nothing watches the data, tracer particles only where the device advances them"""
+        if self.cc_data._views_alive():
+            return False
+        if self.particles is not None and self._device_particle_source() is None:
             return False
         if self.rp.get_param("sponge.do_sponge") or type(self).evolve is not Simulation.evolve:
             return False
@@ -121,6 +123,7 @@ class Simulation(CompressibleSimulation):
             self.cc_data.take_pending_fill()
             return st
         return self._evolve_by_device_policy(
-            nsteps, start, lambda st, pol, cfl, n: st.comp_rk_evolve(
-                self._params(), self._rk_scratch[1], integration.a[method], integration.b[method], cfl, pol, n),
+            nsteps, start, lambda st, pol, cfl, n, particles: st.comp_rk_evolve(
+                self._params(), self._rk_scratch[1], integration.a[method], integration.b[method], cfl, pol, n,
+                particles=particles),
             refusable=True)

@@ -441,9 +441,20 @@ struct EvolveRun {
     int cfl_kind = 0;                 // pyrohip_state::cfl_kind / cfl_par of the minimum the run leaves
     double cfl_par[3] = {0.0, 0.0, 0.0};
     bool halo_ok = false, sph_ok = false;     // what frame_fill_ok lets pass in this run
+    // the tracer particle set carried through the run (evolve_bind_particles; nullptr: none), its
+    // parameters (borrowed from the caller for the call) and its live buffer at the start
+    pyrohip_particles *ps = nullptr;
+    const pyrohip_particle_params *pp = nullptr;
+    int ps_live0 = 0;
     // the step just launched may have left its CFL partials for the next policy call (pyrohip_state::pend_part)
     void take_pending() { pend = s->pend_part; npend = s->pend_n; s->pend_part = nullptr; }
 };
+// before evolve_open: a particle set that rides along (ps == nullptr: none).  Single domain only
+int evolve_bind_particles(EvolveRun &r, pyrohip_state *s, pyrohip_particles *ps, const pyrohip_particle_params *pp,
+                          const char *fn);
+// behind the solver's step of an iteration (the state's buffers already exchanged): the bound set
+// over that step's dt (particles.hip: three launches, nothing read back); nothing without a set
+int evolve_particles(EvolveRun &r);
 // open: evolve_begin, the cached-minimum decision (global_min: on a context that reduces the CFL
 // minimum over its ranks only a global one is kept, and only if every rank kept its own), the upload
 // of r.H and the reset of the positivity flag
@@ -457,8 +468,9 @@ int evolve_policy(EvolveRun &r, int m);
 // plain fill (fill: unless the step fills itself) and the policy.  *frame_done: the other buffer's
 // ghost frame is written
 int evolve_between(EvolveRun &r, int m, bool frame, bool fill, bool *frame_done);
-// close: closing policy, the one read-back, buffer parity, the final state's ghost frame (framed: the
-// step kernels work on filled frames; one_launch: they wrote none), the cached minimum, pol, the verdict
+// close: closing policy, the one read-back (the bound set's error word with it), buffer parity of the
+// state and of the set, the final state's ghost frame (framed: the step kernels work on filled
+// frames; one_launch: they wrote none), the cached minimum, pol, the verdict
 int evolve_close(EvolveRun &r, pyrohip_dt_policy *pol, int *steps_done, double *dts_out, bool framed,
                  bool one_launch);
 // enqueue the copy of one plane (laid out like the state's) into a (qx, qy) host array; the
@@ -469,6 +481,16 @@ int plane_to_host(pyrohip_state *s, const double *dev_plane, double *host);
 int particles_alloc(pyrohip_ctx *c, int cap, pyrohip_particles **out);
 // frees the device memory (if the context still lives), unregisters and deletes the handle
 int particles_release(pyrohip_particles *p);
+// ---- particles.hip ----
+// the argument checks of an advance of p with the velocity planes of s (fn: the entry point's name)
+int particles_check(const pyrohip_particles *p, const pyrohip_state *s, const pyrohip_particle_params *P,
+                    const char *fn);
+// one advance inside a device-side run, enqueued behind the step that left the state's current
+// buffer: dt, "this iteration advanced" and the buffer parity are read from S and the state's flag
+// word on the device (live0: the set's live buffer when the run was opened); errors raise p->err
+// and bit 1 of the flag
+int particles_run_advance(pyrohip_particles *p, pyrohip_state *s, const pyrohip_particle_params *P,
+                          const StepScalars *S, int live0);
 
 // boundary types a kernel can apply as an index map while it loads (stencil.h: bc_map)
 inline bool bc_is_index_map(int b, bool allow_odd)

@@ -145,9 +145,11 @@ static int check_comp(pyrohip_state *s, const pyrohip_comp_params *p)
 extern "C" {
 
 // Up to max_steps iterations of the driver's loop without a host round trip per step: the run
-// protocol of DESIGN.md 3.6.1 (evolve.hip) around the CTU step.
-int pyrohip_comp_evolve(pyrohip_state *s, const pyrohip_comp_params *p, double cfl,
-                        pyrohip_dt_policy *pol, int max_steps, int *steps_done, double *dts_out)
+// protocol of DESIGN.md 3.6.1 (evolve.hip) around the CTU step.  particles: a tracer set that
+// rides along, or NULL.
+int pyrohip_comp_evolve_p(pyrohip_state *s, const pyrohip_comp_params *p, double cfl,
+                          pyrohip_dt_policy *pol, int max_steps, int *steps_done, double *dts_out,
+                          pyrohip_particles *particles, const pyrohip_particle_params *pparams)
 {
     PYRO_TRY(check_comp(s, p));
     PYRO_REQUIRE(pol && steps_done, "NULL argument");
@@ -170,6 +172,7 @@ int pyrohip_comp_evolve(pyrohip_state *s, const pyrohip_comp_params *p, double c
     EvolveRun r;
     r.halo_ok = wave;       // (k_fill_frame2 along the halo rows of a slab; a SphericalPolar grid is a single domain)
     r.sph_ok = sphw;
+    PYRO_TRY(evolve_bind_particles(r, s, particles, pparams, __func__));
     // (global_min: a decomposed run steps with the minimum over ALL slabs)
     PYRO_TRY(evolve_open(r, s, pol, cfl, 0, p->gamma, p->dx, p->dy, max_steps, true));
     // steps after the first: the tile kernel applies the boundary rules itself where it can
@@ -187,7 +190,9 @@ int pyrohip_comp_evolve(pyrohip_state *s, const pyrohip_comp_params *p, double c
     // measured no faster (profiles/r04_one_launch_step.txt: every wavefront of that instance starts
     // with ~5 us of dependent latency, the two small launches cost 1-2.5 % of a step; -1.5 % at
     // 16384^2): not the default.
-    bool one_launch = wave && p->step_launches == 1 && !s->nb_set && !c->global_cfl &&
+    // (with a particle set bound the run keeps the three launches: the one-launch steps write no ghost
+    // cell, and the tracers within half a cell of an upper border read the new buffer's frame)
+    bool one_launch = wave && p->step_launches == 1 && !s->nb_set && !c->global_cfl && !r.ps &&
                       comp_can_fuse_fill(s, p, false);
     for (int k = 0; k < 16 && one_launch; k++) one_launch = (s->bc[k] != PYROHIP_BC_HALO);
     pyro::StepPolicy *d_pol = nullptr;
@@ -268,6 +273,7 @@ int pyrohip_comp_evolve(pyrohip_state *s, const pyrohip_comp_params *p, double c
             rc = p->fast_math ? fastm::comp_step_fused_ex(s, &pf, 0.0, r.d_scal, &r.dmin)
                               : exact::comp_step_fused_ex(s, &pf, 0.0, r.d_scal, &r.dmin);
         r.take_pending();       // (the minimum of a tile-kernel launch is taken by the next policy call)
+        if (rc == 0) rc = evolve_particles(r);
     }
     s->frame_prefilled = false;      // (an iteration that stopped between the fill and its step)
     s->pol_next = nullptr;
@@ -283,6 +289,12 @@ int pyrohip_comp_evolve(pyrohip_state *s, const pyrohip_comp_params *p, double c
     rc = evolve_close(r, pol, steps_done, dts_out, framed, one_launch);
     if (s->next_cfl_min <= 0.0) s->cfl_is_global = false;
     return rc;
+}
+
+int pyrohip_comp_evolve(pyrohip_state *s, const pyrohip_comp_params *p, double cfl,
+                        pyrohip_dt_policy *pol, int max_steps, int *steps_done, double *dts_out)
+{
+    return pyrohip_comp_evolve_p(s, p, cfl, pol, max_steps, steps_done, dts_out, nullptr, nullptr);
 }
 
 int pyrohip_comp_dt(pyrohip_state *s, const pyrohip_comp_params *p, double cfl, double *dt_out)
@@ -481,9 +493,10 @@ int pyrohip_comp_rk_step(pyrohip_state *y, const pyrohip_comp_params *p, pyrohip
 // Up to max_steps steps of the compressible_rk driver loop (pyro_sim.py:241-281 with
 // compressible_rk/simulation.py:46-104) without a host round trip per step: as pyrohip_comp_evolve,
 // with the Runge-Kutta step above between the policy calls.
-int pyrohip_comp_rk_evolve(pyrohip_state *y, const pyrohip_comp_params *p, pyrohip_state *k, int nstages,
-                           const double *a, const double *b, double cfl, pyrohip_dt_policy *pol,
-                           int max_steps, int *steps_done, double *dts_out)
+int pyrohip_comp_rk_evolve_p(pyrohip_state *y, const pyrohip_comp_params *p, pyrohip_state *k, int nstages,
+                             const double *a, const double *b, double cfl, pyrohip_dt_policy *pol,
+                             int max_steps, int *steps_done, double *dts_out, pyrohip_particles *particles,
+                             const pyrohip_particle_params *pparams)
 {
     PYRO_TRY(check_rk(y, p, k, nstages, a, b));
     PYRO_REQUIRE(pol && steps_done && max_steps >= 1, "NULL argument / max_steps must be positive");
@@ -496,6 +509,7 @@ int pyrohip_comp_rk_evolve(pyrohip_state *y, const pyrohip_comp_params *p, pyroh
     pyrohip_ctx *c = s->ctx;
     PYRO_REQUIRE(!c->global_cfl, "device-side stepping: compressible_rk runs on a single domain");
     EvolveRun r;
+    PYRO_TRY(evolve_bind_particles(r, s, particles, pparams, __func__));
     PYRO_TRY(evolve_open(r, s, pol, cfl, 1, p->gamma, p->dx, p->dy, max_steps, false));
     int rc = 0;
     for (int m = 0; m < max_steps && rc == 0; m++) {
@@ -519,12 +533,21 @@ int pyrohip_comp_rk_evolve(pyrohip_state *y, const pyrohip_comp_params *p, pyroh
         rc = p->fast_math ? fastm::comp_rk_step_wave(s, p, k, nstages, a, b, 0.0, s->d_scal, &r.dmin)
                           : exact::comp_rk_step_wave(s, p, k, nstages, a, b, 0.0, s->d_scal, &r.dmin);
         r.take_pending();
+        if (rc == 0) rc = evolve_particles(r);
     }
     s->frame_prefilled = false;
     PYRO_TRY(rc);
     rc = evolve_close(r, pol, steps_done, dts_out, true, false);
     s->cfl_is_global = false;
     return rc;
+}
+
+int pyrohip_comp_rk_evolve(pyrohip_state *y, const pyrohip_comp_params *p, pyrohip_state *k, int nstages,
+                           const double *a, const double *b, double cfl, pyrohip_dt_policy *pol,
+                           int max_steps, int *steps_done, double *dts_out)
+{
+    return pyrohip_comp_rk_evolve_p(y, p, k, nstages, a, b, cfl, pol, max_steps, steps_done, dts_out, nullptr,
+                                    nullptr);
 }
 
 int pyrohip_comp_rk_rhs(pyrohip_state *y, const pyrohip_comp_params *p, pyrohip_state *k, int slot)

@@ -3,7 +3,8 @@
 // driver's dt policy -- and the three host steps every such loop is made of: evolve_open,
 // evolve_between, evolve_close (common.h).  The solvers' loops (pyrohip_comp_evolve,
 // pyrohip_comp_rk_evolve: comp_api.hip; pyrohip_swe_evolve: swe.hip) keep what is theirs: which
-// step kernel runs, the first CFL minimum, the halo exchange.
+// step kernel runs, the first CFL minimum, the halo exchange.  A tracer particle set may ride along
+// (DESIGN.md 15.1): evolve_bind_particles before the open, evolve_particles behind every step.
 #include "common.h"
 #include "stencil.h"
 
@@ -164,6 +165,28 @@ static int launch_policy(EvolveRun &r, int slot, int final_call, int flag_mask)
     return 0;
 }
 
+int evolve_bind_particles(EvolveRun &r, pyrohip_state *s, pyrohip_particles *ps, const pyrohip_particle_params *pp,
+                          const char *fn)
+{
+    r.ps = nullptr;
+    if (!ps) return 0;
+    PYRO_TRY(particles_check(ps, s, pp, fn));
+    if (s->nb_set || s->sph) {
+        set_error(std::string(fn) + ": tracer particles ride along on a single Cartesian domain only (not on a "
+                                    "slab of a decomposed run, not on a SphericalPolar grid)");
+        return PYROHIP_ERR_ARG;
+    }
+    r.ps = ps;
+    r.pp = pp;
+    r.ps_live0 = ps->cur;
+    return 0;
+}
+
+int evolve_particles(EvolveRun &r)
+{
+    return r.ps ? particles_run_advance(r.ps, r.s, r.pp, r.d_scal, r.ps_live0) : 0;
+}
+
 int evolve_open(EvolveRun &r, pyrohip_state *s, const pyrohip_dt_policy *pol, double cfl, int cfl_kind, double cfl_a,
                 double dx, double dy, int max_steps, bool global_min)
 {
@@ -191,6 +214,8 @@ int evolve_open(EvolveRun &r, pyrohip_state *s, const pyrohip_dt_policy *pol, do
         r.min_cached = ((double *)c->reduce_host)[0] == 1.0;
     }
     PYRO_CHECK_HIP(hipMemsetAsync(s->d_flag, 0, sizeof(int), c->stream));
+    // (the bound set's error word sticks for the run)
+    if (r.ps) PYRO_CHECK_HIP(hipMemsetAsync(r.ps->err, 0, sizeof(int), c->stream));
     s->pend_part = nullptr;
     return 0;
 }
@@ -248,12 +273,16 @@ int evolve_close(EvolveRun &r, pyrohip_dt_policy *pol, int *steps_done, double *
     PYRO_TRY(comm_wait_halo(s));
     // the one round trip of the call: scalars, flag, last CFL minimum, the dt sequence
     char *hb = (char *)c->reduce_host;                       // 256 pinned bytes
-    static_assert(sizeof(StepScalars) + 16 <= 256, "pinned scratch");
+    static_assert(sizeof(StepScalars) + 24 <= 256, "pinned scratch");
     PYRO_CHECK_HIP(hipMemcpyAsync(hb, r.d_scal, sizeof(StepScalars), hipMemcpyDeviceToHost, c->stream));
     PYRO_CHECK_HIP(hipMemcpyAsync(hb + sizeof(StepScalars), s->d_flag, sizeof(int), hipMemcpyDeviceToHost,
                                   c->stream));
     PYRO_CHECK_HIP(hipMemcpyAsync(hb + sizeof(StepScalars) + 8, r.dmin, sizeof(double), hipMemcpyDeviceToHost,
                                   c->stream));
+    int *perr = (int *)(hb + sizeof(StepScalars) + 16);
+    *perr = 0;
+    if (r.ps)
+        PYRO_CHECK_HIP(hipMemcpyAsync(perr, r.ps->err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     if (dts_out)
         PYRO_CHECK_HIP(hipMemcpyAsync(dts_out, s->d_dts, (size_t)max_steps * sizeof(double),
                                       hipMemcpyDeviceToHost, c->stream));
@@ -270,6 +299,10 @@ int evolve_close(EvolveRun &r, pyrohip_dt_policy *pol, int *steps_done, double *
         s->alt_base = old_base;
         s->d = s->base + geom_lead(g);
     }
+    // the set: one exchange of its two buffers per step that advanced (a failing advance stored
+    // nothing in the live one)
+    const bool part_error = *perr != 0;
+    if (r.ps) r.ps->cur ^= H.steps & 1;
     s->halo_pending = false;
     // the ghost frame of the final state: what single steps leave there is the filled frame of the
     // state BEFORE the last step that advanced, whose interior sits untouched in the other buffer
@@ -291,6 +324,11 @@ int evolve_close(EvolveRun &r, pyrohip_dt_policy *pol, int *steps_done, double *
     s->ghost_by_rules = false;      // a new time level: its ghost cells are stale until the next fill
     pol->t = H.t; pol->dt_old = H.dt_old; pol->n = H.n;
     *steps_done = H.steps;
+    if (part_error) {
+        set_error("a tracer particle's interpolation stencil leaves the state's array (position outside the "
+                  "ghosted grid, NaN or infinite): the state and the particle set are those before that step");
+        return PYROHIP_ERR_STATE;
+    }
     if (invalid) {
         set_error("invalid state: min(rho) <= 0 or min(e) <= 0 on the interior "
                   "(compressible/simulation.py:68-71); the state is the one before that step");

@@ -13,6 +13,9 @@
 //                    the reference rebuilds its dict with popitem(), the order
 //                    reverses at every update whether or not anything was dropped
 // No atomics on data, no workgroup waits for another: the result is deterministic.
+// Inside a device-side run (evolve.hip) the same three launches follow every step
+// in their run-protocol forms (k_part_*_run): dt, "did this iteration advance" and the buffer
+// parity come from device memory, the error word sticks and ends the run.
 // The memory of a set is allocated and released in ctx.hip (particles_alloc /
 // particles_release).
 #include "common.h"
@@ -99,15 +102,12 @@ __device__ inline int wg_scan_incl(int v, int *sh)
 
 // candidate position and velocity of the live particles of `cur` into the candidate arrays (same
 // slot: cand = positions, cand + 2 cap = velocities), keep flags, the survivors of each workgroup
-__global__ __launch_bounds__(kPartWG) void k_part_advance(const double *__restrict__ cur,
-                                                          double *__restrict__ cand, int cap,
-                                                          const int *__restrict__ count,
-                                                          int *__restrict__ keepf,
-                                                          int *__restrict__ wg_count,
-                                                          int *__restrict__ err, PartGrid G, double dt)
+// (flag: the state's flag word of a device-side run, raised with the error word; else nullptr)
+__device__ __forceinline__ void part_advance_wg(const double *__restrict__ cur, double *__restrict__ cand,
+                                                int cap, int n, int *__restrict__ keepf,
+                                                int *__restrict__ wg_count, int *__restrict__ err,
+                                                int *flag, const PartGrid &G, double dt, int *sh)
 {
-    __shared__ int sh[kPartWG];
-    const int n = *count;
     if ((int)(blockIdx.x * kPartWG) >= n) return;      // the whole workgroup (uniform)
     const int t = blockIdx.x * kPartWG + threadIdx.x;
     int kf = 0;
@@ -130,6 +130,7 @@ __global__ __launch_bounds__(kPartWG) void k_part_advance(const double *__restri
             part_side(y, keep, false, G.bc[3], G.ymin, G.ymax);
         } else {
             atomicOr(err, 1);
+            if (flag) atomicOr(flag, 1);
         }
         double *np = cand, *nv = cand + 2 * (size_t)cap;
         np[2 * (size_t)t] = x; np[2 * (size_t)t + 1] = y;
@@ -140,16 +141,22 @@ __global__ __launch_bounds__(kPartWG) void k_part_advance(const double *__restri
     const int tot = wg_scan_incl(kf, sh);
     if (threadIdx.x == kPartWG - 1) wg_count[blockIdx.x] = tot;
 }
+__global__ __launch_bounds__(kPartWG) void k_part_advance(const double *__restrict__ cur,
+                                                          double *__restrict__ cand, int cap,
+                                                          const int *__restrict__ count,
+                                                          int *__restrict__ keepf,
+                                                          int *__restrict__ wg_count,
+                                                          int *__restrict__ err, PartGrid G, double dt)
+{
+    __shared__ int sh[kPartWG];
+    part_advance_wg(cur, cand, cap, *count, keepf, wg_count, err, nullptr, G, dt, sh);
+}
 
 // exclusive scan of the per-workgroup counts (at most kPartWG of them: one per thread), the new
 // live count into count_new
-__global__ __launch_bounds__(kPartWG) void k_part_offsets(const int *__restrict__ count,
-                                                          const int *__restrict__ wg_count,
-                                                          int *__restrict__ wg_off,
-                                                          int *__restrict__ count_new)
+__device__ __forceinline__ void part_offsets_wg(int n, const int *__restrict__ wg_count,
+                                                int *__restrict__ wg_off, int *__restrict__ count_new, int *sh)
 {
-    __shared__ int sh[kPartWG];
-    const int n = *count;
     const int nwg = (n + kPartWG - 1) / kPartWG;
     const int t = threadIdx.x;
     const int c = (t < nwg) ? wg_count[t] : 0;
@@ -157,10 +164,37 @@ __global__ __launch_bounds__(kPartWG) void k_part_offsets(const int *__restrict_
     if (t < nwg) wg_off[t] = incl - c;
     if (t == kPartWG - 1) *count_new = incl;
 }
+__global__ __launch_bounds__(kPartWG) void k_part_offsets(const int *__restrict__ count,
+                                                          const int *__restrict__ wg_count,
+                                                          int *__restrict__ wg_off,
+                                                          int *__restrict__ count_new)
+{
+    __shared__ int sh[kPartWG];
+    part_offsets_wg(*count, wg_count, wg_off, count_new, sh);
+}
 
 // survivor number r (old order) -> slot total - 1 - r of the other buffer `out`: candidate position
 // and velocity, initial position from `cur`.  (The candidates have arrays of their own: a slot of
 // `out` is written while another workgroup may not have read its own candidate yet.)
+__device__ __forceinline__ void part_scatter_wg(const double *__restrict__ cur, const double *__restrict__ cand,
+                                                double *__restrict__ out, int cap, int n, int n_new,
+                                                const int *__restrict__ keepf,
+                                                const int *__restrict__ wg_off, int *sh)
+{
+    if ((int)(blockIdx.x * kPartWG) >= n) return;
+    const int t = blockIdx.x * kPartWG + threadIdx.x;
+    const int kf = (t < n) ? keepf[t] : 0;
+    const int incl = wg_scan_incl(kf, sh);
+    if (!kf) return;
+    const int r = wg_off[blockIdx.x] + incl - 1;
+    const size_t d = (size_t)(n_new - 1 - r), s = (size_t)t;
+    const double *ci = cur + 2 * (size_t)cap;
+    const double *cp = cand, *cv = cand + 2 * (size_t)cap;
+    double *op = out, *oi = out + 2 * (size_t)cap, *ov = out + 4 * (size_t)cap;
+    op[2 * d] = cp[2 * s]; op[2 * d + 1] = cp[2 * s + 1];
+    oi[2 * d] = ci[2 * s]; oi[2 * d + 1] = ci[2 * s + 1];
+    ov[2 * d] = cv[2 * s]; ov[2 * d + 1] = cv[2 * s + 1];
+}
 __global__ __launch_bounds__(kPartWG) void k_part_scatter(const double *__restrict__ cur,
                                                           const double *__restrict__ cand,
                                                           double *__restrict__ out, int cap,
@@ -170,20 +204,62 @@ __global__ __launch_bounds__(kPartWG) void k_part_scatter(const double *__restri
                                                           const int *__restrict__ wg_off)
 {
     __shared__ int sh[kPartWG];
-    const int n = *count;
-    if ((int)(blockIdx.x * kPartWG) >= n) return;
-    const int t = blockIdx.x * kPartWG + threadIdx.x;
-    const int kf = (t < n) ? keepf[t] : 0;
-    const int incl = wg_scan_incl(kf, sh);
-    if (!kf) return;
-    const int r = wg_off[blockIdx.x] + incl - 1;
-    const size_t d = (size_t)(*count_new - 1 - r), s = (size_t)t;
-    const double *ci = cur + 2 * (size_t)cap;
-    const double *cp = cand, *cv = cand + 2 * (size_t)cap;
-    double *op = out, *oi = out + 2 * (size_t)cap, *ov = out + 4 * (size_t)cap;
-    op[2 * d] = cp[2 * s]; op[2 * d + 1] = cp[2 * s + 1];
-    oi[2 * d] = ci[2 * s]; oi[2 * d + 1] = ci[2 * s + 1];
-    ov[2 * d] = cv[2 * s]; ov[2 * d + 1] = cv[2 * s + 1];
+    part_scatter_wg(cur, cand, out, cap, *count, *count_new, keepf, wg_off, sh);
+}
+
+// ---- the run-protocol forms (a device-side run: evolve.hip) ----
+// What the three launches behind the step of iteration m take from device memory instead of from
+// the host: S->dt (the dt the step kernel used), whether the iteration advanced the state at all,
+// and which of the set's two buffers is live.
+struct PartRun {
+    const StepScalars *S;     // of this iteration: written by the policy call in front of the step
+    int *flag;                // the state's flag word (bit 1: the step kernels', an earlier particle error)
+    double *buf[2];           // buf[0]: the live buffer when the run was opened
+    int *count[2];            // ... and their live counts
+};
+// Did iteration m advance the state?  Not past tmax or on a dead run (S->active == 0: the policy
+// call), not when the step kernel has just found its state invalid or an earlier advance of this
+// launch a particle outside the array (bit 1 of the flag: the next policy call makes it S->dead).
+// Then nothing is stored at all.  ONE thread reads the flag for the workgroup: other workgroups
+// of k_part_advance_run may be raising it, and the workgroup's barriers need one answer.
+__device__ __forceinline__ bool part_run_on(const PartRun &R, int *sh)
+{
+    if (threadIdx.x == 0) sh[0] = (R.S->active != 0 && (*(volatile int *)R.flag & 1) == 0) ? 1 : 0;
+    __syncthreads();
+    const bool on = sh[0] != 0;
+    __syncthreads();          // (sh is the scan's next)
+    return on;
+}
+// the live buffer: advances so far in this run = steps that advanced the state (S->steps), each
+// of which exchanged the two
+__device__ __forceinline__ int part_run_live(const PartRun &R) { return R.S->steps & 1; }
+
+__global__ __launch_bounds__(kPartWG) void k_part_advance_run(PartRun R, double *__restrict__ cand, int cap,
+                                                              int *__restrict__ keepf,
+                                                              int *__restrict__ wg_count,
+                                                              int *__restrict__ err, PartGrid G)
+{
+    __shared__ int sh[kPartWG];
+    if (!part_run_on(R, sh)) return;
+    const int b = part_run_live(R);
+    part_advance_wg(R.buf[b], cand, cap, *R.count[b], keepf, wg_count, err, R.flag, G, R.S->dt, sh);
+}
+__global__ __launch_bounds__(kPartWG) void k_part_offsets_run(PartRun R, const int *__restrict__ wg_count,
+                                                              int *__restrict__ wg_off)
+{
+    __shared__ int sh[kPartWG];
+    if (!part_run_on(R, sh)) return;
+    const int b = part_run_live(R);
+    part_offsets_wg(*R.count[b], wg_count, wg_off, R.count[b ^ 1], sh);
+}
+__global__ __launch_bounds__(kPartWG) void k_part_scatter_run(PartRun R, const double *__restrict__ cand,
+                                                              int cap, const int *__restrict__ keepf,
+                                                              const int *__restrict__ wg_off)
+{
+    __shared__ int sh[kPartWG];
+    if (!part_run_on(R, sh)) return;
+    const int b = part_run_live(R);
+    part_scatter_wg(R.buf[b], cand, R.buf[b ^ 1], cap, *R.count[b], *R.count[b ^ 1], keepf, wg_off, sh);
 }
 
 }  // namespace pyro
@@ -196,6 +272,71 @@ static int part_live(const pyrohip_particles *p, const char *fn)
     if (!p->ctx) { set_error(std::string(fn) + ": the context of this particle set was shut down"); return PYROHIP_ERR_ARG; }
     return 0;
 }
+
+#define PART_REQUIRE(cond, msg)                                               \
+    do {                                                                      \
+        if (!(cond)) {                                                        \
+            set_error(std::string(fn) + ": " + (msg));                        \
+            return PYROHIP_ERR_ARG;                                           \
+        }                                                                     \
+    } while (0)
+
+namespace pyro {
+
+int particles_check(const pyrohip_particles *p, const pyrohip_state *s, const pyrohip_particle_params *P,
+                    const char *fn)
+{
+    PYRO_TRY(part_live(p, fn));
+    PART_REQUIRE(s && P, "NULL argument");
+    PART_REQUIRE(P->size == sizeof(pyrohip_particle_params),
+                 "pyrohip_particle_params.size is not the size this library was built with");
+    PART_REQUIRE(s->ctx == p->ctx, "state and particle set live on different contexts");
+    PART_REQUIRE(P->vel_mode == PYROHIP_PART_VEL_PLANES || P->vel_mode == PYROHIP_PART_VEL_RATIO,
+                 "bad velocity mode");
+    const int nidx = P->vel_mode == PYROHIP_PART_VEL_RATIO ? 3 : 2;
+    for (int k = 0; k < nidx; k++)
+        PART_REQUIRE(P->idx[k] >= 0 && P->idx[k] < s->nvar, "plane index out of range");
+    for (int k = 0; k < 4; k++)
+        PART_REQUIRE(P->bc[k] >= PYROHIP_PART_DROP && P->bc[k] <= PYROHIP_PART_MIRROR,
+                     "bad particle boundary kind");
+    return 0;
+}
+
+// the grid and the velocity planes of the state's CURRENT buffer, as the kernels take them
+static PartGrid part_grid(const pyrohip_state *s, const pyrohip_particle_params *P)
+{
+    const Geom &g = s->g;
+    PartGrid G;
+    G.xmin = P->xmin; G.xmax = P->xmax; G.ymin = P->ymin; G.ymax = P->ymax; G.dx = P->dx; G.dy = P->dy;
+    for (int k = 0; k < 4; k++) G.bc[k] = P->bc[k];
+    G.mode = P->vel_mode;
+    G.qx = g.qx; G.qy = g.qy; G.ilo = g.ilo; G.jlo = g.jlo; G.pitch = g.pitch;
+    G.u = s->d + (size_t)P->idx[0] * g.plane;
+    G.v = s->d + (size_t)P->idx[1] * g.plane;
+    G.den = P->vel_mode == PYROHIP_PART_VEL_RATIO ? s->d + (size_t)P->idx[2] * g.plane : nullptr;
+    return G;
+}
+
+int particles_run_advance(pyrohip_particles *p, pyrohip_state *s, const pyrohip_particle_params *P,
+                          const StepScalars *S, int live0)
+{
+    pyrohip_ctx *c = p->ctx;
+    const PartGrid G = part_grid(s, P);
+    PartRun R;
+    R.S = S;
+    R.flag = s->d_flag;
+    for (int k = 0; k < 2; k++) { R.buf[k] = p->buf[live0 ^ k]; R.count[k] = p->count + (live0 ^ k); }
+    PYRO_LAUNCH(c, "k_part_advance_run", k_part_advance_run, dim3(p->nwg), dim3(kPartWG), 0, R, p->cand, p->cap,
+                p->keep, p->wg_count, p->err, G);
+    PYRO_LAUNCH(c, "k_part_offsets_run", k_part_offsets_run, dim3(1), dim3(kPartWG), 0, R,
+                (const int *)p->wg_count, p->wg_off);
+    PYRO_LAUNCH(c, "k_part_scatter_run", k_part_scatter_run, dim3(p->nwg), dim3(kPartWG), 0, R,
+                (const double *)p->cand, p->cap, (const int *)p->keep, (const int *)p->wg_off);
+    PYRO_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+}  // namespace pyro
 
 extern "C" {
 
@@ -276,31 +417,11 @@ int pyrohip_particles_download(pyrohip_particles *p, int *n, double *pos, double
 int pyrohip_particles_advance(pyrohip_particles *p, pyrohip_state *s,
                               const pyrohip_particle_params *P, double dt)
 {
-    PYRO_TRY(part_live(p, __func__));
-    PYRO_REQUIRE(s && P, "NULL argument");
-    PYRO_REQUIRE(P->size == sizeof(pyrohip_particle_params),
-                 "pyrohip_particle_params.size is not the size this library was built with");
-    PYRO_REQUIRE(s->ctx == p->ctx, "state and particle set live on different contexts");
-    PYRO_REQUIRE(P->vel_mode == PYROHIP_PART_VEL_PLANES || P->vel_mode == PYROHIP_PART_VEL_RATIO,
-                 "bad velocity mode");
-    const int nidx = P->vel_mode == PYROHIP_PART_VEL_RATIO ? 3 : 2;
-    for (int k = 0; k < nidx; k++)
-        PYRO_REQUIRE(P->idx[k] >= 0 && P->idx[k] < s->nvar, "plane index out of range");
-    for (int k = 0; k < 4; k++)
-        PYRO_REQUIRE(P->bc[k] >= PYROHIP_PART_DROP && P->bc[k] <= PYROHIP_PART_MIRROR,
-                     "bad particle boundary kind");
+    PYRO_TRY(particles_check(p, s, P, __func__));
     pyrohip_ctx *c = p->ctx;
     PYRO_CHECK_HIP(hipSetDevice(c->device));
     PYRO_TRY(comm_wait_halo(s));
-    const Geom &g = s->g;
-    PartGrid G;
-    G.xmin = P->xmin; G.xmax = P->xmax; G.ymin = P->ymin; G.ymax = P->ymax; G.dx = P->dx; G.dy = P->dy;
-    for (int k = 0; k < 4; k++) G.bc[k] = P->bc[k];
-    G.mode = P->vel_mode;
-    G.qx = g.qx; G.qy = g.qy; G.ilo = g.ilo; G.jlo = g.jlo; G.pitch = g.pitch;
-    G.u = s->d + (size_t)P->idx[0] * g.plane;
-    G.v = s->d + (size_t)P->idx[1] * g.plane;
-    G.den = nidx == 3 ? s->d + (size_t)P->idx[2] * g.plane : nullptr;
+    const PartGrid G = part_grid(s, P);
     const double *cur = p->buf[p->cur];
     double *nxt = p->buf[p->cur ^ 1];
     const int *cnt = p->count + p->cur;

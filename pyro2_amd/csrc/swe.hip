@@ -1046,9 +1046,10 @@ int pyrohip_swe_step(pyrohip_state *s, double dx, double dy, double grav, int li
 // 143-193: ghost fill, CFL time step, evolve) without a host round trip per step: the run
 // protocol of DESIGN.md 3.6.1 (evolve.hip) around the one-launch step kernel, whose wavefronts
 // leave the CFL partials the next policy call reduces.
-int pyrohip_swe_evolve(pyrohip_state *s, double dx, double dy, double grav, int limiter, int riemann,
-                       int fast_math, double cfl, pyrohip_dt_policy *pol, int max_steps,
-                       int *steps_done, double *dts_out)
+int pyrohip_swe_evolve_p(pyrohip_state *s, double dx, double dy, double grav, int limiter, int riemann,
+                         int fast_math, double cfl, pyrohip_dt_policy *pol, int max_steps,
+                         int *steps_done, double *dts_out, pyrohip_particles *particles,
+                         const pyrohip_particle_params *pparams)
 {
     PYRO_TRY(sw_check(s, dx, dy, grav, limiter, riemann));
     PYRO_REQUIRE(pol && steps_done && max_steps >= 1, "NULL argument / max_steps must be positive");
@@ -1063,21 +1064,28 @@ int pyrohip_swe_evolve(pyrohip_state *s, double dx, double dy, double grav, int 
     pyrohip_ctx *c = s->ctx;
     PYRO_TRY(state_alt(s));     // (k_fill_frame2 writes the second buffer's frame)
     EvolveRun r;
+    PYRO_TRY(evolve_bind_particles(r, s, particles, pparams, __func__));
     PYRO_TRY(evolve_open(r, s, pol, cfl, 2, grav, dx, dy, max_steps, false));
     // one partial per wavefront of the step kernel (46 978 at 16384^2, 128 820 at 32768^2 on 256
     // CUs), sized BEFORE the first launch: growing the buffer later would move what dmin points at
     const size_t nunits = (size_t)swx::swe_wave_units(s->g, c->num_cus);
     PYRO_TRY(c->reduce.ensure(sw_reduce_doubles(nunits) * sizeof(double)));
     double *part = (double *)c->reduce.p;
+    // With a particle set bound, the contracted build takes the CFL minimum of EVERY step the way
+    // pyrohip_swe_dt does (k_sw_cfl on the filled state, the reference's operation order): the
+    // step kernel's own partials come from reciprocal-based quotients there, an ulp away, and the
+    // run has to reproduce single steps -- the tracers' dt included -- bit for bit.
+    const bool own_min = r.ps != nullptr && fast_math != 0;
     int rc = 0;
     for (int m = 0; m < max_steps && rc == 0; m++) {
         bool frame_done = false;
-        if (m == 0) {      // the CFL minimum of the state as handed over (whole array, filled)
+        if (m == 0 || own_min) {      // the CFL minimum of the state as handed over (whole array, filled)
             rc = evolve_fill(r, true, &frame_done);          // pyro_sim.py:250: fill_BC_all
             if (rc) break;
-            if (r.min_cached) r.dmin = &s->d_scal->min0;
+            r.pend = nullptr;
+            if (m == 0 && r.min_cached) r.dmin = &s->d_scal->min0;
             else rc = sw_cfl_min_device(s, dx, dy, grav, &r.dmin, nunits);
-            if (rc == 0) rc = evolve_policy(r, 0);
+            if (rc == 0) rc = evolve_policy(r, m);
         } else
             rc = evolve_between(r, m, true, true, &frame_done);
         if (rc) break;
@@ -1089,10 +1097,21 @@ int pyrohip_swe_evolve(pyrohip_state *s, double dx, double dy, double grav, int 
             rc = PYROHIP_ERR_ARG;
         }
         r.pend = part; r.npend = np;    // (held here, not in the state: the kernel's own buffer)
+        if (rc == 0) rc = evolve_particles(r);
     }
     PYRO_TRY(rc);
-    // (no swe kernel raises the positivity flag: the verdict is always "valid")
-    return evolve_close(r, pol, steps_done, dts_out, true, false);
+    // (no swe kernel raises the positivity flag: only a bound particle set can end the run)
+    rc = evolve_close(r, pol, steps_done, dts_out, true, false);
+    if (own_min) s->next_cfl_min = -1.0;      // (the next call starts from k_sw_cfl's minimum too)
+    return rc;
+}
+
+int pyrohip_swe_evolve(pyrohip_state *s, double dx, double dy, double grav, int limiter, int riemann,
+                       int fast_math, double cfl, pyrohip_dt_policy *pol, int max_steps,
+                       int *steps_done, double *dts_out)
+{
+    return pyrohip_swe_evolve_p(s, dx, dy, grav, limiter, riemann, fast_math, cfl, pol, max_steps, steps_done,
+                                dts_out, nullptr, nullptr);
 }
 
 // stage: 0 Uxl0 1 Uxr0 2 Uyl0 3 Uyr0 (face states before the transverse

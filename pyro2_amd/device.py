@@ -306,12 +306,13 @@ class DeviceState:
             check(self._l.pyrohip_swe_step_ex(self.h, float(dx), float(dy), float(grav), int(limiter),
                                               r, float(dt), int(kernel_set), int(fast_math)))
 
-    def swe_evolve(self, dx, dy, grav, limiter, riemann, cfl, policy, max_steps, fast_math=0):
+    def swe_evolve(self, dx, dy, grav, limiter, riemann, cfl, policy, max_steps, fast_math=0, particles=None):
         """up to max_steps swe steps with the driver's dt policy on the device (as comp_evolve);
         returns the dt of the steps taken"""
         r = self.SWE_RIEMANN[riemann] if isinstance(riemann, str) else int(riemann)
-        return self._evolve(policy, max_steps, lambda *tail: self._l.pyrohip_swe_evolve(
-            self.h, float(dx), float(dy), float(grav), int(limiter), r, int(fast_math), float(cfl), *tail))
+        return self._evolve(policy, max_steps, "pyrohip_swe_evolve",
+                            (self.h, float(dx), float(dy), float(grav), int(limiter), r, int(fast_math), float(cfl)),
+                            particles)
 
     def swe_stage(self, name):
         names = ("Uxl0", "Uxr0", "Uyl0", "Uyr0", "FxT", "FyT", "Fx", "Fy")
@@ -669,35 +670,41 @@ class DeviceState:
             check(self._l.pyrohip_comp_rk_step(self.h, C.byref(params), kstate.h, float(dt), len(b),
                                                dptr(a), dptr(b)))
 
-    def _evolve(self, policy, max_steps, call):
-        """one device-side run: call(pol, max_steps, steps_done, dts_out) is the
-        library's entry point with its leading arguments bound; `policy` is advanced in place,
-        also when the run ends on an invalid state"""
+    def _evolve(self, policy, max_steps, entry, head, particles=None):
+        """one device-side run: `entry` is the name of the library's entry
+        point, `head` its leading arguments; `policy` is advanced in place, also when the run
+        ends on an invalid state.  particles: (DeviceParticles, ParticleParams) of a tracer set
+        that rides along (the entry point's _p form), or None"""
         pc = _lib.DtPolicyC(policy.tmax, policy.f0, policy.mx, policy.fix, policy.t, policy.dt_old,
                             policy.n)
         done = C.c_int()
         dts = np.empty(int(max_steps))
+        tail = (C.byref(pc), int(max_steps), C.byref(done), dptr(dts))
+        if particles is not None:
+            entry, tail = entry + "_p", tail + (particles[0].h, C.byref(particles[1]))
         with self.ctx.lock:
-            rc = call(C.byref(pc), int(max_steps), C.byref(done), dptr(dts))
+            rc = getattr(self._l, entry)(*head, *tail)
         policy.t, policy.dt_old, policy.n = pc.t, pc.dt_old, int(pc.n)
         _check_run(rc, dts[:done.value])
         return dts[:done.value]
 
-    def comp_rk_evolve(self, params, kstate, a, b, cfl, policy, max_steps):
+    def comp_rk_evolve(self, params, kstate, a, b, cfl, policy, max_steps, particles=None):
         """up to max_steps compressible_rk steps with the driver's dt policy on the device
         (as comp_evolve); returns the dt of the steps taken"""
         a = np.ascontiguousarray(a, dtype=np.float64)
         b = np.ascontiguousarray(b, dtype=np.float64)
-        return self._evolve(policy, max_steps, lambda *tail: self._l.pyrohip_comp_rk_evolve(
-            self.h, C.byref(params), kstate.h, len(b), dptr(a), dptr(b), float(cfl), *tail))
+        return self._evolve(policy, max_steps, "pyrohip_comp_rk_evolve",
+                            (self.h, C.byref(params), kstate.h, len(b), dptr(a), dptr(b), float(cfl)), particles)
 
-    def comp_evolve(self, params, cfl, policy, max_steps):
+    def comp_evolve(self, params, cfl, policy, max_steps, particles=None):
         """up to max_steps single_steps (ghost fill, dt policy, evolve) without a host
         round trip per step.  `policy`: an object with tmax, f0 (init_tstep_factor), mx
         (max_dt_change), fix, t, dt_old, n (decomp.DtPolicy / helpers.DtPolicy); it is
-        advanced in place.  Returns the dt of the steps taken."""
-        return self._evolve(policy, max_steps, lambda *tail: self._l.pyrohip_comp_evolve(
-            self.h, C.byref(params), float(cfl), *tail))
+        advanced in place.  particles: (DeviceParticles, ParticleParams) of a tracer set that is
+        advanced behind every step (Particles.device_binding), or None.  Returns the dt of the
+        steps taken."""
+        return self._evolve(policy, max_steps, "pyrohip_comp_evolve", (self.h, C.byref(params), float(cfl)),
+                            particles)
 
     STAGES = {"q": 0, "xi": 1, "XM": 2, "XP": 3, "YM": 4, "YP": 5, "FxT": 6,
               "FyT": 7, "Fx": 8, "Fy": 9}
@@ -1012,11 +1019,11 @@ class DeviceParticles:
             check(self._l.pyrohip_particles_count(self.h, C.byref(n)))
         return n.value
 
-    def advance(self, state, grid, bc_kinds, mode, indices, dt):
-        """one update over dt with the velocity in `state` (pyrohip_particles_advance).
-        grid: anything with xmin, xmax, ymin, ymax, dx, dy; bc_kinds: the four particle
-        boundary names (xlb, xrb, ylb, yrb); mode: "planes" (indices iu, iv) or "ratio"
-        (indices inum_x, inum_y, iden)"""
+    @staticmethod
+    def params(grid, bc_kinds, mode, indices):
+        """pyrohip_particle_params.  grid: anything with xmin, xmax, ymin, ymax, dx, dy; bc_kinds:
+        the four particle boundary names (xlb, xrb, ylb, yrb); mode: "planes" (indices iu, iv) or
+        "ratio" (indices inum_x, inum_y, iden)"""
         P = _lib.ParticleParams()
         P.size = C.sizeof(_lib.ParticleParams)
         P.xmin, P.xmax, P.ymin, P.ymax = (float(grid.xmin), float(grid.xmax), float(grid.ymin),
@@ -1028,5 +1035,11 @@ class DeviceParticles:
         assert len(indices) == (3 if mode == "ratio" else 2)
         for k, n in enumerate(indices):
             P.idx[k] = int(n)
+        return P
+
+    def advance(self, state, grid, bc_kinds, mode, indices, dt):
+        """one update over dt with the velocity in `state` (pyrohip_particles_advance);
+        grid, bc_kinds, mode, indices: as for params()"""
+        P = self.params(grid, bc_kinds, mode, indices)
         with self.ctx.lock:
             check(self._l.pyrohip_particles_advance(self.h, state.h, C.byref(P), float(dt)))

@@ -21,7 +21,9 @@ The particles have two homes.  `update_particles(dt, u, v)` with host arrays
 path above.  Where the velocity comes out of the evolving state -- stored
 x-/y-velocity planes, or momenta over density / height --
 `update_particles_device` runs the same arithmetic in three HIP launches beside
-the solver's step (csrc/particles.hip, pyrohip_particles_advance): the state is
+the solver's step (csrc/particles.hip, pyrohip_particles_advance), and a solver's
+evolve_many carries the set through its device-side run (device_binding /
+device_ran: the same launches behind every step, dt read on the device): the state is
 never downloaded for the tracers, and the positions are the same bit for bit.
 `pos`, `init` and `vel` are properties over a host copy and a device copy
 (device.DeviceParticles) with validity flags: the set is downloaded only when
@@ -144,6 +146,21 @@ class Particles:
         myg, bc = self.sim_data.grid, self.bc
         dev = self._device(state.ctx)
         dev.advance(state, myg, (bc.xlb, bc.xrb, bc.ylb, bc.yrb), mode, indices, dt)
+        self._host_valid = False
+
+    def device_binding(self, ctx, mode, indices):
+        """(DeviceParticles, pyrohip_particle_params) for a device-side run that carries the set
+        (DeviceState.comp_evolve / comp_rk_evolve / swe_evolve, particles=...): the set is uploaded
+        if the host copy is the current one.  None: nothing left to move.  The caller reports the
+        end of the run with device_ran()."""
+        if self._host_valid and len(self._pos) == 0:
+            return None
+        bc = self.bc
+        dev = self._device(ctx)
+        return dev, dev.params(self.sim_data.grid, (bc.xlb, bc.xrb, bc.ylb, bc.yrb), mode, indices)
+
+    def device_ran(self):
+        """the run that device_binding() was made for has ended: the device copy is the current one"""
         self._host_valid = False
 
     # pyro keys its dict by the initial position: a second particle with the

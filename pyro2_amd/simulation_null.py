@@ -207,7 +207,9 @@ class NullSimulation:
         """evolve_many of the solvers whose dt policy runs in a kernel: up to
         nsteps of fill_BC_all + compute_timestep + evolve without a host round trip per step.
         start() -> device state (and what the solver does first); call(state, policy, cfl,
-        nsteps) -> the time steps taken.  refusable: the library's own rules for device-side
+        nsteps, particles) -> the time steps taken, `particles` being what the device state's
+        *_evolve methods take: the tracer set, advanced on the device behind every step
+        (DESIGN.md 15.1), or None.  refusable: the library's own rules for device-side
         stepping are stricter than can_evolve_many's -- a refusal before the first step means
         "step singly from now on"."""
         from ._lib import PyroHipError
@@ -220,8 +222,12 @@ class NullSimulation:
         tm = self.tc.timer("evolve")
         tm.begin()
         st = start()
+        bound = None
+        if self.particles is not None:
+            # (can_evolve_many: only a set the device can advance gets here)
+            bound = self.particles.device_binding(st.ctx, *self._device_particle_source())
         try:
-            dts = call(st, pol, float(rp.get_param("driver.cfl")), int(nsteps))
+            dts = call(st, pol, float(rp.get_param("driver.cfl")), int(nsteps), bound)
         except PyroHipError as e:
             if not refusable or "device-side stepping:" not in str(e) or pol.n != int(self.n):
                 raise
@@ -229,6 +235,8 @@ class NullSimulation:
             dts = []
         finally:
             self.cc_data.device_modified()
+            if bound is not None:
+                self.particles.device_ran()
             self.cc_data.t, self.n, self.dt_old = pol.t, pol.n, pol.dt_old
         if len(dts):
             self.dt = float(dts[-1])

@@ -114,9 +114,12 @@ class Simulation(NullSimulation):
 
     def can_evolve_many(self):
         """batches of steps on the device (pyrohip_swe_evolve): standard boundary types filled
-        by the device, nothing watching the data, no tracer particles, the plain evolve()"""
+        by the device, nothing watching the data, tracer particles only where the device
+        advances them, the plain evolve()"""
         cc = self.cc_data
-        if self.particles is not None or cc._views_alive() or type(self).evolve is not Simulation.evolve:
+        if cc._views_alive() or type(self).evolve is not Simulation.evolve:
+            return False
+        if self.particles is not None and self._device_particle_source() is None:
             return False
         simple = ("outflow", "reflect-even", "reflect-odd", "periodic")
         if not all(b in simple for n in cc.names for b in cc.BCs[n].sides()):
@@ -133,9 +136,9 @@ class Simulation(NullSimulation):
             cc.take_pending_fill()
             return st
         return self._evolve_by_device_policy(
-            nsteps, start, lambda st, pol, cfl, n: st.swe_evolve(
+            nsteps, start, lambda st, pol, cfl, n, particles: st.swe_evolve(
                 g.dx, g.dy, rp.get_param("swe.grav"), rp.get_param("swe.limiter"), rp.get_param("swe.riemann"),
-                cfl, pol, n, fast_math=self._fast_math()))
+                cfl, pol, n, fast_math=self._fast_math(), particles=particles))
 
     def dovis(self):
         import matplotlib.pyplot as plt
