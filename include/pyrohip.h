@@ -691,6 +691,23 @@ int pyrohip_swe_stage_dump(pyrohip_state *s, int stage, double *out);
    iu, iv of the state (ng >= 4, ghost cells filled)                        */
 int pyrohip_bg_step(pyrohip_state *s, int iu, int iv, double dx, double dy,
                     double dt, int limiter);
+/* the same step in ONE launch (k_bg_tile, csrc/burgers.hip): the new level is
+   written to the state's second buffer and the two are exchanged.  The state holds exactly
+   the two velocity components.  Afterwards the whole array equals what pyrohip_bg_step
+   leaves, bit for bit: the new interior, and in the ghost cells the values they had before
+   the call.  No work planes are written (pyrohip_inc_stage_dump has nothing to show).     */
+int pyrohip_bg_step1(pyrohip_state *s, int iu, int iv, double dx, double dy,
+                     double dt, int limiter);
+/* up to max_steps iterations of the burgers driver loop (pyro_sim.py:241-281 with
+   burgers/simulation.py:37-117) without a host round trip per step, as pyrohip_swe_evolve:
+   ghost fill, the driver's dt policy in a kernel on the CFL minimum
+   min(dx / max(max|u|, 1e-12), dy / max(max|v|, 1e-12)) that the previous step's kernel
+   left, the one-launch step.  Single Cartesian domain, outflow / reflect / periodic sides
+   (there the interior maxima are the whole-array maxima the reference takes).  Non-finite
+   velocities are outside the contract: the device maxima do not propagate NaN.            */
+int pyrohip_bg_evolve(pyrohip_state *s, int iu, int iv, double dx, double dy, int limiter,
+                      double cfl, pyrohip_dt_policy *policy, int max_steps, int *steps_done,
+                      double *dts_out);
 /* incompressible Simulation.evolve (pyro/incompressible/simulation.py:200-
    330), the four device pieces around the two MG solves.  mg: a
    pyrohip_mg with the state's nx (= ny) and the BCs of phi.
@@ -844,7 +861,7 @@ int pyrohip_particles_advance(pyrohip_particles *p, pyrohip_state *s,
                               const pyrohip_particle_params *params, double dt);
 
 /* ---- tracer particles inside the device-side stepping loops ----
-   pyrohip_comp_evolve / pyrohip_comp_rk_evolve / pyrohip_swe_evolve with a particle set that
+   pyrohip_comp_evolve / pyrohip_comp_rk_evolve / pyrohip_swe_evolve / pyrohip_bg_evolve with a particle set that
    rides along: behind every step that advanced the state the set is advanced over that
    step's dt -- read from device memory -- by the three launches of
    pyrohip_particles_advance in their run-protocol forms, with the velocity planes and the
@@ -882,6 +899,10 @@ int pyrohip_swe_evolve_p(pyrohip_state *s, double dx, double dy, double grav, in
                          int max_steps, int *steps_done, double *dts_out,
                          pyrohip_particles *particles,
                          const pyrohip_particle_params *pparams);
+int pyrohip_bg_evolve_p(pyrohip_state *s, int iu, int iv, double dx, double dy, int limiter,
+                        double cfl, pyrohip_dt_policy *policy, int max_steps, int *steps_done,
+                        double *dts_out, pyrohip_particles *particles,
+                        const pyrohip_particle_params *pparams);
 
 /* ---- multi-GPU: x-slab decomposition, one process per GPU, RCCL -------- */
 #define PYROHIP_UNIQUE_ID_BYTES 128

@@ -159,6 +159,9 @@ _PROTOS = {
                            C.POINTER(DtPolicyC), C.c_int, C.POINTER(C.c_int), _DP],
     "pyrohip_swe_stage_dump": [_VP, C.c_int, _DP],
     "pyrohip_bg_step": [_VP, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int],
+    "pyrohip_bg_step1": [_VP, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int],
+    "pyrohip_bg_evolve": [_VP, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double,
+                          C.POINTER(DtPolicyC), C.c_int, _IP, _DP],
     "pyrohip_inc_mac_rhs": [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
                             C.c_double, C.c_double, C.c_int, C.c_double, _DP],
     "pyrohip_inc_visc_rhs": [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
@@ -277,6 +280,8 @@ _PROTOS = {
                                  C.POINTER(DtPolicyC), C.c_int, _IP, _DP, _VP, C.POINTER(ParticleParams)],
     "pyrohip_swe_evolve_p": [_VP, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_double,
                              C.POINTER(DtPolicyC), C.c_int, _IP, _DP, _VP, C.POINTER(ParticleParams)],
+    "pyrohip_bg_evolve_p": [_VP, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double,
+                            C.POINTER(DtPolicyC), C.c_int, _IP, _DP, _VP, C.POINTER(ParticleParams)],
 }
 
 EXPORTS = sorted(list(_PROTOS) + ["pyrohip_last_error", "pyrohip_backend"])

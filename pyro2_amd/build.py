@@ -69,6 +69,8 @@ UNITS = [
     ("mg_march.hip", "mg_march_t2", ["-ffp-contract=off", "-mllvm", "-pragma-unroll-threshold=200000", "-DMGM_UNIT=2"]),
     ("incompressible.hip", "incompressible", ["-ffp-contract=off"]),
     ("lm_atm.hip", "lm_atm", ["-ffp-contract=off"]),
+    # burgers: the whole step in one launch and its device-side stepping loop.  ONE build: never contracted
+    ("burgers.hip", "burgers", ["-ffp-contract=off"]),
     ("swe.hip", "swe", ["-ffp-contract=off", "-DPYRO_FAST=0"]),
     ("swe.hip", "swe_fast", ["-ffp-contract=fast", "-DPYRO_FAST=1", "-fno-honor-nans"]),
     ("comm.hip", "comm", ["-ffp-contract=off"]),

@@ -348,7 +348,7 @@ struct pyrohip_state {
     double next_cfl_min = -1.0;  // min over interior of dx/(|u|+c) etc. of the
                                  // state after the last step (-1: unknown)
     bool cfl_is_global = false;  // ... already reduced over all ranks
-    int cfl_kind = 0;            // ... 0: the CTU solver's quantity; 1: compressible_rk's; 2: swe's
+    int cfl_kind = 0;            // ... 0: the CTU solver's quantity; 1: compressible_rk's; 2: swe's; 3: burgers'
     double cfl_par[3] = {0.0, 0.0, 0.0};   // ... of a device-side run: the (gamma | g, dx, dy) it was taken with
                                  // min 1 / ((|u|+c)/dx + (|v|+c)/dy) (comp_rk_step_wave)
     // the ghost cells hold exactly what the boundary rules (outflow / reflect / periodic index
@@ -425,8 +425,8 @@ inline int frame_pieces(const Geom &g)
     const int rows_per_piece = 256 / (2 * g.ng);
     return 2 * g.ng * ((g.qy + 255) / 256) + (g.nx + rows_per_piece - 1) / rows_per_piece;
 }
-// can k_fill_frame2 fill the state's ghost cells (index maps on every side of the four variables, a
-// second buffer)?  halo_ok: x sides that are cuts of a slab pass; sph_ok: a SphericalPolar grid passes
+// can k_fill_frame2 fill the state's ghost cells (four variables or two, index maps on every side of
+// each, a second buffer)?  halo_ok: x sides that are cuts of a slab pass; sph_ok: a SphericalPolar grid passes
 bool frame_fill_ok(const pyrohip_state *s, bool halo_ok = false, bool sph_ok = false);
 // one call of a solver's stepping loop
 struct EvolveRun {

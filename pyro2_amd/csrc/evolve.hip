@@ -10,7 +10,7 @@
 
 using namespace pyro;
 
-// Boundary fill of all four variables AND the ghost frame of the other state buffer in one
+// Boundary fill of all NV variables (4: the hydro states; 2: burgers' u, v) AND the ghost frame of the other state buffer in one
 // launch (device-side stepping with the row-marching kernel: pyrohip_fill_bc is two launches,
 // the copy of the ghost frame into the new buffer a third -- 19 us of kernels and two gaps per
 // step, 2.5 % of a 4096^2 step, 8 % at 2048^2).  A ghost cell's value goes through the x rule
@@ -20,6 +20,7 @@ using namespace pyro;
 // cell of the frame.
 // (b: piece of 256 threads, t: thread in the piece -- a workgroup of k_fill_frame2, or a quarter
 // of one of k_fill_frame2_policy)
+template <int NV>
 __device__ __forceinline__ void fill_frame2_piece(const double *src, double *cur, double *alt,
                                                   const Geom &g, const int *__restrict__ bc, int b, int t)
 {   // src: the buffer whose interior the images are taken from (cur itself, or -- at the end of a
@@ -44,7 +45,7 @@ __device__ __forceinline__ void fill_frame2_piece(const double *src, double *cur
     }
     const size_t k = (size_t)i * g.pitch + j;
 #pragma unroll
-    for (int n = 0; n < 4; n++) {
+    for (int n = 0; n < NV; n++) {
         const pyro::BcMap mx = pyro::bc_map(g.ilo, g.ihi, ng, bc[n * 4 + 0], bc[n * 4 + 1], true);
         const pyro::BcMap my = pyro::bc_map(g.jlo, g.jhi, ng, bc[n * 4 + 2], bc[n * 4 + 3], true);
         const int si = pyro::bc_src(mx, i, g.ilo, g.ihi), sj = pyro::bc_src(my, j, g.jlo, g.jhi);
@@ -56,10 +57,11 @@ __device__ __forceinline__ void fill_frame2_piece(const double *src, double *cur
         if (alt) alt[n * g.plane + k] = w;
     }
 }
+template <int NV>
 __global__ __launch_bounds__(256) void k_fill_frame2(const double *src, double *cur, double *alt,
                                                      Geom g, const int *__restrict__ bc)
 {
-    fill_frame2_piece(src, cur, alt, g, bc, (int)blockIdx.x, (int)threadIdx.x);
+    fill_frame2_piece<NV>(src, cur, alt, g, bc, (int)blockIdx.x, (int)threadIdx.x);
 }
 
 constexpr int kPolicyThreads = 1024;
@@ -114,6 +116,7 @@ __global__ __launch_bounds__(kPolicyThreads) void k_dt_policy(StepScalars *S, co
 // policy (k_dt_policy: reads that step's CFL partials) do not depend on each other.  Workgroups
 // of 1024 threads: the first nfill hold four 256-thread pieces of the fill each, the last one
 // runs the policy.  One launch and its gap less per step (8 us of a 0.68 ms step at 4096^2).
+template <int NV>
 __global__ __launch_bounds__(kPolicyThreads) void k_fill_frame2_policy(
     const double *src, double *cur, double *alt, Geom g, const int *__restrict__ bc, int npieces,
     StepScalars *S, const double *cflmin, const int *flag, double *dts, int slot, const double *part,
@@ -124,7 +127,7 @@ __global__ __launch_bounds__(kPolicyThreads) void k_fill_frame2_policy(
         return;
     }
     const int piece = (int)blockIdx.x * 4 + (int)threadIdx.x / 256;
-    if (piece < npieces) fill_frame2_piece(src, cur, alt, g, bc, piece, (int)threadIdx.x % 256);
+    if (piece < npieces) fill_frame2_piece<NV>(src, cur, alt, g, bc, piece, (int)threadIdx.x % 256);
 }
 
 namespace pyro {
@@ -134,9 +137,9 @@ namespace pyro {
 // other buffer's frame takes a copy, which the exchange posted by the coming step overwrites)
 bool frame_fill_ok(const pyrohip_state *s, bool halo_ok, bool sph_ok)
 {
-    if (s->nvar != 4 || (s->nb_set && !halo_ok) || s->user_bc || s->ramp_bc || (s->sph && !sph_ok) || !s->alt_base)
+    if ((s->nvar != 4 && s->nvar != 2) || (s->nb_set && !halo_ok) || s->user_bc || s->ramp_bc || (s->sph && !sph_ok) || !s->alt_base)
         return false;
-    for (int k = 0; k < 16; k++) {
+    for (int k = 0; k < 4 * s->nvar; k++) {
         const int b = s->bc[k];
         if (b != PYROHIP_BC_OUTFLOW && b != PYROHIP_BC_REFLECT_EVEN && b != PYROHIP_BC_REFLECT_ODD &&
             b != PYROHIP_BC_PERIODIC && !(halo_ok && (k % 4) < 2 && b == PYROHIP_BC_HALO))
@@ -148,8 +151,10 @@ bool frame_fill_ok(const pyrohip_state *s, bool halo_ok, bool sph_ok)
 // k_fill_frame2: the ghost frame of the state's buffer -- and of `alt` -- from the interior at src
 static int launch_frame(pyrohip_state *s, const double *src, double *alt)
 {
-    PYRO_LAUNCH(s->ctx, "k_fill_frame2", k_fill_frame2, dim3(frame_pieces(s->g)), dim3(256), 0, src, s->d, alt,
-                s->g, (const int *)s->d_bc);
+    // (frame_fill_ok: 4 variables or 2)
+    const auto kernel = s->nvar == 2 ? k_fill_frame2<2> : k_fill_frame2<4>;
+    PYRO_LAUNCH(s->ctx, "k_fill_frame2", kernel, dim3(frame_pieces(s->g)), dim3(256), 0, src, s->d, alt, s->g,
+                (const int *)s->d_bc);
     PYRO_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -238,7 +243,8 @@ int evolve_between(EvolveRun &r, int m, bool frame, bool fill, bool *frame_done)
         return launch_policy(r, m, 0, 1);
     }
     const int npieces = frame_pieces(s->g);
-    PYRO_LAUNCH(s->ctx, "k_fill_frame2_policy", k_fill_frame2_policy, dim3((npieces + 3) / 4 + 1),
+    const auto kernel = s->nvar == 2 ? k_fill_frame2_policy<2> : k_fill_frame2_policy<4>;
+    PYRO_LAUNCH(s->ctx, "k_fill_frame2_policy", kernel, dim3((npieces + 3) / 4 + 1),
                 dim3(kPolicyThreads), 0, (const double *)s->d, s->d, s->alt_base + geom_lead(s->g), s->g,
                 (const int *)s->d_bc, npieces, r.d_scal, r.dmin, (const int *)s->d_flag, s->d_dts, m, r.pend,
                 r.npend, const_cast<double *>(r.dmin));

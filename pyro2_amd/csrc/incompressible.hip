@@ -20,6 +20,7 @@
 #include "common.h"
 #include "mg_internal.h"
 #include "stencil.h"
+#include "bg_states.h"   // bg_riemann, bg_upwind and the state formulas (shared with burgers.hip)
 
 namespace pyro {
 
@@ -30,19 +31,6 @@ enum {
     W_UMAC, W_VMAC, W_ADVX, W_ADVY,
     W_NPL
 };
-
-// burgers_interface.py:265-290
-__device__ __forceinline__ double bg_riemann(double ql, double qr)
-{
-    if (ql <= 0.0 && qr >= 0.0) return 0.0;
-    return (ql > 0.0 && ql + qr > 0.0) ? ql : qr;
-}
-// burgers_interface.py:236-262
-__device__ __forceinline__ double bg_upwind(double ql, double qr, double s)
-{
-    if (s == 0.0) return 0.5 * (ql + qr);
-    return (s > 0.0) ? ql : qr;
-}
 
 struct BP {   // kernel parameters
     double dx, dy, dt, dtdx, dtdy;
@@ -71,14 +59,10 @@ __global__ __launch_bounds__(256) void k_bg_hat(const double *__restrict__ u,
     const double ldvx = limited_slope(v[k - 2 * p], v[k - p], vc, v[k + p], v[k + 2 * p], P.limiter);
     const double lduy = limited_slope(u[k - 2], u[k - 1], uc, u[k + 1], u[k + 2], P.limiter);
     const double ldvy = limited_slope(v[k - 2], v[k - 1], vc, v[k + 1], v[k + 2], P.limiter);
-    double uxl = uc + 0.5 * (1.0 - P.dtdx * uc) * ldux;
-    double uxr = uc - 0.5 * (1.0 + P.dtdx * uc) * ldux;
-    double vxl = vc + 0.5 * (1.0 - P.dtdx * uc) * ldvx;
-    double vxr = vc - 0.5 * (1.0 + P.dtdx * uc) * ldvx;
-    double uyl = uc + 0.5 * (1.0 - P.dtdy * vc) * lduy;
-    double uyr = uc - 0.5 * (1.0 + P.dtdy * vc) * lduy;
-    double vyl = vc + 0.5 * (1.0 - P.dtdy * vc) * ldvy;
-    double vyr = vc - 0.5 * (1.0 + P.dtdy * vc) * ldvy;
+    const BgHat hu = bg_hat(uc, ldux, lduy, uc, vc, P.dtdx, P.dtdy);
+    const BgHat hv = bg_hat(vc, ldvx, ldvy, uc, vc, P.dtdx, P.dtdy);
+    double uxl = hu.xl, uxr = hu.xr, uyl = hu.yl, uyr = hu.yr;
+    double vxl = hv.xl, vxr = hv.xr, vyl = hv.yl, vyr = hv.yr;
     if (P.eps != 0.0) {   // apply_diffusion_corrections, burgers_viscous/interface.py:94-171
         const double dx2 = P.dx * P.dx, dy2 = P.dy * P.dy;
         const double lu = (u[k + p] - 2.0 * uc + u[k - p]) / dx2 + (u[k + 1] - 2.0 * uc + u[k - 1]) / dy2;
@@ -129,12 +113,9 @@ __global__ __launch_bounds__(256) void k_bg_trans(const double *__restrict__ u,
         sy = 0.5 * P.dt * lv;
     }
     if (jin) {   // x states: transverse (y) derivative over the cell
-        const double vh0 = bg_riemann(vyl[k], vyr[k]), vh1 = bg_riemann(vyl[k + 1], vyr[k + 1]);
-        const double vbar = 0.5 * (vh0 + vh1);
-        const double uy0 = bg_upwind(uyl[k], uyr[k], vh0), uy1 = bg_upwind(uyl[k + 1], uyr[k + 1], vh1);
-        const double vy0 = bg_upwind(vyl[k], vyr[k], vh0), vy1 = bg_upwind(vyl[k + 1], vyr[k + 1], vh1);
-        const double tu = -0.5 * P.dtdy * vbar * (uy1 - uy0);
-        const double tv = -0.5 * P.dtdy * vbar * (vy1 - vy0);
+        double tu, tv;
+        bg_transverse(P.dtdy, vyl[k], vyr[k], vyl[k + 1], vyr[k + 1], uyl[k], uyr[k], uyl[k + 1], uyr[k + 1],
+                      vyl[k], vyr[k], vyl[k + 1], vyr[k + 1], tu, tv);
         double a = uxl[k + p] + tu, b = uxr[k] + tu, c = vxl[k + p] + tv, d = vxr[k] + tv;
         if (gpx) { a += gx; b += gx; c += gy; d += gy; }
         if (src) { a += sx; b += sx; c += sy; d += sy; }
@@ -142,12 +123,9 @@ __global__ __launch_bounds__(256) void k_bg_trans(const double *__restrict__ u,
         W[C_VXL * pl + k + p] = c; W[C_VXR * pl + k] = d;
     }
     if (iin) {   // y states: transverse (x) derivative over the cell
-        const double uh0 = bg_riemann(uxl[k], uxr[k]), uh1 = bg_riemann(uxl[k + p], uxr[k + p]);
-        const double ubar = 0.5 * (uh0 + uh1);
-        const double vx0 = bg_upwind(vxl[k], vxr[k], uh0), vx1 = bg_upwind(vxl[k + p], vxr[k + p], uh1);
-        const double ux0 = bg_upwind(uxl[k], uxr[k], uh0), ux1 = bg_upwind(uxl[k + p], uxr[k + p], uh1);
-        const double sv = -0.5 * P.dtdx * ubar * (vx1 - vx0);
-        const double su = -0.5 * P.dtdx * ubar * (ux1 - ux0);
+        double sv, su;
+        bg_transverse(P.dtdx, uxl[k], uxr[k], uxl[k + p], uxr[k + p], vxl[k], vxr[k], vxl[k + p], vxr[k + p],
+                      uxl[k], uxr[k], uxl[k + p], uxr[k + p], sv, su);
         double a = vyl[k + 1] + sv, b = vyr[k] + sv, c = uyl[k + 1] + su, d = uyr[k] + su;
         if (gpx) { a += gy; b += gy; c += gx; d += gx; }
         if (src) { a += sy; b += sy; c += sx; d += sx; }
@@ -172,11 +150,11 @@ __global__ __launch_bounds__(256) void k_bg_mac(double *__restrict__ W, Geom g)
     BG_FACE()
     if (j <= g.jhi) {
         const double l = W[C_UXL * pl + k], r = W[C_UXR * pl + k];
-        W[W_UMAC * pl + k] = bg_upwind(l, r, bg_riemann(l, r));
+        W[W_UMAC * pl + k] = bg_mac(l, r);
     }
     if (i <= g.ihi) {
         const double l = W[C_VYL * pl + k], r = W[C_VYR * pl + k];
-        W[W_VMAC * pl + k] = bg_upwind(l, r, bg_riemann(l, r));
+        W[W_VMAC * pl + k] = bg_mac(l, r);
     }
 }
 
@@ -192,10 +170,10 @@ __global__ __launch_bounds__(256) void k_bg_update(double *__restrict__ u, doubl
     const size_t k = (size_t)i * p + j;
     const double *um = W + W_UMAC * pl, *vm = W + W_VMAC * pl;
     auto fx = [&](int plane_l, int plane_r, size_t kk) {
-        return 0.5 * bg_upwind(W[plane_l * pl + kk], W[plane_r * pl + kk], um[kk]) * um[kk];
+        return bg_flux(W[plane_l * pl + kk], W[plane_r * pl + kk], um[kk]);
     };
     auto fy = [&](int plane_l, int plane_r, size_t kk) {
-        return 0.5 * bg_upwind(W[plane_l * pl + kk], W[plane_r * pl + kk], vm[kk]) * vm[kk];
+        return bg_flux(W[plane_l * pl + kk], W[plane_r * pl + kk], vm[kk]);
     };
     u[k] = u[k] + P.dtdx * (fx(C_UXL, C_UXR, k) - fx(C_UXL, C_UXR, k + p)) +
            P.dtdy * (fy(C_UYL, C_UYR, k) - fy(C_UYL, C_UYR, k + 1));
@@ -348,8 +326,8 @@ __global__ __launch_bounds__(256) void k_bgv_rhs(const double *__restrict__ w,
     const double *um = W + W_UMAC * pl, *vm = W + W_VMAC * pl;
     const int XL = comp ? C_VXL : C_UXL, XR = comp ? C_VXR : C_UXR;
     const int YL = comp ? C_VYL : C_UYL, YR = comp ? C_VYR : C_UYR;
-    auto fx = [&](size_t kk) { return 0.5 * bg_upwind(W[XL * pl + kk], W[XR * pl + kk], um[kk]) * um[kk]; };
-    auto fy = [&](size_t kk) { return 0.5 * bg_upwind(W[YL * pl + kk], W[YR * pl + kk], vm[kk]) * vm[kk]; };
+    auto fx = [&](size_t kk) { return bg_flux(W[XL * pl + kk], W[XR * pl + kk], um[kk]); };
+    auto fy = [&](size_t kk) { return bg_flux(W[YL * pl + kk], W[YR * pl + kk], vm[kk]); };
     const double A = (fx(k + p) - fx(k)) / P.dx + (fy(k + 1) - fy(k)) / P.dy;
     const double a = w[k];
     const double lap = (w[k + p] - 2.0 * a + w[k - p]) / (P.dx * P.dx) +

@@ -327,6 +327,20 @@ class DeviceState:
             check(self._l.pyrohip_bg_step(self.h, int(iu), int(iv), float(dx), float(dy),
                                           float(dt), int(limiter)))
 
+    def bg_step1(self, iu, iv, dx, dy, dt, limiter):
+        """the same step in one launch (csrc/burgers.hip): writes the state's second buffer and
+        exchanges the two; the whole array ends up as bg_step leaves it"""
+        with self.ctx.lock:
+            check(self._l.pyrohip_bg_step1(self.h, int(iu), int(iv), float(dx), float(dy),
+                                           float(dt), int(limiter)))
+
+    def bg_evolve(self, iu, iv, dx, dy, limiter, cfl, policy, max_steps, particles=None):
+        """up to max_steps burgers steps with the driver's dt policy on the device (as
+        swe_evolve); returns the dt of the steps taken"""
+        return self._evolve(policy, max_steps, "pyrohip_bg_evolve",
+                            (self.h, int(iu), int(iv), float(dx), float(dy), int(limiter), float(cfl)),
+                            particles)
+
     def inc_mac_rhs(self, mg, iu, iv, igpx, igpy, dx, dy, dt, limiter, nu=0.0):
         out = C.c_double()
         with self.ctx.lock:
