@@ -683,6 +683,14 @@ int pyrohip_swe_evolve(pyrohip_state *s, double dx, double dy, double grav, int 
 /* test hook: 0-3 U_xl U_xr U_yl U_yr before the transverse terms, 4 FxT 5 FyT
    (transverse fluxes), 6 Fx 7 Fy -> host (qx, qy, 4)                        */
 int pyrohip_swe_stage_dump(pyrohip_state *s, int stage, double *out);
+/* the launch geometry of the one-launch step (k_sw_wave) on an nx x ny grid on a device of
+   num_cus compute units (<= 0: 256), without launching anything: out6 = { column strips (58
+   updated columns each), rows per regular row strip, row strips, n_extra (the column strips
+   [0, n_extra) are cut into row strips + 1 equal parts instead), wavefronts per launch,
+   wavefronts resident at once }.  The code pyrohip_swe_step_ex and pyrohip_swe_evolve go by.
+   ng is checked (>= 0) and otherwise unused: the geometry depends on the interior alone; the
+   argument keeps the call shaped like pyrohip_comp_wave_geometry. */
+int pyrohip_swe_wave_geometry(int nx, int ny, int ng, int num_cus, int *out6);
 
 /* ---- burgers / incompressible (the solvers on top of the multigrid solver;
         SURVEY.md 8 rows f1, f4) ------------------------------------------- */

@@ -646,6 +646,76 @@ def gen_swe():
          bc=bc_names(p.rp), tmax=np.array(p.sim.tmax), riemann=np.array("Roe"))
 
 
+def gen_swe_edge():
+    """one HLLC step without limiting (swe.limiter = 0) on piecewise-constant blocks with height
+    ratios up to 16: face states of NEGATIVE height, where riemann_hllc's max(smallc, sqrt(g h)) is
+    Python's max of a NaN (smallc) and its shock speeds are NaN (every comparison false) -- and the
+    step stays finite.  The state covers the whole array, ghost cells included; no boundary fill."""
+    import pyro.swe as swe
+    import pyro.swe.interface as sifc
+    import pyro.swe.unsplit_fluxes as sflx
+    nx, ny = 12, 20
+    p = Pyro("swe")
+    p.initialize_problem("quad", inputs_dict={"mesh.nx": nx, "mesh.ny": ny, "mesh.xmax": 0.6, "mesh.ymax": 1.3,
+                                              "swe.riemann": "HLLC", "swe.limiter": 0, "swe.grav": 2.0})
+    sim = p.sim
+    rp, ivars, myg = sim.rp, sim.ivars, sim.cc_data.grid
+    # (h, u, v, X) per block; blocks of 3 x 3 cells from the array's corner, the picks written out
+    states = np.array([[1.0, 0.0, 0.0, 1.0], [0.25, 0.3, -0.2, 0.1], [4.0, -0.5, 0.4, 0.7],
+                       [0.5, 2.5, -2.5, 0.3], [2.0, -3.0, 3.0, 0.9], [0.25, -0.1, 0.2, 0.5],
+                       [4.0, 0.7, -0.6, 0.2], [1.5, 0.2, 1.9, 0.6]])
+    pick = np.array([[0, 2, 1, 6, 5, 2, 3, 1, 4, 0],
+                     [5, 1, 2, 0, 6, 1, 7, 2, 5, 6],
+                     [2, 6, 5, 4, 1, 0, 2, 1, 6, 3],
+                     [1, 0, 6, 1, 2, 5, 1, 6, 0, 2],
+                     [6, 3, 1, 2, 7, 6, 0, 5, 2, 1],
+                     [0, 5, 2, 6, 1, 2, 4, 1, 6, 5],
+                     [2, 1, 7, 5, 6, 1, 2, 0, 1, 6]])
+    S = states[pick[np.arange(myg.qx) // 3][:, np.arange(myg.qy) // 3]]
+    U = sim.cc_data.data
+    U[:, :, ivars.ih] = S[..., 0]
+    U[:, :, ivars.ixmom] = S[..., 0] * S[..., 1]
+    U[:, :, ivars.iymom] = S[..., 0] * S[..., 2]
+    U[:, :, ivars.ihx] = S[..., 0] * S[..., 3]
+    sim.method_compute_timestep()
+    dt = sim.dt
+    g = rp.get_param("swe.grav")
+    out = {"U0": np.array(U), "dt": np.array(dt), "riemann": np.array("HLLC"),
+           "meta": np.array([myg.nx, myg.ny, myg.ng, myg.dx, myg.dy, g, 0, rp.get_param("driver.cfl")])}
+    q = swe.cons_to_prim(U, ivars, myg)
+    ldx = myg.scratch_array(nvar=ivars.nvar)
+    ldy = myg.scratch_array(nvar=ivars.nvar)
+    for n in range(ivars.nvar):
+        ldx[:, :, n] = reconstruction.limit(q[:, :, n], myg, 1, 0)
+        ldy[:, :, n] = reconstruction.limit(q[:, :, n], myg, 2, 0)
+    args = (ivars.ih, ivars.iu, ivars.iv, ivars.ix, ivars.naux, g)
+    V_l, V_r = sifc.states(1, myg.ng, myg.dx, dt, *args, q, ldx)
+    out["Uxl0"] = np.array(swe.prim_to_cons(V_l, ivars, myg))
+    out["Uxr0"] = np.array(swe.prim_to_cons(V_r, ivars, myg))
+    V_l, V_r = sifc.states(2, myg.ng, myg.dy, dt, *args, q, ldy)
+    out["Uyl0"] = np.array(swe.prim_to_cons(ai.ArrayIndexer(d=V_l, grid=myg), ivars, myg))
+    out["Uyr0"] = np.array(swe.prim_to_cons(ai.ArrayIndexer(d=V_r, grid=myg), ivars, myg))
+    rargs = (ivars.ih, ivars.ixmom, ivars.iymom, ivars.ihx, ivars.naux)
+    out["FxT"] = np.array(sifc.riemann_hllc(1, myg.ng, *rargs, sim.solid.xl, sim.solid.xr, g, out["Uxl0"], out["Uxr0"]))
+    out["FyT"] = np.array(sifc.riemann_hllc(2, myg.ng, *rargs, sim.solid.yl, sim.solid.yr, g, out["Uyl0"], out["Uyr0"]))
+    Fx, Fy = sflx.unsplit_fluxes(sim.cc_data, rp, ivars, sim.solid, sim.tc, dt)
+    out["Fx"], out["Fy"] = np.array(Fx), np.array(Fy)
+    sim.evolve()
+    out["U1"] = np.array(sim.cc_data.data)
+    # the case is what it is for: negative face heights in both directions (on faces the update
+    # uses), a finite result
+    b = myg.ng
+    fx = (slice(b, b + nx + 1), slice(b, b + ny))
+    fy = (slice(b, b + nx), slice(b, b + ny + 1))
+    nneg = [int((out[l][sl + (0,)] < 0).sum() + (out[r][sl + (0,)] < 0).sum())
+            for l, r, sl in (("Uxl0", "Uxr0", fx), ("Uyl0", "Uyr0", fy))]
+    print("swe_edge: dt", dt, "faces of negative height (x, y)", nneg)
+    assert min(nneg) > 0, nneg
+    assert np.isfinite(out["U1"]).all()
+    assert np.abs(out["U1"] - out["U0"])[b:-b, b:-b].max() > 1e-3
+    save("swe_edge", **out)
+
+
 def gen_mg_4096():
     """BASELINE config 4 at full size: the reference's CellCenterMG2d(4096^2),
     10 V-cycles.  The solution does not fit a fixture, so
@@ -1459,6 +1529,8 @@ if __name__ == "__main__":
         gen_compressible_rk()
     if "swe" in sys.argv[1:]:
         gen_swe()
+    if "swe_edge" in sys.argv[1:]:
+        gen_swe_edge()
     if "mg_4096" in sys.argv[1:]:
         gen_mg_4096()
     if "diff_2048" in sys.argv[1:]:

@@ -497,7 +497,17 @@ def swe_dt(U, P, cfl):
              C.c_double(cfl))
 
 
-def swe_step(U, P, dt, stages=False):
+SWE_NCNT = 22     # counters per direction (pyro_oracle.c: ORC_SWE_NCNT)
+
+
+def swe_step(U, P, dt, stages=False, counts=False):
+    """one step in place; returns the stage dict (empty without stages), with counts=True
+    (stages, counts): counts[d] for d = 0 (x), 1 (y), a dict of what the step went through in
+    the oracle -- both Riemann passes: "hllc_exit" faces per HLLC exit (S_r <= 0; S_c <= 0 < S_r;
+    S_l < 0 < S_c; fall-through), "shock_l" / "shock_r" HLLC faces with the shock form of S_l /
+    S_r, "h_l_nonpos" / "h_r_nonpos" faces with a non-positive left / right height, "hh_fix0" /
+    "hh_fix2" Roe faces whose lambda[0] / lambda[2] the Harten-Hyman fix rewrites, "e_val"
+    3 x 4 cells of the tracing per sign class (positive, negative, +0, -0) of e_val[0..2]"""
     _ck(U)
     st = SweStages()
     outs = {}
@@ -505,8 +515,18 @@ def swe_step(U, P, dt, stages=False):
         for n, _t in SweStages._fields_:
             outs[n] = np.zeros_like(U)
             setattr(st, n, _p(outs[n]))
-    lib().orc_swe_step(_p(U), C.byref(P), C.c_double(dt), C.byref(st) if stages else None)
-    return outs
+    if not counts:
+        lib().orc_swe_step(_p(U), C.byref(P), C.c_double(dt), C.byref(st) if stages else None)
+        return outs
+    cnt = (C.c_long * (2 * SWE_NCNT))()
+    lib().orc_swe_step_counts(_p(U), C.byref(P), C.c_double(dt), C.byref(st) if stages else None, cnt)
+    res = []
+    for d in range(2):
+        c = [int(v) for v in cnt[d * SWE_NCNT:(d + 1) * SWE_NCNT]]
+        res.append({"hllc_exit": tuple(c[0:4]), "shock_l": c[4], "shock_r": c[5], "h_l_nonpos": c[6],
+                    "h_r_nonpos": c[7], "hh_fix0": c[8], "hh_fix2": c[9],
+                    "e_val": tuple(tuple(c[10 + 4 * m:14 + 4 * m]) for m in range(3))})
+    return outs, res
 
 
 class GenMG(VCMG):

@@ -2608,6 +2608,18 @@ typedef struct {
     int riemann;     /* 0 Roe, 1 HLLC */
 } orc_swe_params;
 
+/* What a step went through (orc_swe_step_counts; NULL: not counted), per direction d = idir - 1
+   at swe_cnt[ORC_SWE_NCNT * d + ...]; the two Riemann passes of a step (transverse, final) both count:
+     0..3   HLLC faces per exit: S_r <= 0; S_c <= 0 < S_r; S_l < 0 < S_c; fall-through
+     4, 5   HLLC faces with the shock form of S_l, of S_r
+     6, 7   faces (either solver) with a non-positive left, right height
+     8, 9   Roe faces where the Harten-Hyman fix rewrites lambda[0], lambda[2]
+     10 + 4 m + s   cells of the tracing by the sign of e_val[m], m = 0..2: s = 0 positive,
+            1 negative, 2 +0, 3 -0 */
+#define ORC_SWE_NCNT 22
+static long *swe_cnt = NULL;
+#define SWE_COUNT(idir, k) do { if (swe_cnt) swe_cnt[ORC_SWE_NCNT * ((idir) - 1) + (k)]++; } while (0)
+
 /* interface.py:557-578 */
 static void swe_cons_flux(int idir, double g, const double *U, double *F)
 {
@@ -2665,12 +2677,16 @@ static void swe_states(int idir, int nx, int ny, int ng, double dx, double dt, d
                 lvec[0][k] = lvec[0][k] * 0.50 / (cs * q[0]);
                 lvec[2][k] = -lvec[2][k] * 0.50 / (cs * q[0]);
             }
+            for (int m = 0; m < 3; m++) {
+                const double e = e_val[m];
+                if (e == e) SWE_COUNT(idir, 10 + 4 * m + (e > 0.0 ? 0 : e < 0.0 ? 1 : signbit(e) ? 3 : 2));
+            }
             double *ql = (idir == 1) ? q_l + ((size_t)(i + 1) * qy + j) * 4
                                      : q_l + ((size_t)i * qy + (j + 1)) * 4;
             double *qr = q_r + ((size_t)i * qy + j) * 4;
-            double factor = 0.5 * (1.0 - dtdx * dmax(e_val[2], 0.0));
+            double factor = 0.5 * (1.0 - dtdx * pymax(e_val[2], 0.0));
             for (int m = 0; m < 4; m++) ql[m] = q[m] + factor * dq[m];
-            factor = 0.5 * (1.0 + dtdx * dmin(e_val[0], 0.0));
+            factor = 0.5 * (1.0 + dtdx * pymin(e_val[0], 0.0));
             for (int m = 0; m < 4; m++) qr[m] = q[m] - factor * dq[m];
             for (int m = 0; m < 4; m++) {
                 double asum = 0.0;
@@ -2705,7 +2721,10 @@ static void swe_riemann_roe(int idir, int nx, int ny, int ng, double g, const do
             double *Fo = F + ((size_t)i * qy + j) * 4;
             const double h_l = Ul[SH], un_l = Ul[im] / h_l;
             const double h_r = Ur[SH], un_r = Ur[im] / h_r;
-            const double c_l = dmax(smallc, sqrt(g * h_l)), c_r = dmax(smallc, sqrt(g * h_r));
+            /* Python's max(smallc, x): smallc where the root is NaN (h < 0) */
+            const double c_l = pymax(smallc, sqrt(g * h_l)), c_r = pymax(smallc, sqrt(g * h_r));
+            if (h_l <= 0.0) SWE_COUNT(idir, 6);
+            if (h_r <= 0.0) SWE_COUNT(idir, 7);
             double U_roe[4], delta[4], lambda[4], alpha[4], K[4][4];
             for (int n = 0; n < 4; n++) {
                 U_roe[n] = (Ul[n] / sqrt(h_l) + Ur[n] / sqrt(h_r)) / (sqrt(h_l) + sqrt(h_r));
@@ -2742,6 +2761,8 @@ static void swe_riemann_roe(int idir, int nx, int ny, int ng, double g, const do
             const double h_star = 1.0 / g * SQ(0.5 * (c_l + c_r) + 0.25 * (un_l - un_r));
             const double u_star = 0.5 * (un_l + un_r) + c_l - c_r;
             const double c_star = sqrt(g * h_star);
+            if (fabs(lambda[0]) < tol) SWE_COUNT(idir, 8);
+            if (fabs(lambda[2]) < tol) SWE_COUNT(idir, 9);
             if (fabs(lambda[0]) < tol)
                 lambda[0] = lambda[0] * (u_star - c_star - lambda[0]) /
                             (u_star - c_star - (un_l - c_l));
@@ -2769,7 +2790,10 @@ static void swe_riemann_hllc(int idir, int nx, int ny, int ng, double g, const d
             double *Fo = F + ((size_t)i * qy + j) * 4;
             const double h_l = Ul[SH], un_l = Ul[im] / h_l, ut_l = Ul[it] / h_l;
             const double h_r = Ur[SH], un_r = Ur[im] / h_r, ut_r = Ur[it] / h_r;
-            const double c_l = dmax(smallc, sqrt(g * h_l)), c_r = dmax(smallc, sqrt(g * h_r));
+            /* Python's max(smallc, x): smallc where the root is NaN (h < 0) */
+            const double c_l = pymax(smallc, sqrt(g * h_l)), c_r = pymax(smallc, sqrt(g * h_r));
+            if (h_l <= 0.0) SWE_COUNT(idir, 6);
+            if (h_r <= 0.0) SWE_COUNT(idir, 7);
             const double h_avg = 0.5 * (h_l + h_r), c_avg = 0.5 * (c_l + c_r);
             const double hstar = h_avg - 0.25 * (un_r - un_l) * h_avg / c_avg;
             const double S_l = (hstar <= h_l) ? un_l - c_l
@@ -2779,6 +2803,9 @@ static void swe_riemann_hllc(int idir, int nx, int ny, int ng, double g, const d
             const double S_c = (S_l * h_r * (un_r - S_r) - S_r * h_l * (un_l - S_l)) /
                                (h_r * (un_r - S_r) - h_l * (un_l - S_l));
             double Us[4];
+            if (!(hstar <= h_l)) SWE_COUNT(idir, 4);
+            if (!(hstar <= h_r)) SWE_COUNT(idir, 5);
+            SWE_COUNT(idir, S_r <= 0.0 ? 0 : (S_c <= 0.0 && 0.0 < S_r) ? 1 : (S_l < 0.0 && 0.0 < S_c) ? 2 : 3);
             if (S_r <= 0.0) {
                 swe_cons_flux(idir, g, Ur, Fo);
             } else if (S_c <= 0.0 && 0.0 < S_r) {
@@ -2828,10 +2855,12 @@ double orc_swe_dt(const double *U, int nx, int ny, int ng, double dx, double dy,
     for (size_t k = 0; k < N; k++) {
         const double h = U[k * 4 + SH], u = U[k * 4 + SMX] / h, v = U[k * 4 + SMY] / h;
         const double cs = sqrt(g * h);
-        xm = dmin(xm, dx / (fabs(u) + cs));
-        ym = dmin(ym, dy / (fabs(v) + cs));
+        /* ndarray.min(): a NaN stays */
+        const double xt = dx / (fabs(u) + cs), yt = dy / (fabs(v) + cs);
+        xm = (xm != xm || xt != xt) ? NAN : dmin(xm, xt);
+        ym = (ym != ym || yt != yt) ? NAN : dmin(ym, yt);
     }
-    return cfl * dmin(xm, ym);
+    return cfl * pymin(xm, ym);     /* Python's min(xtmp.min(), ytmp.min()) */
 }
 
 typedef struct {
@@ -2901,6 +2930,15 @@ void orc_swe_step(double *U, const orc_swe_params *P, double dt, orc_swe_stages 
 #undef U4
     free(q); free(ldx); free(ldy); free(tmp); free(V_l); free(V_r);
     free(Uxl); free(Uxr); free(Uyl); free(Uyr); free(Fx); free(Fy);
+}
+
+/* the same step, counting into counts[2 * ORC_SWE_NCNT] (zeroed here; not thread-safe) */
+void orc_swe_step_counts(double *U, const orc_swe_params *P, double dt, orc_swe_stages *st, long *counts)
+{
+    memset(counts, 0, sizeof(long) * 2 * ORC_SWE_NCNT);
+    swe_cnt = counts;
+    orc_swe_step(U, P, dt, st);
+    swe_cnt = NULL;
 }
 #undef SQ
 

@@ -158,6 +158,7 @@ _PROTOS = {
     "pyrohip_swe_evolve": [_VP, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_double,
                            C.POINTER(DtPolicyC), C.c_int, C.POINTER(C.c_int), _DP],
     "pyrohip_swe_stage_dump": [_VP, C.c_int, _DP],
+    "pyrohip_swe_wave_geometry": [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)],
     "pyrohip_bg_step": [_VP, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int],
     "pyrohip_bg_step1": [_VP, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int],
     "pyrohip_bg_evolve": [_VP, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double,

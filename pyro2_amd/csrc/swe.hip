@@ -337,10 +337,21 @@ __device__ __forceinline__ V4 sw_hllc(const V4 &Ul, const V4 &Ur, double g, bool
     const double c_l = fmax(smallc, psqrt(g * h_l)), c_r = fmax(smallc, psqrt(g * h_r));
     const double h_avg = 0.5 * (h_l + h_r), c_avg = 0.5 * (c_l + c_r);
     const double hstar = h_avg - pdiv(0.25 * (un_r - un_l) * h_avg, c_avg);
-    const double S_l = (hstar <= h_l) ? un_l - c_l
-                                      : un_l - pdiv(c_l * psqrt(0.5 * (hstar + h_l) * hstar), h_l);
-    const double S_r = (hstar <= h_r) ? un_r + c_r
-                                      : un_r + pdiv(c_r * psqrt(0.5 * (hstar + h_r) * hstar), h_r);
+    const double rad_l = 0.5 * (hstar + h_l) * hstar, rad_r = 0.5 * (hstar + h_r) * hstar;
+    const double S_l = (hstar <= h_l) ? un_l - c_l : un_l - pdiv(c_l * psqrt(rad_l), h_l);
+    const double S_r = (hstar <= h_r) ? un_r + c_r : un_r + pdiv(c_r * psqrt(rad_r), h_r);
+#if PYRO_FAST
+    // A negative radicand (face heights below zero: unlimited slopes at a large jump) is a NaN wave
+    // speed in the reference, and every comparison below is false for it: S_r NaN (and with it S_c)
+    // falls through to F(Ul); S_l NaN leaves only the first exit.  The contracted root returns 0
+    // there and this unit is compiled without NaN semantics, so the exits are taken from the
+    // radicands' signs (finite numbers; sqrt(-0) = -0 is no NaN).
+    // A right state of height exactly 0 (a supercritical cell's lower face: h - dq_h / 2 with dyadic
+    // heights) has u = 0 / 0 there -- or +-inf, and then 0 (inf - inf) in S_c: again no comparison holds.
+    const bool nan_l = !(hstar <= h_l) && rad_l < 0.0, nan_r = (!(hstar <= h_r) && rad_r < 0.0) || h_r == 0.0;
+    if (nan_r) return sw_cons_flux(Ul, g, x);
+    if (nan_l) return sw_cons_flux(S_r <= 0.0 ? Ur : Ul, g, x);
+#endif
     const double S_c = pdiv(S_l * h_r * (un_r - S_r) - S_r * h_l * (un_l - S_l),
                             h_r * (un_r - S_r) - h_l * (un_l - S_l));
     V4 Us, F;
@@ -851,6 +862,22 @@ static int sww_rows(int nx, int ncb, int cus)
     return best;
 }
 
+// the launch geometry of k_sw_wave on an nx x ny grid with `cus` compute units (0: 256): what the
+// step, the sizing of a device-side run's partials and pyrohip_swe_wave_geometry all go by
+struct SwwGeom { int ncb, L, nsb, n_extra, nunits, slots; };
+static SwwGeom sww_geometry(int nx, int ny, int cus)
+{
+    SwwGeom w;
+    if (cus <= 0) cus = 256;
+    w.slots = 8 * cus;
+    w.ncb = (ny + SWW_OUT - 1) / SWW_OUT;
+    w.L = sww_rows(nx, w.ncb, cus);
+    w.nsb = (nx + w.L - 1) / w.L;
+    w.n_extra = wave_fill_extra(w.ncb, w.nsb, nx, w.slots);
+    w.nunits = w.ncb * w.nsb + w.n_extra;
+    return w;
+}
+
 // ghost frame of the four planes from one buffer to the other (1-d grid: 2 ng blocks of
 // columns for the ghost rows, then row blocks for the ghost columns)
 __global__ __launch_bounds__(256) void k_sw_copy_frame(const double *__restrict__ src,
@@ -888,12 +915,9 @@ int swe_step_wave(pyrohip_state *s, double dx, double dy, double grav, int limit
     const Geom &g = s->g;
     PYRO_TRY(state_alt(s));
     SWW P{dx, dy, dt, grav, limiter, 0, 0, 0, 0, 0, 0, nullptr, 0};
-    const int slots = 8 * (c->num_cus > 0 ? c->num_cus : 256);
-    P.ncb = (g.ny + SWW_OUT - 1) / SWW_OUT;
-    P.L = sww_rows(g.nx, P.ncb, c->num_cus > 0 ? c->num_cus : 256);
-    P.nsb = (g.nx + P.L - 1) / P.L;
-    P.n_extra = wave_fill_extra(P.ncb, P.nsb, g.nx, slots);
-    P.nunits = P.ncb * P.nsb + P.n_extra;
+    const SwwGeom w = sww_geometry(g.nx, g.ny, c->num_cus);
+    const int slots = w.slots;
+    P.ncb = w.ncb; P.L = w.L; P.nsb = w.nsb; P.n_extra = w.n_extra; P.nunits = w.nunits;
     if (nparts) *nparts = P.nunits;
     // one round of resident wavefronts: the pair of a SIMD ends together -- the one with more rows left
     // takes the priority (GPU; comp_wave.hip), turns by phase otherwise
@@ -929,10 +953,15 @@ int swe_step_wave(pyrohip_state *s, double dx, double dy, double grav, int limit
 // caller of a device-side run sizes the reduction buffer with it BEFORE the first launch
 int swe_wave_units(const Geom &g, int cus)
 {
-    const int ncb = (g.ny + SWW_OUT - 1) / SWW_OUT;
-    const int L = sww_rows(g.nx, ncb, cus > 0 ? cus : 256);
-    const int nsb = (g.nx + L - 1) / L;
-    return ncb * nsb + wave_fill_extra(ncb, nsb, g.nx, 8 * (cus > 0 ? cus : 256));
+    return sww_geometry(g.nx, g.ny, cus).nunits;
+}
+// (for callers that want to know before they launch: the tests that pick shapes for every path of
+// the kernel's unit decoding)  out: ncb, L, nsb, n_extra, wavefronts, resident slots
+int swe_wave_geometry(int nx, int ny, int cus, int *out)
+{
+    const SwwGeom w = sww_geometry(nx, ny, cus);
+    out[0] = w.ncb; out[1] = w.L; out[2] = w.nsb; out[3] = w.n_extra; out[4] = w.nunits; out[5] = w.slots;
+    return 0;
 }
 #endif
 
@@ -996,6 +1025,12 @@ int pyrohip_swe_dt(pyrohip_state *s, double dx, double dy, double grav, double c
     PYRO_CHECK_HIP(hipStreamSynchronize(c->stream));
     *dt_out = cfl * ((double *)c->reduce_host)[0];
     return 0;
+}
+
+int pyrohip_swe_wave_geometry(int nx, int ny, int ng, int num_cus, int *out6)
+{
+    PYRO_REQUIRE(out6 && nx >= 1 && ny >= 1 && ng >= 0, "bad argument");
+    return swx::swe_wave_geometry(nx, ny, num_cus, out6);
 }
 
 // kernel_set: 0 the staged kernels (every stage dumpable: pyrohip_swe_stage_dump), 1 the whole

@@ -117,6 +117,26 @@ for rs in ("Roe", "HLLC"):
     ref = Uw[4:-4, 4:-4]
     out["swe_" + rs] = float(max(np.abs(U[..., n] - ref[..., n]).max() / max(np.abs(ref[..., n]).max(), 1e-300)
                                  for n in range(3)))
+
+# ... and one step of HLLC without limiting on piecewise-constant blocks (21 x 117; tests/swe_cases.py):
+# faces of negative height, whose shock speed is the root of a negative number in the reference --
+# a NaN that selects its exits -- and 0 from the contracted root
+import swe_cases as sc
+shape = (21, 117)
+dxb, dyb, gb = sc.shape_params(shape)
+seams = sc.row_seams(shape[0], [device.swe_wave_geometry(shape[0], shape[1], 4, cus) for cus in (4, 256)])
+Ub = sc.make_state("blocks", shape[0], shape[1], gb, sc.state_seed(shape, "blocks"), seams)
+Pb = orc.swe_params(shape[0], shape[1], 4, dxb, dyb, gb, 0, "HLLC")
+dtb = orc.swe_dt(Ub, Pb, 0.8)
+Uo = Ub.copy()
+_, cnt = orc.swe_step(Uo, Pb, dtb, counts=True)
+assert np.isfinite(Uo).all() and min(c["h_l_nonpos"] + c["h_r_nonpos"] for c in cnt) > 0
+s = device.DeviceState(ctx, shape[0], shape[1], 4, [["outflow"] * 4] * 4)
+s.upload(Ub)
+s.swe_step(dxb, dyb, gb, 0, "HLLC", dtb, fast_math=1)
+U = s.download()[4:-4, 4:-4]
+ref = Uo[4:-4, 4:-4]
+out["swe_blocks_HLLC0"] = float((np.abs(U - ref) / (np.abs(ref) + np.array([1.0, 0.1, 0.1, 0.1]))).max())
 print("RESULT " + json.dumps(out))
 '''
 
@@ -134,7 +154,7 @@ def test_contracted_builds_with_gpu_precision_quotients_on_the_emulator(tmp_path
     assert p.returncode == 0, p.stdout[-1500:] + p.stderr[-3000:]
     res = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:])
     print(res)
-    for k in ("comp_ks1", "comp_ks2", "comp_ks1_evolve", "comp_ks2_evolve", "rk4", "swe_Roe", "swe_HLLC"):
+    for k in ("comp_ks1", "comp_ks2", "comp_ks1_evolve", "comp_ks2_evolve", "rk4", "swe_Roe", "swe_HLLC", "swe_blocks_HLLC0"):
         assert res[k] <= 1e-10, (k, res)
     assert res["comp_ks1_dt"] <= 1e-10 and res["comp_ks2_dt"] <= 1e-10
     assert res["adv"] <= 1e-12, res

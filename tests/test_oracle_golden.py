@@ -568,6 +568,58 @@ def test_oracle_swe(golden, k):
     assert np.abs(U[I] - g[pre + "final"][I]).max() < 1e-13
 
 
+def test_oracle_swe_edge(golden):
+    """one HLLC step without limiting on blocks with height ratios up to 16 (gen_golden.py:
+    gen_swe_edge): face states of negative height.  riemann_hllc's max(smallc, sqrt(g h)) is
+    Python's max -- smallc for the NaN root -- and its NaN shock speeds fail every comparison;
+    the oracle follows it bit for bit (libm-pow mode, as test_oracle_swe), stages and new state"""
+    g = golden("swe_edge")
+    P, _ = _swe_params(g, "")
+    ng = P.ng
+    I = (slice(ng, -ng), slice(ng, -ng))
+    assert (g["Uxl0"][ng:-ng + 1, ng:-ng, 0] < 0).any() and (g["Uyr0"][ng:-ng, ng:-ng + 1, 0] < 0).any()
+    assert np.isfinite(g["U1"]).all()
+    orc.set_scalar_pow(1)
+    try:
+        U = g["U0"].copy()
+        st, counts = orc.swe_step(U, P, float(g["dt"]), stages=True, counts=True)
+        assert float(g["dt"]) == orc.swe_dt(g["U0"], P, float(g["meta"][7]))
+        for nm in ("Uxl0", "Uxr0", "Uyl0", "Uyr0", "FxT", "FyT", "Fx", "Fy"):
+            assert np.array_equal(st[nm], g[nm]), nm
+        assert np.array_equal(U[I], g["U1"][I])
+        assert min(c["h_l_nonpos"] + c["h_r_nonpos"] for c in counts) > 0
+    finally:
+        orc.set_scalar_pow(0)
+    U = g["U0"].copy()
+    orc.swe_step(U, P, float(g["dt"]))
+    assert np.abs(U[I] - g["U1"][I]).max() < 1e-13
+
+
+def test_oracle_swe_dt_hands_on_nan(golden):
+    """compute_timestep is cfl * min(xtmp.min(), ytmp.min()) (swe/simulation.py:167-171):
+    ndarray.min() hands a NaN on, Python's min(a, b) keeps a unless b < a.  So a NaN cell
+    whose x quotient is NaN gives NaN, and one where only the y quotient is NaN (the second
+    argument) leaves the x minimum"""
+    g = golden("swe_edge")
+    P, cfl = _swe_params(g, "")
+    U = g["U0"].copy()
+    good = orc.swe_dt(U, P, cfl)
+    assert np.isfinite(good)
+
+    def numpy_dt(U):
+        with np.errstate(invalid="ignore", divide="ignore"):
+            h, u, v = U[..., 0], U[..., 1] / U[..., 0], U[..., 2] / U[..., 0]
+            cs = np.sqrt(P.g * h)
+            return cfl * float(min((P.dx / (abs(u) + cs)).min(), (P.dy / (abs(v) + cs)).min()))
+    Un = U.copy()
+    Un[5, 7, 0] = -1.0                    # sqrt(g h) is NaN: both quotients
+    assert np.isnan(numpy_dt(Un)) and np.isnan(orc.swe_dt(Un, P, cfl))
+    Uy = U.copy()
+    Uy[5, 7, 2] = np.nan                  # only v: Python's min keeps the x minimum
+    want = numpy_dt(Uy)
+    assert np.isfinite(want) and orc.swe_dt(Uy, P, cfl) == want
+
+
 def test_swe_reference_regression_dam(golden):
     """pyro/test.py:113: swe dam inputs.dam.x vs dam_x_0081.h5 (128x10, 81
     steps, Roe): oracle from the reference's IC against the stored golden"""
