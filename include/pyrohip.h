@@ -412,10 +412,18 @@ typedef struct {
    previous step left in device memory, the step kernels take dt from device
    memory.  Steps past tmax do nothing.  One synchronisation at the end returns
    the number of steps taken, the policy state and (dts_out, may be NULL, max_steps
-   doubles) the dt of each step (-1 for the ones not taken).  Cartesian grids,
-   outflow / reflect / periodic / halo boundaries, kernel sets -1 / 1 / 2, no
-   sponge.  PYROHIP_ERR_STATE: a step found an invalid state; the state left
-   behind is the one before that step, like after a failed pyrohip_comp_step. */
+   doubles) the dt of each step (-1 for the ones not taken).  Outflow / reflect /
+   periodic / halo boundaries, kernel sets -1 / 1 / 2.  On a single Cartesian domain
+   also the stratified atmospheres: hse y sides, ambient on the upper
+   y side (pyrohip_state_set_user_bc), gravity, a heating profile and the sponge --
+   one fill launch per step that also leaves the CFL minimum of the ghost frame, the
+   sponge as a launch behind the step; bit-identical to the same steps taken singly,
+   ghost frame included, and no cached minimum is left behind.  Refused with a
+   "device-side stepping:" message: the ramp boundary, a host-evaluated source,
+   hse / ambient sides or the sponge on a slab, on a SphericalPolar grid or with a
+   tracer set (pyrohip_comp_evolve_p).  PYROHIP_ERR_STATE: a step found an invalid
+   state; the state left behind is the one before that step, like after a failed
+   pyrohip_comp_step. */
 int pyrohip_comp_evolve(pyrohip_state *s, const pyrohip_comp_params *p, double cfl,
                         pyrohip_dt_policy *policy, int max_steps, int *steps_done,
                         double *dts_out);

@@ -250,11 +250,21 @@ class Simulation(NullSimulation):
         self.n += 1
         tm.end()
 
+    def _sponge_on_device(self):
+        """no sponge, or one the device-side stepping loop carries: single Cartesian domain,
+        no tracer set"""
+        if not self.rp.get_param("sponge.do_sponge"):
+            return True
+        cc = self.cc_data
+        return cc.grid.coord_type == 0 and cc.slab is None and self.particles is None
+
     def can_evolve_many(self):
         """may the driver hand several steps at once to the device
-        (pyrohip_comp_evolve)?  Standard boundary types, no sponge, tracer particles only
-        where the device advances them (Cartesian grid), a fused kernel set, nothing watching
-        the data (a SphericalPolar grid: its one-launch step, i.e. no heating profile either)."""
+        (pyrohip_comp_evolve)?  Standard boundary types -- on a single Cartesian domain also
+        hse / ambient y sides and the sponge --, tracer particles only
+        where the device advances them (Cartesian grid, no sponge), a fused kernel set, nothing
+        watching the data (a SphericalPolar grid: its one-launch step, i.e. no heating profile
+        either)."""
         cc = self.cc_data
         if self._host_source():
             return False
@@ -262,11 +272,16 @@ class Simulation(NullSimulation):
             return False
         if cc.grid.coord_type != 0 and self._heating() is not None:
             return False
-        if self.rp.get_param("sponge.do_sponge") or type(self).evolve is not Simulation.evolve:
+        if type(self).evolve is not Simulation.evolve or not self._sponge_on_device():
             return False
         simple = ("outflow", "reflect-even", "reflect-odd", "periodic")
-        if not all(b in simple for n in cc.names for b in cc.BCs[n].sides()):
-            return False
+        sides = [b for n in cc.names for b in cc.BCs[n].sides()]
+        if not all(b in simple for b in sides):
+            # the stratified atmospheres: hse / ambient, where the device fills them
+            if not all(b in simple + ("hse", "ambient") for b in sides) or not cc._device_user_bc():
+                return False
+            if cc.grid.coord_type != 0 or cc.slab is not None:
+                return False
         if any(cc._has_host_bc(n) for n in cc.names) or cc._views_alive():
             return False
         if getattr(self, "_device_stepping_refused", False):
@@ -285,6 +300,7 @@ class Simulation(NullSimulation):
         def call(st, pol, cfl, n, particles):
             if self.cc_data.slab is not None:     # COLLECTIVE (no tracers: setup_particles refuses them)
                 return self._slab().evolve(pol, cfl, n, params=self._params())
+            self.cc_data._push_user_bc(st)        # (hse / ambient sides: gamma, grav, the ambient state)
             return st.comp_evolve(self._params(), cfl, pol, n, particles=particles)
         # (refusable: e.g. a SphericalPolar grid too small for the tile kernel, mixed boundary
         # kinds on a side -- the staged set can step those)

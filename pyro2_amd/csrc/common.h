@@ -103,6 +103,9 @@ struct pyrohip_ctx {
     // rows they have left (comp_wave.hip: wave_prio_feedback); [SIMD of the chip][wavefront slot], tagged per launch
     pyro::DevBuf prio_board;
     unsigned launch_seq = 0;
+    // device-side stepping of a stratified run (hse / ambient sides, the sponge): the CFL partials of
+    // the frame fill, then those of the sponge (comp_api.hip)
+    pyro::DevBuf strat;
     // tracer particle sets alive on this context (ctx.hip: particles_alloc / particles_release;
     // pyrohip_shutdown releases the device memory of those still here)
     std::vector<pyrohip_particles *> psets;
@@ -175,6 +178,8 @@ int comm_wait_halo(pyrohip_state *s);
 // plain ghost fill (x sides, then y sides) of cnt planes laid out like the
 // state's planes n0.. with the boundary types of those variables (ctx.hip)
 int fill_bc_planes(pyrohip_state *s, double *planes, int n0, int cnt);
+// the constant rows of the ambient boundary, by variable (ctx.hip; pyrohip_state_set_user_bc)
+void user_bc_ambient(const pyrohip_state *s, double out[4]);
 }  // namespace pyro
 
 // launch on the context's stream, bracketed by events when profiling is on
@@ -261,6 +266,17 @@ __device__ inline void dt_policy_apply(StepScalars *S, double cmin, bool invalid
     S->hdtV = (0.5 * dt) / (S->dx * S->dy);              // unsplit_fluxes.py:444-445
     S->dtdV = dt / (S->dx * S->dy);                      // simulation.py:375
     dts[slot] = go ? dt : -1.0;
+}
+
+// "Will the policy call that comes next let a step run?" -- dt_policy_apply's own test, for a
+// kernel that runs in front of that call and must do nothing on an inactive iteration (the frame
+// fill of a stratified run, compressible.hip).  invalid: the positivity flag of the step before.
+__device__ inline bool dt_policy_goes_on(const StepScalars *S, bool invalid)
+{
+    invalid = invalid || S->dead != 0;
+    double t = S->t;
+    if (S->active && !invalid) t += S->dt;
+    return !invalid && (t < S->tmax);
 }
 
 // The row-marching step kernel as the ONLY launch of a step (pyrohip_comp_evolve).  Nothing in
@@ -438,6 +454,13 @@ struct EvolveRun {
     const double *dmin = nullptr;     // device: the CFL minimum the next policy call takes ...
     const double *pend = nullptr;     // ... after reducing the last step's partials into it, if it left any
     int npend = 0;
+    // a stratified run (comp_api.hip): the CFL partials of the frame cells the fill in front of the
+    // next policy call wrote -- that call takes the minimum of both; its fills and its sponge keep
+    // still on inactive iterations, so the close leaves the frames alone (own_frames) and the
+    // minimum the run ends with, the interior's, is not the state's (whole array, hse ghost rows)
+    const double *fpart = nullptr;
+    int nfpart = 0;
+    bool own_frames = false;
     int cfl_kind = 0;                 // pyrohip_state::cfl_kind / cfl_par of the minimum the run leaves
     double cfl_par[3] = {0.0, 0.0, 0.0};
     bool halo_ok = false, sph_ok = false;     // what frame_fill_ok lets pass in this run

@@ -15,6 +15,10 @@ int comp_step_fused_ex(pyrohip_state *, const pyrohip_comp_params *, double, con
 int comp_step_wave_ex(pyrohip_state *, const pyrohip_comp_params *, double, const StepScalars *,
                       const double **);
 int comp_cfl_min_device(pyrohip_state *, const pyrohip_comp_params *, const double **);
+int comp_fill_frame_user(pyrohip_state *, const pyrohip_comp_params *, const StepScalars *, double *);
+int comp_fill_frame_user_parts(const pyrohip_state *);
+int comp_sponge_run(pyrohip_state *, const pyrohip_comp_params *, const StepScalars *, double *);
+int comp_sponge_run_parts(const pyrohip_state *);
 int comp_step_sph(pyrohip_state *, const pyrohip_comp_params *, double);
 int comp_step_wave_sph(pyrohip_state *, const pyrohip_comp_params *, double);
 int comp_step_wave_sph_ex(pyrohip_state *, const pyrohip_comp_params *, double, const StepScalars *,
@@ -54,6 +58,10 @@ int comp_step_fused_ex(pyrohip_state *, const pyrohip_comp_params *, double, con
 int comp_step_wave_ex(pyrohip_state *, const pyrohip_comp_params *, double, const StepScalars *,
                       const double **);
 int comp_cfl_min_device(pyrohip_state *, const pyrohip_comp_params *, const double **);
+int comp_fill_frame_user(pyrohip_state *, const pyrohip_comp_params *, const StepScalars *, double *);
+int comp_fill_frame_user_parts(const pyrohip_state *);
+int comp_sponge_run(pyrohip_state *, const pyrohip_comp_params *, const StepScalars *, double *);
+int comp_sponge_run_parts(const pyrohip_state *);
 int comp_step_sph(pyrohip_state *, const pyrohip_comp_params *, double);
 int comp_step_wave_sph(pyrohip_state *, const pyrohip_comp_params *, double);
 int comp_step_wave_sph_ex(pyrohip_state *, const pyrohip_comp_params *, double, const StepScalars *,
@@ -131,6 +139,22 @@ static bool comp_can_fuse_sph(const pyrohip_state *s, const pyrohip_comp_params 
     return same_index_map_kinds(s, false);
 }
 
+// Device-side stepping of a stratified state (hse / ambient y sides, the sponge):
+// can k_fill_frame2_user fill its ghost frame?  Index maps on the x sides of every variable; index
+// maps, hse or -- upper side -- ambient on the y sides; every image of a ghost cell an interior
+// cell (nx, ny >= ng) and the cells at jlo and jhi two different ones.
+static bool strat_fill_ok(const pyrohip_state *s)
+{
+    if (s->nvar != 4 || s->g.nx < s->g.ng || s->g.ny < s->g.ng || s->g.ny < 2) return false;
+    for (int n = 0; n < 4; n++) {
+        const int *b = &s->bc[n * 4];
+        if (!bc_is_index_map(b[0], true) || !bc_is_index_map(b[1], true)) return false;
+        if (!bc_is_index_map(b[2], true) && b[2] != PYROHIP_BC_HSE) return false;
+        if (!bc_is_index_map(b[3], true) && b[3] != PYROHIP_BC_HSE && b[3] != PYROHIP_BC_AMBIENT) return false;
+    }
+    return true;
+}
+
 static int check_comp(pyrohip_state *s, const pyrohip_comp_params *p)
 {
     PYRO_REQUIRE(s && p, "NULL argument");
@@ -160,11 +184,24 @@ int pyrohip_comp_evolve_p(pyrohip_state *s, const pyrohip_comp_params *p, double
     PYRO_REQUIRE(p->riemann >= 0 && p->riemann <= 2, "riemann must be 0 (HLLC), 1 (CGF) or 2 (HLLC_lm)");
     // (a SphericalPolar grid steps on the device where its step is one launch: comp_can_fuse_sph)
     const bool sphf = s->sph != nullptr && comp_can_fuse_sph(s, p);
-    PYRO_REQUIRE((!s->sph || sphf) && !s->user_bc && !s->ramp_bc && !p->do_sponge && !s->ext_old,
-                 "device-side stepping: standard boundaries, no sponge, no host-evaluated source; "
+    PYRO_REQUIRE((!s->sph || sphf) && !s->ramp_bc && !s->ext_old,
+                 "device-side stepping: no ramp boundary, no host-evaluated source; "
                  "a SphericalPolar grid needs CGF and outflow / reflect / periodic sides "
                  "(use pyrohip_comp_dt / pyrohip_comp_step)");
     pyrohip_ctx *c = s->ctx;
+    // a stratified run: hse / ambient y sides and / or the sponge -- its own fill
+    // (one launch, with the frame's CFL minimum) and the sponge behind every step
+    const bool strat = s->user_bc || p->do_sponge != 0;
+    if (strat) {
+        PYRO_REQUIRE(!s->sph && !s->nb_set && !c->global_cfl && !particles && strat_fill_ok(s),
+                     "device-side stepping: hse / ambient boundaries and the sponge step on the device on a "
+                     "single Cartesian domain, without tracer particles: outflow / reflect / periodic x sides, "
+                     "ambient on the upper y side only, at least ng cells each way "
+                     "(use pyrohip_comp_dt / pyrohip_comp_step)");
+        PYRO_REQUIRE(!s->user_bc || s->user_bc_set, "hse / ambient boundary: call pyrohip_state_set_user_bc first");
+        PYRO_REQUIRE(!p->do_sponge || p->sponge_rho_begin > p->sponge_rho_full,
+                     "sponge_rho_begin must exceed sponge_rho_full (simulation.py:172)");
+    }
     const bool wave = !sphf && takes_wave_kernel_ctu(s->g, p);
     // SphericalPolar grid on the row-marching kernel (comp_sph_wave.hip: reads a filled frame)
     const bool sphw = sphf && takes_wave_kernel(s->g, p);
@@ -175,10 +212,24 @@ int pyrohip_comp_evolve_p(pyrohip_state *s, const pyrohip_comp_params *p, double
     PYRO_TRY(evolve_bind_particles(r, s, particles, pparams, __func__));
     // (global_min: a decomposed run steps with the minimum over ALL slabs)
     PYRO_TRY(evolve_open(r, s, pol, cfl, 0, p->gamma, p->dx, p->dy, max_steps, true));
+    double *fpart = nullptr, *spart = nullptr;
+    int nfpart = 0, nspart = 0;
+    if (strat) {
+        // (a minimum a single step left is the interior's: the first step reduces the filled array)
+        r.min_cached = false;
+        r.own_frames = true;
+        PYRO_TRY(state_alt(s));
+        nfpart = p->fast_math ? fastm::comp_fill_frame_user_parts(s) : exact::comp_fill_frame_user_parts(s);
+        nspart = p->do_sponge ? (p->fast_math ? fastm::comp_sponge_run_parts(s) : exact::comp_sponge_run_parts(s)) : 0;
+        PYRO_TRY(c->strat.ensure((size_t)(nfpart + nspart) * sizeof(double)));
+        fpart = (double *)c->strat.p;
+        spart = fpart + nfpart;
+    }
     // steps after the first: the tile kernel applies the boundary rules itself where it can
     // (the first one needs filled ghost cells for the CFL minimum over the whole array)
     // (the spherical kernel reads every ghost cell through the boundary rules anyway)
-    const bool fuse = (sphf && !sphw) || comp_can_fuse_fill(s, p, wave);
+    // (a stratified run always fills: the sponge acts on the ghost cells in memory)
+    const bool fuse = !strat && ((sphf && !sphw) || comp_can_fuse_fill(s, p, wave));
     pyrohip_comp_params pf = *p;
     // step_launches 1: the row-marching kernel as the ONLY launch of a step (single domain;
     // outflow / reflect / periodic sides, the same kind for the four variables): it reads ghost
@@ -192,7 +243,7 @@ int pyrohip_comp_evolve_p(pyrohip_state *s, const pyrohip_comp_params *p, double
     // 16384^2): not the default.
     // (with a particle set bound the run keeps the three launches: the one-launch steps write no ghost
     // cell, and the tracers within half a cell of an upper border read the new buffer's frame)
-    bool one_launch = wave && p->step_launches == 1 && !s->nb_set && !c->global_cfl && !r.ps &&
+    bool one_launch = !strat && wave && p->step_launches == 1 && !s->nb_set && !c->global_cfl && !r.ps &&
                       comp_can_fuse_fill(s, p, false);
     for (int k = 0; k < 16 && one_launch; k++) one_launch = (s->bc[k] != PYROHIP_BC_HALO);
     pyro::StepPolicy *d_pol = nullptr;
@@ -229,7 +280,23 @@ int pyrohip_comp_evolve_p(pyrohip_state *s, const pyrohip_comp_params *p, double
         if (rc) break;
         pf.fuse_fill = (fuse && m > 0) ? 1 : 0;
         bool frame_done = false;
-        if (m == 0) {   // CFL minimum of the state as handed over (full array, ghost cells filled)
+        if (strat) {
+            // one launch: the frames of both buffers by the hse / ambient rules and the CFL partials
+            // of the cells written; nothing on an iteration that will not advance
+            rc = p->fast_math ? fastm::comp_fill_frame_user(s, p, r.d_scal, fpart)
+                              : exact::comp_fill_frame_user(s, p, r.d_scal, fpart);
+            if (rc) break;
+            frame_done = true;
+            if (m == 0) {   // CFL minimum of the state as handed over: the full reduction
+                rc = p->fast_math ? fastm::comp_cfl_min_device(s, p, &r.dmin)
+                                  : exact::comp_cfl_min_device(s, p, &r.dmin);
+                if (rc) break;
+            } else {        // min(interior: the last step's or the sponge's partials, frame: the fill's)
+                r.fpart = fpart;
+                r.nfpart = nfpart;
+            }
+            rc = evolve_policy(r, m);
+        } else if (m == 0) {   // CFL minimum of the state as handed over (full array, ghost cells filled)
             rc = evolve_fill(r, framed, &frame_done);
             if (rc) break;
             if (r.min_cached)
@@ -273,6 +340,14 @@ int pyrohip_comp_evolve_p(pyrohip_state *s, const pyrohip_comp_params *p, double
             rc = p->fast_math ? fastm::comp_step_fused_ex(s, &pf, 0.0, r.d_scal, &r.dmin)
                               : exact::comp_step_fused_ex(s, &pf, 0.0, r.d_scal, &r.dmin);
         r.take_pending();       // (the minimum of a tile-kernel launch is taken by the next policy call)
+        if (rc == 0 && p->do_sponge) {
+            // the sponge on the new buffer, ghost frame included; the next policy call takes the
+            // partials of the interior behind it, not the step's
+            rc = p->fast_math ? fastm::comp_sponge_run(s, p, r.d_scal, spart)
+                              : exact::comp_sponge_run(s, p, r.d_scal, spart);
+            r.pend = spart;
+            r.npend = nspart;
+        }
         if (rc == 0) rc = evolve_particles(r);
     }
     s->frame_prefilled = false;      // (an iteration that stopped between the fill and its step)
@@ -286,7 +361,7 @@ int pyrohip_comp_evolve_p(pyrohip_state *s, const pyrohip_comp_params *p, double
         r.npend = pyro::kPolSetWords;
         r.dmin = (const double *)(s->d_polmem + 3 * (size_t)pyro::kPolSetWords);
     }
-    rc = evolve_close(r, pol, steps_done, dts_out, framed, one_launch);
+    rc = evolve_close(r, pol, steps_done, dts_out, framed && !strat, one_launch);
     if (s->next_cfl_min <= 0.0) s->cfl_is_global = false;
     return rc;
 }

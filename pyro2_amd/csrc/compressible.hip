@@ -444,6 +444,187 @@ int comp_sponge(pyrohip_state *s, const pyrohip_comp_params *p, double dt)
     return 0;
 }
 
+// ... inside a device-side run (pyrohip_comp_evolve with the sponge): dt from the
+// step scalars, nothing on an iteration that does not advance (past tmax, after an invalid state:
+// the step before it stored nothing either), and the CFL partials of the interior AFTER the
+// sponge, one per workgroup -- the step kernel's describe the state before it.  sponge_cell is
+// the bit-faithful build's in both builds; the CFL quantity is this build's (k_cfl)
+__global__ __launch_bounds__(256) void k_sponge_run(double *__restrict__ U, Geom g,
+                                                    const StepScalars *__restrict__ S,
+                                                    const int *__restrict__ flag, double rho_begin,
+                                                    double rho_full, double tau, double gamma, double dx,
+                                                    double dy, double *__restrict__ partial)
+{
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    const int i = blockIdx.y;
+    double m = INFINITY;
+    if (S->active && !(*flag & 1) && j < g.qy) {
+        const size_t k = (size_t)i * g.pitch + j;
+        Cons Uc = load_cons(U, g.plane, k);
+        sponge_cell(Uc, S->dt, rho_begin, rho_full, tau);
+        store_cons(U, g.plane, k, Uc);
+        if (i >= g.ilo && i <= g.ihi && j >= g.jlo && j <= g.jhi) m = cfl_cell(Uc, gamma, dx, dy);
+    }
+    m = block_reduce_min(m);
+    if (threadIdx.x == 0) partial[blockIdx.y * gridDim.x + blockIdx.x] = m;
+}
+
+int comp_sponge_run_parts(const pyrohip_state *s) { return ((s->g.qy + 255) / 256) * s->g.qx; }
+
+int comp_sponge_run(pyrohip_state *s, const pyrohip_comp_params *p, const StepScalars *S, double *partial)
+{
+    const Geom &g = s->g;
+    PYRO_LAUNCH(s->ctx, "k_sponge_run", k_sponge_run, dim3((g.qy + 255) / 256, g.qx), dim3(256), 0, s->d, g, S,
+                (const int *)s->d_flag, p->sponge_rho_begin, p->sponge_rho_full, p->sponge_timescale, p->gamma,
+                p->dx, p->dy, partial);
+    PYRO_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---- the ghost frame of a stratified state in ONE launch ----
+// Boundary fill of all four variables under hse / ambient y sides -- pyrohip_fill_bc's up to nine
+// launches (k_fill_x + k_fill_y for density and energy, the same for the momenta, k_fill_y_user per
+// variable) -- into the state's buffer AND the other buffer's frame (as k_fill_frame2, evolve.hip,
+// does for index maps: the step is spared its frame copy), with the minimum of the CFL quantity
+// over the cells written, one partial per workgroup: the whole-array minimum of the reference is
+// min(interior: the step's partials, frame: these).  It lives here, not beside k_fill_frame2,
+// because that quantity is the arithmetic build's own (cfl_cell as k_cfl evaluates it).
+//   x sides: index maps (outflow / reflect / periodic), per variable; y sides: index maps, with hse
+//   and ambient counting as outflow first (k_fill_y); then the hse energy, integrated away from
+//   row jlo / jhi (hse_start / hse_next), and the ambient constants on the upper side.
+// The order of fill_BC_all, variable by variable, shows in the corners (ctx.hip: pyrohip_fill_bc):
+// the hse energy of an x-ghost row takes density and energy from the x-ghost values of THIS fill
+// (here: through the x map, from the interior) and the momenta from those of the PREVIOUS fill,
+// which are in memory until this launch overwrites them.  So ONE thread owns everything that
+// depends on a cell (i, jlo) or (i, jhi) of a ghost row: it reads the old momenta there, then
+// writes that cell and the ng ghost cells beyond it, all four variables.  Nothing else the launch
+// reads is written by it (every other source cell is interior: nx, ny >= ng).
+//   workgroups [0, nrow_blocks): one thread per (y side, row i of the array) -- the ng ghost cells
+//     of that row beyond jlo / jhi, and in a ghost row the cell at jlo / jhi itself;
+//   then 2 ng ghost rows x nxb pieces of 256 columns: the cells of the ghost rows strictly
+//     between jlo and jhi.
+// Nothing is written on an iteration whose step will not run (dt_policy_goes_on: past tmax, after
+// an invalid state): the frames of both buffers stay what the last step that advanced left.
+struct FrameUser {
+    BcMap mx[4], my[4];        // per variable; hse / ambient sides as outflow
+    int hse_lo, hse_hi;        // the energy is integrated on the lower / upper y side
+    int amb_hi[4];             // variable n is constant beyond the upper y side
+    double amb[4];
+    double hgamma, hgrav, hdy; // pyrohip_state_set_user_bc
+    double gamma, dx, dy;      // of the CFL quantity
+    int nrow_blocks, nxb;
+};
+__device__ __forceinline__ double frame_image(const double *U, const Geom &g, const FrameUser &F, int n, int i,
+                                              int j)
+{
+    const BcMap &mx = F.mx[n], &my = F.my[n];
+    const int si = bc_src(mx, i, g.ilo, g.ihi), sj = bc_src(my, j, g.jlo, g.jhi);
+    const bool neg = ((i < g.ilo && mx.odd_lo) || (i > g.ihi && mx.odd_hi)) !=
+                     ((j < g.jlo && my.odd_lo) || (j > g.jhi && my.odd_hi));
+    const double v = U[(size_t)n * g.plane + (size_t)si * g.pitch + sj];
+    return neg ? -v : v;
+}
+__device__ __forceinline__ double frame_put(double *cur, double *alt, const Geom &g, size_t k, const Cons &V,
+                                            const FrameUser &F)
+{
+    store_cons(cur, g.plane, k, V);
+    store_cons(alt, g.plane, k, V);
+    return cfl_cell(V, F.gamma, F.dx, F.dy);
+}
+__global__ __launch_bounds__(256) void k_fill_frame2_user(double *cur, double *alt, Geom g, FrameUser F,
+                                                          const StepScalars *__restrict__ S,
+                                                          const int *__restrict__ flag,
+                                                          double *__restrict__ partial)
+{
+    const int b = (int)blockIdx.x, t = (int)threadIdx.x;
+    double m = INFINITY;
+    const bool go = dt_policy_goes_on(S, (*flag & 1) != 0);
+    if (go && b < F.nrow_blocks) {
+        const int u = b * 256 + t;
+        if (u < 2 * g.qx) {
+            const int side = u / g.qx, i = u - side * g.qx;
+            const int jb = side ? g.jhi : g.jlo;
+            const size_t row = (size_t)i * g.pitch;
+            // (a ghost row: the momenta of the previous fill, before this thread overwrites them)
+            const double xm_mem = cur[2 * g.plane + row + jb], ym_mem = cur[3 * g.plane + row + jb];
+            Cons B;
+            B.d = frame_image(cur, g, F, 0, i, jb);
+            B.E = frame_image(cur, g, F, 1, i, jb);
+            B.mx = frame_image(cur, g, F, 2, i, jb);
+            B.my = frame_image(cur, g, F, 3, i, jb);
+            if (i < g.ilo || i > g.ihi) m = fmin(m, frame_put(cur, alt, g, row + jb, B, F));
+            const bool hse = side ? F.hse_hi != 0 : F.hse_lo != 0;
+            HseMarch h{0.0, 0.0, 0.0};
+            if (hse) h = hse_start(B.d, B.E, xm_mem, ym_mem, F.hgamma);
+            for (int k = 1; k <= g.ng; k++) {
+                const int j = side ? g.jhi + k : g.jlo - k;
+                Cons V;
+                V.d = (side && F.amb_hi[0]) ? F.amb[0] : frame_image(cur, g, F, 0, i, j);
+                V.mx = (side && F.amb_hi[2]) ? F.amb[2] : frame_image(cur, g, F, 2, i, j);
+                V.my = (side && F.amb_hi[3]) ? F.amb[3] : frame_image(cur, g, F, 3, i, j);
+                V.E = (side && F.amb_hi[1]) ? F.amb[1]
+                      : hse ? hse_next(h, side != 0, F.hgamma, F.hgrav, F.hdy)
+                            : frame_image(cur, g, F, 1, i, j);
+                m = fmin(m, frame_put(cur, alt, g, row + j, V, F));
+            }
+        }
+    } else if (go) {
+        const int bb = b - F.nrow_blocks, rr = bb / F.nxb;
+        const int i = (rr < g.ng) ? rr : g.ihi + 1 + (rr - g.ng);
+        const int j = g.jlo + 1 + (bb - rr * F.nxb) * 256 + t;
+        if (j < g.jhi) {
+            Cons V;
+            V.d = frame_image(cur, g, F, 0, i, j);
+            V.E = frame_image(cur, g, F, 1, i, j);
+            V.mx = frame_image(cur, g, F, 2, i, j);
+            V.my = frame_image(cur, g, F, 3, i, j);
+            m = frame_put(cur, alt, g, (size_t)i * g.pitch + j, V, F);
+        }
+    }
+    m = block_reduce_min(m);
+    if (t == 0) partial[b] = m;
+}
+
+static int frame_user_setup(const pyrohip_state *s, const pyrohip_comp_params *p, FrameUser &F)
+{
+    const Geom &g = s->g;
+    const auto plain = [](int b) { return (b == PYROHIP_BC_HSE || b == PYROHIP_BC_AMBIENT) ? (int)PYROHIP_BC_OUTFLOW : b; };
+    for (int n = 0; n < 4; n++) {
+        F.mx[n] = bc_map(g.ilo, g.ihi, g.ng, s->bc[n * 4 + 0], s->bc[n * 4 + 1], true);
+        F.my[n] = bc_map(g.jlo, g.jhi, g.ng, plain(s->bc[n * 4 + 2]), plain(s->bc[n * 4 + 3]), true);
+        F.amb_hi[n] = (s->bc[n * 4 + 3] == PYROHIP_BC_AMBIENT) ? 1 : 0;
+    }
+    F.hse_lo = (s->bc[1 * 4 + 2] == PYROHIP_BC_HSE) ? 1 : 0;
+    F.hse_hi = (s->bc[1 * 4 + 3] == PYROHIP_BC_HSE) ? 1 : 0;
+    user_bc_ambient(s, F.amb);
+    F.hgamma = s->ubc_gamma; F.hgrav = s->ubc_grav; F.hdy = s->ubc_dy;
+    F.gamma = p->gamma; F.dx = p->dx; F.dy = p->dy;
+    F.nrow_blocks = (2 * g.qx + 255) / 256;
+    F.nxb = g.ny > 2 ? (g.ny - 2 + 255) / 256 : 0;
+    return F.nrow_blocks + 2 * g.ng * F.nxb;
+}
+
+// workgroups of the launch = CFL partials it leaves
+int comp_fill_frame_user_parts(const pyrohip_state *s)
+{
+    FrameUser F;
+    pyrohip_comp_params p;
+    memset(&p, 0, sizeof(p));
+    return frame_user_setup(s, &p, F);
+}
+
+// the caller (pyrohip_comp_evolve) checked: index maps on the x sides, index maps / hse / ambient
+// (upper) on the y sides, nx, ny >= ng, a second buffer
+int comp_fill_frame_user(pyrohip_state *s, const pyrohip_comp_params *p, const StepScalars *S, double *partial)
+{
+    FrameUser F;
+    const int nwg = frame_user_setup(s, p, F);
+    PYRO_LAUNCH(s->ctx, "k_fill_frame2_user", k_fill_frame2_user, dim3(nwg), dim3(256), 0, s->d,
+                s->alt_base + geom_lead(s->g), s->g, F, S, (const int *)s->d_flag, partial);
+    PYRO_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
 // ---- CFL over the whole array (ghost cells included), derives.py ---------
 __global__ __launch_bounds__(256) void k_cfl(const double *__restrict__ U, Geom g, double gamma,
                                              double dx, double dy, double *__restrict__ partial)

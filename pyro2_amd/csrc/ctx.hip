@@ -4,6 +4,7 @@
 // (pyro/mesh/array_indexer.py:150-274).
 #include "common.h"
 #include "reduce.h"
+#include "stencil.h"
 
 namespace pyro {
 
@@ -157,16 +158,11 @@ __global__ void k_fill_y_user(double *__restrict__ d, Geom g, const int *__restr
     const double dens_base = d[row + jb];
     const double ener = d[(size_t)g.plane + row + jb];
     const double xm = d[2 * (size_t)g.plane + row + jb], ym = d[3 * (size_t)g.plane + row + jb];
-    const double ke_base = 0.5 * (xm * xm + ym * ym) / dens_base;
-    const double eint_base = (ener - ke_base) / dens_base;
-    double pres_base = dens_base * eint_base * (ub.gamma - 1.0);   // eos.pres
+    HseMarch h = hse_start(dens_base, ener, xm, ym, ub.gamma);     // (stencil.h)
     double *e = d + (size_t)g.plane + row;
     for (int k = 1; k <= g.ng; k++) {
         const int j = side ? g.jhi + k : g.jlo - k;
-        const double pres_next = side ? pres_base + ub.grav * dens_base * ub.dy
-                                      : pres_base - ub.grav * dens_base * ub.dy;
-        e[j] = pres_next / (ub.gamma - 1.0) + ke_base;             // eos.rhoe
-        pres_base = pres_next;
+        e[j] = hse_next(h, side != 0, ub.gamma, ub.grav, ub.dy);
     }
 }
 
@@ -406,6 +402,18 @@ int particles_release(pyrohip_particles *p)
     return 0;
 }
 
+// the constant rows of the ambient boundary (BC.py:162-176), by variable: density, energy,
+// x-momentum, y-momentum
+void user_bc_ambient(const pyrohip_state *s, double out[4])
+{
+    const double *A = s->ubc_amb;   // rho, u, v, p
+    const double ke = 0.5 * A[0] * (A[1] * A[1] + A[2] * A[2]);
+    out[0] = A[0];
+    out[1] = A[3] / (s->ubc_gamma - 1.0) + ke;
+    out[2] = A[0] * A[1];
+    out[3] = A[0] * A[2];
+}
+
 }  // namespace pyro
 
 using namespace pyro;
@@ -460,6 +468,7 @@ int pyrohip_shutdown(pyrohip_ctx *c)
     c->staging.release();
     c->reduce.release();
     c->prio_board.release();
+    c->strat.release();
     c->mg_trace.release();
     if (c->reduce_host) (void)hipHostFree(c->reduce_host);
     (void)hipEventDestroy(c->ev0);
@@ -825,16 +834,9 @@ static int fill_bc_range(pyrohip_state *s, int n0, int cnt)
             const bool hse = (n == 1) && (yl == PYROHIP_BC_HSE || yr == PYROHIP_BC_HSE);
             const bool amb = (yr == PYROHIP_BC_AMBIENT);
             if (!hse && !amb) continue;
-            const double *A = s->ubc_amb;   // rho, u, v, p
-            UserBc ub{s->ubc_gamma, s->ubc_grav, s->ubc_dy, 0.0};
-            // BC.py:162-176; n: density, energy, x-momentum, y-momentum
-            if (n == 0) ub.amb_val = A[0];
-            else if (n == 2) ub.amb_val = A[0] * A[1];
-            else if (n == 3) ub.amb_val = A[0] * A[2];
-            else {
-                const double ke = 0.5 * A[0] * (A[1] * A[1] + A[2] * A[2]);
-                ub.amb_val = A[3] / (s->ubc_gamma - 1.0) + ke;
-            }
+            double rows[4];
+            user_bc_ambient(s, rows);
+            const UserBc ub{s->ubc_gamma, s->ubc_grav, s->ubc_dy, rows[n]};
             hipLaunchKernelGGL(k_fill_y_user, dim3((g.qx + 63) / 64, 2), dim3(64), 0, c->stream,
                                s->d, g, (const int *)s->d_bc, n, ub);
         }

@@ -71,15 +71,18 @@ constexpr int kPolicyThreads = 1024;
 __device__ __forceinline__ void dt_policy_block(StepScalars *S, const double *cflmin,
                                                 const int *flag, double *dts, int slot,
                                                 int final_call, const double *part, int nparts,
-                                                double *minout, int flag_mask)
+                                                double *minout, int flag_mask, const double *fpart,
+                                                int nfpart)
 {
     // the CFL minimum of the previous step: already reduced (cflmin), or still the
     // per-workgroup partials of the tile kernel (part: reduced here, kept in minout)
+    // (fpart: a stratified run -- the partials of the frame cells the fill in front of this call
+    // wrote; the minimum of both is the reference's, over the whole array with ghost cells filled)
     // (1024 threads, four loads in flight each: 40 000 partials at 16384^2 -- with 256 threads
     // and one dependent load after the other this took 36 us at 8192^2, 1.4 % of the step)
     __shared__ double red[kPolicyThreads];
     __shared__ double cmin_s;
-    if (part != nullptr) {
+    if (part != nullptr || fpart != nullptr) {
         double m0 = INFINITY, m1 = INFINITY, m2 = INFINITY, m3 = INFINITY;
         const int nt = blockDim.x;
         int i = threadIdx.x;
@@ -88,6 +91,8 @@ __device__ __forceinline__ void dt_policy_block(StepScalars *S, const double *cf
             m0 = fmin(m0, a); m1 = fmin(m1, b); m2 = fmin(m2, c2); m3 = fmin(m3, d);
         }
         for (; i < nparts; i += nt) m0 = fmin(m0, part[i]);
+        for (i = threadIdx.x; i < nfpart; i += nt) m1 = fmin(m1, fpart[i]);
+        if (part == nullptr && threadIdx.x == 0) m2 = fmin(m2, *cflmin);
         const double m = fmin(fmin(m0, m1), fmin(m2, m3));
         red[threadIdx.x] = m;
         __syncthreads();
@@ -107,9 +112,10 @@ __device__ __forceinline__ void dt_policy_block(StepScalars *S, const double *cf
 __global__ __launch_bounds__(kPolicyThreads) void k_dt_policy(StepScalars *S, const double *cflmin,
                                                    const int *flag, double *dts, int slot,
                                                    int final_call, const double *part, int nparts,
-                                                   double *minout, int flag_mask)
+                                                   double *minout, int flag_mask, const double *fpart,
+                                                   int nfpart)
 {
-    dt_policy_block(S, cflmin, flag, dts, slot, final_call, part, nparts, minout, flag_mask);
+    dt_policy_block(S, cflmin, flag, dts, slot, final_call, part, nparts, minout, flag_mask, fpart, nfpart);
 }
 // The two small launches between two steps of a device-side run in ONE (round 6): the ghost
 // frames of both buffers (k_fill_frame2: reads the state the last step left) and the driver's dt
@@ -123,7 +129,7 @@ __global__ __launch_bounds__(kPolicyThreads) void k_fill_frame2_policy(
     int nparts, double *minout)
 {
     if (blockIdx.x + 1 == gridDim.x) {
-        dt_policy_block(S, cflmin, flag, dts, slot, 0, part, nparts, minout, 1);
+        dt_policy_block(S, cflmin, flag, dts, slot, 0, part, nparts, minout, 1, nullptr, 0);
         return;
     }
     const int piece = (int)blockIdx.x * 4 + (int)threadIdx.x / 256;
@@ -163,10 +169,11 @@ static int launch_policy(EvolveRun &r, int slot, int final_call, int flag_mask)
 {
     pyrohip_state *s = r.s;
     PYRO_LAUNCH(s->ctx, "k_dt_policy", k_dt_policy, dim3(1), dim3(kPolicyThreads), 0, r.d_scal, r.dmin,
-                (const int *)s->d_flag, s->d_dts, slot, final_call, r.pend, r.npend, const_cast<double *>(r.dmin),
-                flag_mask);
+                (const int *)s->d_flag, s->d_dts, slot, final_call, r.pend, r.pend ? r.npend : 0,
+                const_cast<double *>(r.dmin), flag_mask, r.fpart, r.fpart ? r.nfpart : 0);
     PYRO_CHECK_HIP(hipGetLastError());
     r.pend = nullptr;
+    r.fpart = nullptr;
     return 0;
 }
 
@@ -316,15 +323,19 @@ int evolve_close(EvolveRun &r, pyrohip_dt_policy *pol, int *steps_done, double *
         // (its steps wrote no ghost cell; after an invalid step the other buffer is that step's
         // debris: the state's own images)
         if (H.steps >= 1) PYRO_TRY(launch_frame(s, invalid ? s->d : s->alt_base + geom_lead(g), nullptr));
-    } else if (framed && !invalid) {
+    } else if (framed && !invalid && !r.own_frames) {
         PYRO_TRY(restore_frame_after_inactive(s, H.steps, max_steps, r.halo_ok, r.sph_ok));
     }
     // after an invalid step: the reference's assert fires right behind fill_BC_all (pyro_sim.py:250-256), so the
     // state left behind carries its own filled ghost cells -- whatever the step's launch and the inactive
     // iterations behind it did to the frames of the two buffers
-    if (invalid && !s->nb_set) PYRO_TRY(pyrohip_fill_bc(s, -1));
+    // (a stratified run: the fill in front of the step that met it is the last that wrote -- its fills keep
+    // still on inactive iterations -- and that frame is the single steps'; another fill here would take the
+    // hse corners from the momenta of THIS fill)
+    if (invalid && !s->nb_set && !r.own_frames) PYRO_TRY(pyrohip_fill_bc(s, -1));
     // the minimum of the last launch belongs to the state only if that launch advanced it
-    s->next_cfl_min = (H.steps == max_steps && !invalid) ? lastmin : -1.0;
+    // (a stratified run ends with the interior's minimum alone: not kept, as after single steps)
+    s->next_cfl_min = (H.steps == max_steps && !invalid && !r.own_frames) ? lastmin : -1.0;
     s->cfl_kind = r.cfl_kind;
     memcpy(s->cfl_par, r.cfl_par, sizeof(r.cfl_par));
     s->ghost_by_rules = false;      // a new time level: its ghost cells are stale until the next fill

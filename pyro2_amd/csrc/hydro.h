@@ -1033,6 +1033,9 @@ __device__ __forceinline__ ConsN riemann_face(const ConsN &Ul, const ConsN &Ur, 
 
 // Sponge, compressible/simulation.py:164-184 and :427-441 (acts on every
 // cell of the array, ghost cells included)
+// (both arithmetic builds run the sponge of the bit-faithful one, pyrohip_comp_step: never
+// contracted, also where the contracted build compiles it -- k_sponge_run, compressible.hip;
+// fp_keep, stencil.h: the products stay products)
 __device__ __forceinline__ void sponge_cell(Cons &U, double dt, double rho_begin, double rho_full,
                                             double tau)
 {
@@ -1044,9 +1047,11 @@ __device__ __forceinline__ void sponge_cell(Cons &U, double dt, double rho_begin
     else f = 0.5 * (1.0 - cos(PI * (rho - rho_begin) / (rho_full - rho_begin)));
     const double kappa = f / tau;
     const double xo = U.mx, yo = U.my;
-    U.mx = xo / (1.0 + dt * kappa);
-    U.my = yo / (1.0 + dt * kappa);
-    const double dke = 0.5 * ((U.mx * U.mx + U.my * U.my) - (xo * xo + yo * yo)) / U.d;
+    const double damp = 1.0 + fp_keep(dt * kappa);
+    U.mx = xo / damp;
+    U.my = yo / damp;
+    const double dke = 0.5 * ((fp_keep(U.mx * U.mx) + fp_keep(U.my * U.my)) -
+                              (fp_keep(xo * xo) + fp_keep(yo * yo))) / U.d;
     U.E += dke;
 }
 

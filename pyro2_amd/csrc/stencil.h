@@ -137,6 +137,39 @@ __device__ __forceinline__ int bc_src(const BcMap &m, int i, int lo, int hi)
     return i < lo ? m.alo * i + m.blo : (i > hi ? m.ahi * i + m.bhi : i);
 }
 
+// hse boundary of the compressible solver, energy (compressible/BC.py:64-84 lower y side, :95-115
+// upper): the pressure of the last interior cell integrated outwards at constant density
+// (dp = rho g dy), its kinetic energy kept.  hse_start: that cell; hse_next: the energy of the next
+// ghost cell away from it.  IEEE operations in the reference's order, never contracted (fp_keep):
+// the variable-by-variable fill (k_fill_y_user, ctx.hip) and the one-launch frame fill of a
+// device-side run (k_fill_frame2_user, compressible.hip, both arithmetic builds) give the same bits.
+// fp_keep: a product that must stay a product.  A unit compiled with -ffp-contract=fast fuses it
+// into the sum it feeds whatever pragma surrounds it; the value passes through an empty asm
+// statement, which the instruction selector does not look through.
+__device__ __forceinline__ double fp_keep(double x)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(x));
+#endif
+    return x;
+}
+struct HseMarch { double pres, dens, ke; };
+__device__ __forceinline__ HseMarch hse_start(double dens, double ener, double xm, double ym, double gamma)
+{
+    HseMarch h;
+    h.dens = dens;
+    h.ke = 0.5 * (fp_keep(xm * xm) + fp_keep(ym * ym)) / dens;
+    const double eint = (ener - h.ke) / dens;
+    h.pres = dens * eint * (gamma - 1.0);                          // eos.pres
+    return h;
+}
+__device__ __forceinline__ double hse_next(HseMarch &h, bool upper, double gamma, double grav, double dy)
+{
+    const double dp = fp_keep(grav * h.dens * dy);
+    h.pres = upper ? h.pres + dp : h.pres - dp;
+    return h.pres / (gamma - 1.0) + h.ke;                          // eos.rhoe
+}
+
 // Tile kernels that load THROUGH the ghost fill (advection_nonuniform.hip, advection_rk.hip):
 // array cell (i, j) of a variable with the row / column maps mr / mc -> the offset of its interior
 // source cell in the plane.  Cells beyond the array feed discarded faces only: any address inside.
