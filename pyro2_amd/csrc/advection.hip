@@ -37,6 +37,7 @@
 // expressions fuse); pyrohip_adv_params.fast_math selects.
 #include "common.h"
 #include "stencil.h"
+#include "wave_march.h"
 #include <type_traits>
 
 #ifndef PYRO_FAST
@@ -122,28 +123,13 @@ struct AdvParams {
     int bxl, bxr, byl, byr; // boundary types of the variable (fill)
 };
 
-// lane l-1 / l+1 (rotation: the end lanes are apron, see comp_wave.hip)
-#if !defined(PYRO_EMU)
-template <int CTRL> __device__ __forceinline__ double adv_dpp(double v)
-{
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xf, 0xf, true);
-    hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double adv_m1(double v) { return adv_dpp<0x13C>(v); }   // wave_ror:1
-__device__ __forceinline__ double adv_p1(double v) { return adv_dpp<0x134>(v); }   // wave_rol:1
-#else
-__device__ __forceinline__ double adv_m1(double v) { return __shfl_up(v, 1, 64); }
-__device__ __forceinline__ double adv_p1(double v) { return __shfl_down(v, 1, 64); }
-#endif
-
 // the lane's two cells of a row: a at column j0 = 2 l (+ strip offset), b at j0 + 1
 struct D2 { double a, b; };
 // the same quantity one column to the left / right of each of the two cells: one DPP
-// double move each, the other neighbour is the lane's own second cell
-__device__ __forceinline__ D2 adv_left(const D2 &q) { return D2{adv_m1(q.b), q.a}; }
-__device__ __forceinline__ D2 adv_right(const D2 &q) { return D2{q.b, adv_p1(q.a)}; }
+// double move each (wave_march.h: a rotation, the end lanes are apron), the other neighbour is the
+// lane's own second cell
+__device__ __forceinline__ D2 adv_left(const D2 &q) { return D2{lane_from_lower(q.b), q.a}; }
+__device__ __forceinline__ D2 adv_right(const D2 &q) { return D2{q.b, lane_from_upper(q.a)}; }
 
 // limited slope from shared limit2 values (reconstruction.py:9-120)
 // (measured, contracted build: HALF slopes in signed min / max form, as in the compressible and

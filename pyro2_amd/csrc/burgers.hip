@@ -263,10 +263,7 @@ static int bg_step_tile(pyrohip_state *s, int iu, int iv, double dx, double dy, 
     PYRO_LAUNCH(c, "k_bg_tile", kernels[limiter], grid, block, 0, in + (size_t)iu * g.plane,
                 in + (size_t)iv * g.plane, out + (size_t)iu * g.plane, out + (size_t)iv * g.plane, g, P, S, part);
     PYRO_CHECK_HIP(hipGetLastError());
-    double *old_base = s->base;       // the buffers change places
-    s->base = s->alt_base;
-    s->alt_base = old_base;
-    s->d = s->base + geom_lead(g);
+    state_swap_alt(s);
     s->next_cfl_min = -1.0;
     s->ghost_by_rules = false;
     return 0;

@@ -378,7 +378,7 @@ struct pyrohip_state {
 };
 
 // the rows-left board of the SIMD pairs for a row-marching launch whose wavefronts all sit on the chip at once or in
-// two rounds (comp_wave.hip: the one with more rows left takes the priority): 2^16 SIMD numbers (XCC, SE, SH, CU,
+// two rounds (wave_march.h: the one with more rows left takes the priority): 2^16 SIMD numbers (XCC, SE, SH, CU,
 // SIMD fields of the hardware id) x 2 slots, zeroed once, tagged per launch (1 .. 32767: never the zeroed board's 0)
 inline int prio_board_acquire(pyrohip_ctx *c, int **board, int *tag)
 {
@@ -391,15 +391,6 @@ inline int prio_board_acquire(pyrohip_ctx *c, int **board, int *tag)
     *board = (int *)c->prio_board.p;
     *tag = (int)c->launch_seq;
     return 0;
-}
-// one-round launches: as many strips as wavefront slots -- the first n_extra of the ncb column strips are cut into
-// nsb + 1 row strips of equal length instead of nsb (a SIMD left with ONE wavefront gets little out of it and
-// the launch lasts as long as its last wavefront: tools/wave_timeline.py)
-inline int wave_fill_extra(int ncb, int nsb, int nx, int slots)
-{
-    const int nreg = ncb * nsb;
-    if (nsb < 2 || nreg >= slots || nx / (nsb + 1) < 8) return 0;
-    return slots - nreg < ncb ? slots - nreg : ncb;
 }
 // the CFL minimum the last step of a device-side run left still describes the state: same kind of
 // quantity, same (gamma | g, dx, dy), nothing has written the state since (every writer resets it)
@@ -426,6 +417,9 @@ inline bool state_work_is(const pyrohip_state *s, int owner, size_t planes)
 int state_take_work(pyrohip_state *s, int n);
 // the second buffer (nvar planes, zeroed once)
 int state_alt(pyrohip_state *s);
+// the state's buffer and the second one change places (the pointers only: what else a new time level
+// resets -- next_cfl_min, ghost_by_rules, stages_valid -- is the caller's)
+void state_swap_alt(pyrohip_state *s);
 // set-up of a run that advances on the device: the step scalars and the dt sequence (max_steps + 1
 // slots) in device memory, *H zeroed and filled from the policy.  The caller sets min0 / keep0 and
 // uploads H.
@@ -441,6 +435,8 @@ inline int frame_pieces(const Geom &g)
     const int rows_per_piece = 256 / (2 * g.ng);
     return 2 * g.ng * ((g.qy + 255) / 256) + (g.nx + rows_per_piece - 1) / rows_per_piece;
 }
+// the ghost frame of a four-variable state carried over to its second buffer (k_copy_frame4)
+void state_copy_frame4(pyrohip_state *s);
 // can k_fill_frame2 fill the state's ghost cells (four variables or two, index maps on every side of
 // each, a second buffer)?  halo_ok: x sides that are cuts of a slab pass; sph_ok: a SphericalPolar grid passes
 bool frame_fill_ok(const pyrohip_state *s, bool halo_ok = false, bool sph_ok = false);

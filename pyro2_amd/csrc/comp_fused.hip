@@ -700,38 +700,6 @@ __global__ __launch_bounds__(FNT, FUSED_MINW) void k_ctu_fused_sph(const double 
     if (t == 0) partial[tile] = cfl;
 }
 
-// ghost frame of all 4 planes old -> new (the reference updates in place, so
-// ghost cells keep their pre-step values)
-// O(perimeter): blockIdx.y enumerates the 2*ng ghost rows (all j) followed by
-// the nx interior rows (only their 2*ng ghost columns)
-__global__ void k_copy_frame4(const double *__restrict__ src, double *__restrict__ dst, Geom g)
-{
-    // 1-d grid: the 2 ng full ghost rows in pieces of 256 columns, then the ghost columns of
-    // the interior rows (a 2-d grid whose column part ran in block column 0 only launched
-    // 33 thousand workgroups at 16384^2 for 1024 that had work)
-    const int ng = g.ng;
-    const int nxb = (g.qy + 255) / 256, nrowblk = 2 * ng * nxb;
-    const int b = blockIdx.x;
-    int i, j;
-    if (b < nrowblk) {                              // a piece of a full ghost row
-        const int rr = b / nxb;
-        i = (rr < ng) ? rr : g.ihi + 1 + (rr - ng);
-        j = (b - rr * nxb) * 256 + (int)threadIdx.x;
-        if (j >= g.qy) return;
-    } else {                                        // ghost columns of interior rows
-        const int t = threadIdx.x;                  // 256 threads: 2*ng columns x rows
-        const int rows_per_block = 256 / (2 * ng);
-        const int r = (b - nrowblk) * rows_per_block + t / (2 * ng);
-        const int kx = t % (2 * ng);
-        if (r >= g.nx || t >= rows_per_block * 2 * ng) return;
-        i = g.ilo + r;
-        j = (kx < ng) ? kx : g.jhi + 1 + (kx - ng);
-    }
-    const size_t k = (size_t)i * g.pitch + j;
-#pragma unroll
-    for (int n = 0; n < 4; n++) dst[n * g.plane + k] = src[n * g.plane + k];
-}
-
 // second state buffer + the kernel parameters both single-launch kernels share
 int fused_prepare(pyrohip_state *s, const pyrohip_comp_params *p, double dt, FP &P, double *&Uin,
                   double *&Uout, bool reset_flag, bool second_buffer)
@@ -777,19 +745,11 @@ int fused_prepare(pyrohip_state *s, const pyrohip_comp_params *p, double dt, FP 
 // after the step kernel: ghost frame old -> new, minimum of the per-workgroup
 // CFL partials (all-reduced over the slabs when decomposed), positivity flag,
 // swap of the two state buffers
-void fused_copy_frame(pyrohip_state *s)
-{
-    pyrohip_ctx *c = s->ctx;
-    const Geom &g = s->g;
-    hipLaunchKernelGGL(k_copy_frame4, dim3(frame_pieces(g)), dim3(256), 0, c->stream,
-                       (const double *)s->d, s->alt_base + geom_lead(g), g);
-}
-
 int fused_tail(pyrohip_state *s, double *part, int nparts, bool frame_copied, const double **dmin_out,
                bool defer)
 {
     pyrohip_ctx *c = s->ctx;
-    if (!frame_copied) fused_copy_frame(s);
+    if (!frame_copied) state_copy_frame4(s);
     if (defer && !c->global_cfl && nparts <= 128 * kMinStageBlocks) {
         // device-side stepping: the next policy kernel (one workgroup anyway) takes the
         // minimum of the partials itself (up to 128 per thread: the row-marching kernel's
@@ -811,14 +771,6 @@ int fused_tail(pyrohip_state *s, double *part, int nparts, bool frame_copied, co
     return 0;
 }
 
-void fused_swap(pyrohip_state *s)
-{
-    double *old_base = s->base;
-    s->base = s->alt_base;
-    s->alt_base = old_base;
-    s->d = s->base + geom_lead(s->g);
-}
-
 int fused_sync(pyrohip_state *s, const double *dmin)
 {
     pyrohip_ctx *c = s->ctx;
@@ -834,7 +786,7 @@ int fused_sync(pyrohip_state *s, const double *dmin)
                   "(compressible/simulation.py:68-71)");
         return PYROHIP_ERR_STATE;
     }
-    fused_swap(s);
+    state_swap_alt(s);
     s->next_cfl_min = ((double *)c->reduce_host)[0];
     s->cfl_kind = 0;
     return 0;
@@ -898,7 +850,7 @@ int comp_step_fused_ex(pyrohip_state *s, const pyrohip_comp_params *p, double dt
     if (post) PYRO_TRY(comm_post_halo(s, Uout));
     const double *dmin;
     PYRO_TRY(fused_tail(s, part, P.ntiles, true, &dmin, S != nullptr));   // the kernel wrote the ghost frame
-    if (S) { fused_swap(s); *dmin_out = dmin; s->halo_pending = post; return 0; }
+    if (S) { state_swap_alt(s); *dmin_out = dmin; s->halo_pending = post; return 0; }
     const int rc = fused_sync(s, dmin);
     s->halo_pending = post && rc == 0;
     return rc;
@@ -955,7 +907,7 @@ int comp_step_fused_sph_ex(pyrohip_state *s, const pyrohip_comp_params *p, doubl
                 (const double *)Uin, Uout, g, P, G, s->d_flag, part, S);
     const double *dmin;
     PYRO_TRY(fused_tail(s, part, P.ntiles, true, &dmin, S != nullptr));   // the kernel wrote the ghost frame
-    if (S) { fused_swap(s); *dmin_out = dmin; s->halo_pending = false; return 0; }
+    if (S) { state_swap_alt(s); *dmin_out = dmin; s->halo_pending = false; return 0; }
     // (the minimum is method_compute_timestep's: whole array, ghost cells of the NEW state as the
     // boundary rules will fill them included -- sphf_ghost_cfl; pyrohip_comp_dt takes it from here)
     const int rc = fused_sync(s, dmin);

@@ -29,6 +29,7 @@
 #include "common.h"
 #include "hydro.h"
 #include "reduce.h"
+#include "wave_march.h"
 
 #ifndef PYRO_FAST
 #define PYRO_FAST 0
@@ -56,28 +57,18 @@ constexpr int SWOUT = 56;          // columns a wavefront updates (reach of a ce
 #define SPHW_LIMIT2 limit2
 #define SPHW_SLOPE slope_shared
 #endif
-#if defined(PYRO_EMU)
-#define SPHW_FENCE() do {} while (0)
-#else
-#define SPHW_FENCE() __builtin_amdgcn_sched_barrier(0)
-#endif
 
-#if !defined(PYRO_EMU)
-template <int CTRL> __device__ __forceinline__ double sphw_dpp(double v)
+// lane l-1 / l+1 (wave_march.h) of a conserved state
+using pyro::lane_from_lower;
+using pyro::lane_from_upper;
+__device__ __forceinline__ Cons lane_from_lower(const Cons &U)
 {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xf, 0xf, true);
-    hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
+    return Cons{lane_from_lower(U.d), lane_from_lower(U.E), lane_from_lower(U.mx), lane_from_lower(U.my)};
 }
-__device__ __forceinline__ double lm1(double v) { return sphw_dpp<0x13C>(v); }   // wave_ror:1: lane l-1
-__device__ __forceinline__ double lp1(double v) { return sphw_dpp<0x134>(v); }   // wave_rol:1: lane l+1
-#else
-__device__ __forceinline__ double lm1(double v) { return __shfl_up(v, 1, 64); }
-__device__ __forceinline__ double lp1(double v) { return __shfl_down(v, 1, 64); }
-#endif
-__device__ __forceinline__ Cons lm1(const Cons &U) { return Cons{lm1(U.d), lm1(U.E), lm1(U.mx), lm1(U.my)}; }
-__device__ __forceinline__ Cons lp1(const Cons &U) { return Cons{lp1(U.d), lp1(U.E), lp1(U.mx), lp1(U.my)}; }
+__device__ __forceinline__ Cons lane_from_upper(const Cons &U)
+{
+    return Cons{lane_from_upper(U.d), lane_from_upper(U.E), lane_from_upper(U.mx), lane_from_upper(U.my)};
+}
 
 // per-lane LDS stash (slot s of lane l at doubles s * 64 + l)
 constexpr int SS_YM = 0, SS_YP = 4, SS_FXT = 8, SS_XP = 12, SS_XPC = 16, SS_FX = 20, SS_L2 = 24,
@@ -111,7 +102,7 @@ __global__ __launch_bounds__(64, 2) void k_sph_wave(const double *__restrict__ U
     const int per = (P.nunits + 7) / 8;
     const int unit = pyro_uniform(((int)blockIdx.x % 8) * per + (int)blockIdx.x / 8);
     if (unit >= P.nunits) return;
-    const int nreg = P.ncb * P.nsb;      // (units behind: the extra strip of the column strips [0, n_extra): comp_wave.hip)
+    const int nreg = P.ncb * P.nsb;      // (units behind: the extra strip of the column strips [0, n_extra): wave_march.h)
     const int cb = pyro_uniform(unit < nreg ? unit % P.ncb : unit - nreg);
     const int sb = pyro_uniform(unit < nreg ? unit / P.ncb : P.nsb);
     double dt = P.dt;
@@ -125,8 +116,8 @@ __global__ __launch_bounds__(64, 2) void k_sph_wave(const double *__restrict__ U
     int i0 = g.ilo + sb * P.L;
     int i1 = (sb == P.nsb - 1) ? g.ihi + 1 : i0 + P.L;
     if (cb < P.n_extra) {      // nsb + 1 strips of equal length (to a row)
-        i0 = g.ilo + (int)((long)sb * g.nx / (P.nsb + 1));
-        i1 = g.ilo + (int)((long)(sb + 1) * g.nx / (P.nsb + 1));
+        i0 = wave_extra_row(sb, P.nsb, g.nx, g.ilo);
+        i1 = wave_extra_row(sb + 1, P.nsb, g.nx, g.ilo);
     }
     const int j = g.jlo + cb * SWOUT - 4 + l;
     const int jc = (j < g.qy) ? j : g.qy - 1;              // ragged last strip: clamped, unused
@@ -234,48 +225,13 @@ __global__ __launch_bounds__(64, 2) void k_sph_wave(const double *__restrict__ U
         sput(st, SS_FXT, one); sput(st, SS_FX, one); sput(st, SS_L2, one); sput(st, SS_L2 + 4, one);
         st[SS_PXT * 64] = 1.0; st[SS_PX * 64] = 1.0; st[SS_CFL * 64] = INFINITY;
     }
-#if !defined(PYRO_EMU)
     // launches of up to two rounds of resident wavefronts: the two wavefronts of a SIMD take turns
-    // at the priority, two rows each, so that the pair ends together (comp_wave.hip; here the
+    // at the priority, two rows each, so that the pair ends together (wave_march.h; here the
     // second one holds it five eighths of the time: 2048^2 0.325 / 0.314 / 0.307 / 0.315 / 0.326 ms
-    // per step with 0 / 4 / 5 / 6 / 7 eighths)
-    unsigned hw_id;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw_id));
-    const int wslot = (int)(hw_id & 1u);
-    // (comp_wave.hip: the two wavefronts of a SIMD tell each other their rows left, the one behind takes the priority)
-    const bool prio_fb = P.prio_board != nullptr;
-    int *prio_mine = nullptr, *prio_other = nullptr;
-    int prio_seen = 0;
-    if (prio_fb) {
-        unsigned xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        int *const pair = P.prio_board + 2 * (int)(((xcc & 15u) << 12) | ((hw_id >> 4) & 0xfffu));
-        prio_mine = pair + wslot;
-        prio_other = pair + (wslot ^ 1);
-    }
-    auto prio_publish = [&](int k) {      // (behind the request of the next row)
-        if (!prio_fb) return;
-        __hip_atomic_store(prio_mine, (P.prio_tag << 16) | (i1 + 3 - k), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        prio_seen = __hip_atomic_load(prio_other, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    };
-#else
-    auto prio_publish = [](int) {};
-#endif
+    // per step with 0 / 4 / 5 / 6 / 7 eighths); with a board the one with more rows left takes it
+    WavePrio prio = wave_prio_begin(P.prio_board, P.prio_tag, true);
     for (int k = i0 - 4; k <= i1 + 3; k++) {
-#if !defined(PYRO_EMU)
-        if (prio_fb) {
-            const int seen = __builtin_amdgcn_readfirstlane(prio_seen);
-            const int left = i1 + 3 - k;
-            const int other_left = ((seen >> 16) == P.prio_tag) ? (seen & 0xffff) : left;
-            if (left > other_left) __builtin_amdgcn_s_setprio(1);
-            else if (left < other_left) __builtin_amdgcn_s_setprio(0);
-        } else
-        if (P.prio_duty > 0) {
-            const int phase = ((k - i0) >> 1) & 7;
-            if (wslot ? (phase < P.prio_duty) : (phase >= P.prio_duty)) __builtin_amdgcn_s_setprio(1);
-            else __builtin_amdgcn_s_setprio(0);
-        }
-#endif
+        wave_prio_turn(prio, k, i0, i1 + 3, P.prio_duty);
 #pragma unroll
         for (int n = 0; n < 4; n++) { wr[n] = wr[n + 1]; wu[n] = wu[n + 1]; wv[n] = wv[n + 1]; wp[n] = wp[n + 1]; }
         if (!SPHW_DELAY) Uem = Ue;
@@ -290,7 +246,7 @@ __global__ __launch_bounds__(64, 2) void k_sph_wave(const double *__restrict__ U
         // ---- row k arrives: primitives
         {
             Cons U = Upre;
-            if (!SPHW_DELAY) { Upre = loadU(k + 1); prio_publish(k); }
+            if (!SPHW_DELAY) { Upre = loadU(k + 1); wave_prio_publish(prio, i1 + 3 - k); }
             const bool interior = row_in(k) && jin;
             const bool dnan = nan_bits(U.d);      // np.maximum keeps a NaN: the floor must not launder it
             if (interior) U.d = fmax(U.d, P.small_dens);
@@ -302,12 +258,12 @@ __global__ __launch_bounds__(64, 2) void k_sph_wave(const double *__restrict__ U
 #if !defined(PYRO_EMU)
                 asm volatile("" : "+v"(wr[4]), "+v"(wu[4]), "+v"(wv[4]), "+v"(wp[4]));   // (the arrived row is consumed HERE)
 #endif
-                SPHW_FENCE();
+                PYRO_SCHED_FENCE();
                 if (k - 1 >= i0 + 4 && jout) store_row(Upend, k - 5);      // the update iteration k-1 made
                 Ucx = loadU(k - 4);                 // (in front of the next row's request: its wait leaves that one out)
                 Upre = loadU(k + 1);
-                prio_publish(k);
-                SPHW_FENCE();
+                wave_prio_publish(prio, i1 + 3 - k);
+                PYRO_SCHED_FENCE();
             }
         }
         // ---- flatten_x and limit2_x of row k-2 (window index 2)
@@ -341,7 +297,7 @@ __global__ __launch_bounds__(64, 2) void k_sph_wave(const double *__restrict__ U
             const bool frow = (k >= i0 + 4);           // row f is updated by this strip
             // geometry of rows i-1 (w = -1), i (0), i+1 (+1) at column j (jp: j + 1)
             const double cB = FAC ? st[SS_CB * 64] : 0.0, cC = FAC ? st[SS_CC * 64] : 0.0;
-            const double cBp = FAC ? lp1(cB) : 0.0, cCp = FAC ? lp1(cC) : 0.0;
+            const double cBp = FAC ? lane_from_upper(cB) : 0.0, cCp = FAC ? lane_from_upper(cC) : 0.0;
             auto rowi = [&](int w) { return w < 0 ? i - 1 : (w == 0 ? i : ipc); };
             auto gAx = [&](int w) { return FAC ? fabs(RF(0, rowi(w)) * cB) : GA.Ax(rowi(w), jc); };
             auto gAy = [&](int w, bool jp) {
@@ -353,7 +309,7 @@ __global__ __launch_bounds__(64, 2) void k_sph_wave(const double *__restrict__ U
             auto gLy = [&](int w) { return FAC ? RF(4, rowi(w)) : GA.Ly(rowi(w), jc); };
             const double gLx = P.dx;                   // Lx = dr everywhere (patch.py:262; checked by the caller for FAC)
             // FF: a / V, a / Ly, a / Lx as products (|A B| = |A| |B| exactly: the stash holds |B|, |C|)
-            const double cRE = FF ? st[SS_CRE * 64] : 0.0, cREp = FF ? lp1(cRE) : 0.0;
+            const double cRE = FF ? st[SS_CRE * 64] : 0.0, cREp = FF ? lane_from_upper(cRE) : 0.0;
             auto overV = [&](double a, int w, bool jp) {
                 return FF ? a * ((jp ? cREp : cRE) * RF(8, rowi(w))) : pdiv(a, gV(w, jp));
             };
@@ -365,15 +321,15 @@ __global__ __launch_bounds__(64, 2) void k_sph_wave(const double *__restrict__ U
             double ym[4], yp[4], l2y[4] = {0, 0, 0, 0};
 #pragma unroll
             for (int n = 0; n < 4; n++) {
-                ym[n] = lm1(q0[n]);
-                yp[n] = lp1(q0[n]);
+                ym[n] = lane_from_lower(q0[n]);
+                yp[n] = lane_from_upper(q0[n]);
                 if (limiter != 0) l2y[n] = SPHW_LIMIT2(ym[n], q0[n], yp[n]);
             }
             um = ym[1]; vm = ym[2];
             double xi = 1.0;
             if (flat) {     // flatten_multid (reconstruction.py:167-183)
-                const double fy = flatten_1d(lm1(ym[3]), ym[3], yp[3], lp1(yp[3]), ym[2], yp[2], P.z0, P.z1, P.delta);
-                const double fym = lm1(fy), fyp = lp1(fy);
+                const double fy = flatten_1d(lane_from_lower(ym[3]), ym[3], yp[3], lane_from_upper(yp[3]), ym[2], yp[2], P.z0, P.z1, P.delta);
+                const double fym = lane_from_lower(fy), fyp = lane_from_upper(fy);
                 const double px_ = (qp[3] - qm[3] > 0) ? fxa : fxn;
                 const double py_ = (yp[3] - ym[3] > 0) ? fym : fyp;
                 xi = fmin(fmin(fxb, px_), fmin(fy, py_));
@@ -385,11 +341,11 @@ __global__ __launch_bounds__(64, 2) void k_sph_wave(const double *__restrict__ U
 #pragma unroll
             for (int n = 0; n < 4; n++) {
                 dqx[n] = xi * SPHW_SLOPE(l2a[n], l2b[n], l2n[n], qm[n], q0[n], qp[n], limiter);
-                const double l2m = (limiter == 2) ? lm1(l2y[n]) : 0.0;
-                const double l2p = (limiter == 2) ? lp1(l2y[n]) : 0.0;
+                const double l2m = (limiter == 2) ? lane_from_lower(l2y[n]) : 0.0;
+                const double l2p = (limiter == 2) ? lane_from_upper(l2y[n]) : 0.0;
                 dqy[n] = xi * SPHW_SLOPE(l2m, l2y[n], l2p, ym[n], q0[n], yp[n], limiter);
             }
-            SPHW_FENCE();
+            PYRO_SCHED_FENCE();
             // ---- external sources on the face states (simulation.py:117-124, unsplit_fluxes.py:
             // 308-326): a ghost cell takes the value of the cell its boundary rule copies from,
             // with the variable's sign
@@ -440,7 +396,7 @@ __global__ __launch_bounds__(64, 2) void k_sph_wave(const double *__restrict__ U
                 }
                 Dn = ux + vy;
             }
-            const double Dn_p = lp1(Dn);
+            const double Dn_p = lane_from_upper(Dn);
             double avx = 0.0, avy = 0.0;
             if (row_in(i) && jin) {
                 const double divU_x = 0.5 * (Dn + Dn_p);
@@ -450,7 +406,7 @@ __global__ __launch_bounds__(64, 2) void k_sph_wave(const double *__restrict__ U
                 const double divU_y = 0.5 * (Dp + Dn);
                 avy = P.cvisc * fmax(-divU_y * gLy(-1), 0.0);
             }
-            SPHW_FENCE();
+            PYRO_SCHED_FENCE();
             // ---- x states of row c (interface.py:106, 216-224), transverse x flux on its lower face
             // c^2 (interface.py:122; the contracted build: without the root)
             const double cs2 = PYRO_FAST ? gamma * q0[3] * prcp(q0[0]) : 0.0;
@@ -470,7 +426,7 @@ __global__ __launch_bounds__(64, 2) void k_sph_wave(const double *__restrict__ U
             Cons FxTn{0, 0, 0, 0};
             double pxtn = 0.0;
             if (xface) FxTn = sphf_face(sget(st, SS_XP), XMn, gamma, true, P.solid_xl && i == g.ilo, pxtn);
-            SPHW_FENCE();
+            PYRO_SCHED_FENCE();
             // ---- row f: y states corrected with F_xT of rows f, f+1 (unsplit_fluxes.py:444-481: the
             // upper state takes the volume of the cell above its face), final y flux
             Cons Fy{0, 0, 0, 0}, Fyh{0, 0, 0, 0};
@@ -483,18 +439,18 @@ __global__ __launch_bounds__(64, 2) void k_sph_wave(const double *__restrict__ U
                 YMc.mx += overLx(-hdt * dpx);
                 Cons YPc = sphf_corrected(sget(st, SS_YP), FxTn, Ahi, FxTp, Alo, overV(hdt, -1, true));
                 YPc.mx += overLx(-hdt * dpx);
-                Fy = sphf_face(lm1(YPc), YMc, gamma, false, P.solid_yl && j == g.jlo, py);
+                Fy = sphf_face(lane_from_lower(YPc), YMc, gamma, false, P.solid_yl && j == g.jlo, py);
                 if (SPHW_DELAY) Uem = old_f();
-                const Cons Umy = lm1(Uem);
+                const Cons Umy = lane_from_lower(Uem);
                 Fy.d += avy * (Umy.d - Uem.d);
                 Fy.E += avy * (Umy.E - Uem.E);
                 Fy.mx += avy * (Umy.mx - Uem.mx);
                 Fy.my += avy * (Umy.my - Uem.my);
-                Fyh = lp1(Fy);
-                pyh = lp1(py);
+                Fyh = lane_from_upper(Fy);
+                pyh = lane_from_upper(py);
             }
             if (xface) { sput(st, SS_FXT, FxTn); st[SS_PXT * 64] = pxtn; }
-            SPHW_FENCE();
+            PYRO_SCHED_FENCE();
             // ---- y states of row c (interface.py:106, 226-234), transverse y flux on its lower face
             trace_states(q0[0], q0[2], q0[1], q0[3], dqy[0], dqy[2], dqy[1], dqy[3], gamma,
                          overLy(dt, 0), lo, hi);
@@ -514,14 +470,14 @@ __global__ __launch_bounds__(64, 2) void k_sph_wave(const double *__restrict__ U
             sput(st, SS_YM, YMn);
             sput(st, SS_YP, YPn);
             double pyt = 0.0;
-            const Cons FyT = sphf_face(lm1(YPn), YMn, gamma, false, P.solid_yl && j == g.jlo, pyt);
-            SPHW_FENCE();
+            const Cons FyT = sphf_face(lane_from_lower(YPn), YMn, gamma, false, P.solid_yl && j == g.jlo, pyt);
+            PYRO_SCHED_FENCE();
             // ---- transverse correction of the x states of row c, final x flux
             Cons XMc, XPc;
             {
-                const Cons FyTh = lp1(FyT);            // F_yT at (i, j+1)
+                const Cons FyTh = lane_from_upper(FyT);            // F_yT at (i, j+1)
                 const double Ahi = gAy(0, true), Alo = gAy(0, false);
-                const double dpy = lp1(pyt) - pyt;
+                const double dpy = lane_from_upper(pyt) - pyt;
                 XMc = sphf_corrected(XMn, FyTh, Ahi, FyT, Alo, overV(hdt, 0, false));
                 XMc.my += overLy(-hdt * dpy, 0);
                 XPc = sphf_corrected(XPn, FyTh, Ahi, FyT, Alo, overV(hdt, 1, false));
@@ -539,7 +495,7 @@ __global__ __launch_bounds__(64, 2) void k_sph_wave(const double *__restrict__ U
                 Fxn.my += avx * (Uem.my - Ue.my);
             }
             sput(st, SS_XPC, XPc);
-            SPHW_FENCE();
+            PYRO_SCHED_FENCE();
             // ---- conservative update of row f with the area / volume arrays, the pressure gradients
             // and the source predictor-corrector (simulation.py:375-423) + CFL of the new state
             if (frow && jout) {
@@ -610,25 +566,6 @@ __global__ __launch_bounds__(64, 2) void k_sph_wave(const double *__restrict__ U
     if (l == 0) partial[sb * P.ncb + cb] = wm;
 }
 
-// rows per strip: whole rounds of the resident wavefronts (two per SIMD) + one strip time for the
-// stragglers of the last round (comp_wave.hip: wave_rows); a strip costs L + 8 iterations
-int sphw_rows(int nx, int ncb, int slots)
-{
-    if (nx <= 32) return nx;
-    long best_cost = -1;
-    int best = 32;
-    for (int L = 32; L <= 160 && L <= nx; L++) {
-        int nsb = (nx + L - 1) / L;
-        if (nsb > 1 && nx - (nsb - 1) * L < 4) nsb--;
-        const int Leff = (nx + nsb - 1) / nsb;
-        const long waves = (long)ncb * nsb;
-        const long rounds = (waves + slots - 1) / slots;
-        const long cost = (waves <= slots ? 1 : rounds + 1) * (Leff + 8);
-        if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = L; }
-    }
-    return best;
-}
-
 }  // namespace
 
 // SphericalPolar grid, one step in ONE launch of the row-marching kernel.  The caller checked what
@@ -656,11 +593,10 @@ int comp_step_wave_sph_ex(pyrohip_state *s, const pyrohip_comp_params *p, double
     const int fac = (h.rowf && h.colf) ? 1 : 0;       // the caller handed the 1-d factors over
     const int cus = c->num_cus > 0 ? c->num_cus : 256;
     P.ncb = (g.ny + SWOUT - 1) / SWOUT;
-    P.L = sphw_rows(g.nx, P.ncb, 8 * cus);
+    P.L = wave_strip_rows(g.nx, P.ncb, 8 * cus, 32);      // (slots: two wavefronts per SIMD)
     if (p->march_rows > 0) P.L = p->march_rows < g.nx ? p->march_rows : g.nx;
-    P.nsb = (g.nx + P.L - 1) / P.L;
-    if (P.nsb > 1 && g.nx - (P.nsb - 1) * P.L < g.ng) P.nsb--;
-    // (one round: as many strips as wavefront slots; the pairs of the SIMDs told their rows left: comp_wave.hip)
+    P.nsb = wave_strip_count(g.nx, P.L, g.ng);
+    // (one round: as many strips as wavefront slots; the pairs of the SIMDs told their rows left: wave_march.h)
     P.n_extra = p->march_rows > 0 ? 0 : wave_fill_extra(P.ncb, P.nsb, g.nx, 8 * cus);
     P.nunits = P.ncb * P.nsb + P.n_extra;
     P.prio_duty = (P.nunits <= 2 * 8 * cus) ? 5 : 0;
@@ -682,7 +618,7 @@ int comp_step_wave_sph_ex(pyrohip_state *s, const pyrohip_comp_params *p, double
     s->frame_prefilled = false;
     const double *dmin;
     PYRO_TRY(fused_tail(s, part, P.nunits, frame_done, &dmin, S != nullptr));
-    if (S) { fused_swap(s); *dmin_out = dmin; s->halo_pending = false; return 0; }
+    if (S) { state_swap_alt(s); *dmin_out = dmin; s->halo_pending = false; return 0; }
     // (the minimum is method_compute_timestep's: whole array, the new state's ghost cells as the
     // boundary rules will fill them included -- sphf_ghost_cfl)
     const int rc = fused_sync(s, dmin);

@@ -37,6 +37,7 @@
 #include "common.h"
 #include "hydro.h"
 #include "reduce.h"
+#include "wave_march.h"
 
 #ifndef PYRO_FAST
 #define PYRO_FAST 0
@@ -62,57 +63,26 @@ constexpr int WOUT = 56;          // columns a wavefront updates
 #define LIMIT2 limit2
 #define SLOPE_SHARED slope_shared
 #endif
-// stage boundary: the scheduler may not move instructions across it.  The
-// stages are written in the order that keeps the live ranges short (a value is
-// produced right before the Riemann problem that consumes it); left alone, the
-// scheduler interleaves the stages for ILP and pushes the kernel over 256 VGPRs.
-#if defined(PYRO_EMU)
-#define STAGE_FENCE() do {} while (0)
-#else
-#define STAGE_FENCE() __builtin_amdgcn_sched_barrier(0)
-#endif
 constexpr int WAVE_PRIO_SHIFT = 1;    // the priority changes hands in units of 2 rows
 constexpr int WAVE_MINW = 2;          // waves per SIMD the register allocation must allow
 
-// value of the same variable in lane l-1 / l+1.  The ends of the wavefront are
-// apron lanes whose results are never stored, but what they compute matters
-// for speed: a wavefront executes every lazily evaluated branch (flattening,
-// the shock branches of the wave-speed estimate) that ANY lane takes.  The DPP
-// moves therefore ROTATE (lane 0 reads lane 63: a finite physical state, equal
-// to its own in uniform regions) -- with shifts + bound_ctrl the end lanes read
-// 0, went to NaN and dragged the wavefront through the slow paths (+8 v_rsq /
-// v_rcp per row, PMC); shifts that keep the own value need a register copy in
-// front of every move (the `old` operand is tied to the destination).  The
-// shuffle variant (the emulator's) keeps the own value.  gfx950 keeps the GFX9
-// whole-wave DPP shifts (wave_shr:1 / wave_shl:1 move data across all 64 lanes,
-// tools/dpp_probe.hip): two
-// v_mov_b32_dpp per double, a register-to-register VALU move without the
-// LDS-crossbar round trip of ds_bpermute (__shfl_up / __shfl_down).
+// lane l-1 / l+1 (wave_march.h) of a conserved state; two lanes away
+using pyro::lane_from_lower;
+using pyro::lane_from_upper;
 #if !defined(PYRO_EMU)
-template <int CTRL> __device__ __forceinline__ double lane_dpp(double v)
-{
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xf, 0xf, true);
-    hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double lane_m1(double v) { return lane_dpp<0x13C>(v); }   // wave_ror:1
-__device__ __forceinline__ double lane_p1(double v) { return lane_dpp<0x134>(v); }   // wave_rol:1
-__device__ __forceinline__ double lane_m2(double v) { return lane_m1(lane_m1(v)); }
-__device__ __forceinline__ double lane_p2(double v) { return lane_p1(lane_p1(v)); }
+__device__ __forceinline__ double lane_m2(double v) { return lane_from_lower(lane_from_lower(v)); }
+__device__ __forceinline__ double lane_p2(double v) { return lane_from_upper(lane_from_upper(v)); }
 #else
-__device__ __forceinline__ double lane_m1(double v) { return __shfl_up(v, 1, 64); }
-__device__ __forceinline__ double lane_p1(double v) { return __shfl_down(v, 1, 64); }
 __device__ __forceinline__ double lane_m2(double v) { return __shfl_up(v, 2, 64); }
 __device__ __forceinline__ double lane_p2(double v) { return __shfl_down(v, 2, 64); }
 #endif
-__device__ __forceinline__ Cons lane_m1(const Cons &U)
+__device__ __forceinline__ Cons lane_from_lower(const Cons &U)
 {
-    return Cons{lane_m1(U.d), lane_m1(U.E), lane_m1(U.mx), lane_m1(U.my)};
+    return Cons{lane_from_lower(U.d), lane_from_lower(U.E), lane_from_lower(U.mx), lane_from_lower(U.my)};
 }
-__device__ __forceinline__ Cons lane_p1(const Cons &U)
+__device__ __forceinline__ Cons lane_from_upper(const Cons &U)
 {
-    return Cons{lane_p1(U.d), lane_p1(U.E), lane_p1(U.mx), lane_p1(U.my)};
+    return Cons{lane_from_upper(U.d), lane_from_upper(U.E), lane_from_upper(U.mx), lane_from_upper(U.my)};
 }
 
 // Per-lane stash in LDS for the values a row hands to the next iteration
@@ -271,8 +241,8 @@ __global__ __launch_bounds__(64, WAVE_MINW) void k_ctu_wave(const double *__rest
     // than L, so that no strip is shorter than the ghost width -- comp_step_wave_ex)
     int i1 = (sb == P.nsb - 1) ? g.ihi + 1 : i0 + P.L;
     if (cb < P.n_extra) {      // nsb + 1 strips of equal length (to a row)
-        i0 = g.ilo + (int)((long)sb * g.nx / (P.nsb + 1));
-        i1 = g.ilo + (int)((long)(sb + 1) * g.nx / (P.nsb + 1));
+        i0 = wave_extra_row(sb, P.nsb, g.nx, g.ilo);
+        i1 = wave_extra_row(sb + 1, P.nsb, g.nx, g.ilo);
     }
     if (P.n_short > 0 && sb >= P.nsb - P.n_short - P.n_tail) {
         // long strips, then n_short short ones, then n_tail long ones (a slab's last boundary strip)
@@ -544,23 +514,14 @@ __global__ __launch_bounds__(64, WAVE_MINW) void k_ctu_wave(const double *__rest
     }
 
 #if !defined(PYRO_EMU)
-    // The two wavefronts of a SIMD are arbitrated by age: the older one runs almost as if it
-    // were alone, the younger one gets what is left, and when the older one is done the younger
-    // finishes alone at half the issue rate -- measured per wavefront at 4096^2 (one round of
-    // resident wavefronts; tools/timeline_report.py): 1.11 M cycles for one half of the
-    // wavefronts, 1.56 M for the other half, on every SIMD.  With many rounds a new wavefront
-    // takes the place of the finished one and nothing is lost; with one or two rounds the
-    // tail is a third of the launch.  So the two take turns at the higher priority, a few
-    // rows each (by the wavefront's slot number on its SIMD), and finish together.
+    // The two wavefronts of a SIMD take turns at the priority and finish together; by the pair's rows-left
+    // board where the launch has one: the protocol of wave_march.h (WavePrio), which has the explanation.
+    // This kernel keeps its own copy of the code: with the helpers its FB instances came out with other
+    // vector instruction sequences and spill code (out of scalar registers, every change of the set-up moves
+    // the spills), the other instances and the other kernels did not (docs/HISTORY.md).  A fix goes to both.
     unsigned hw_id;
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw_id));
     const int wslot = (int)(hw_id & 1u);
-    // Round 6, second half: the turns by phase are blind -- each wavefront counts its OWN rows, the two
-    // drift apart and the better duty changes with the strip length (tools/wave_timeline.py, 4096^2: the
-    // second wavefront ends 90 us before the first with seven eighths, 80 us after it with four, together with
-    // five; 3072^2 wants seven).  With a board (P.prio_board: one word per SIMD and slot in device memory, the
-    // two wavefronts of a SIMD sit on one XCD = one L2) each tells the other how many rows it has left, a row
-    // late, and the one with more rows left takes the priority: the pair ends together whatever the strips.
     // (FB: instances of their own -- the launches of many rounds, the headline's, keep the code they had; the
     // method-of-lines instances have no register for it)
     const bool prio_fb = FB && !MOL && P.prio_board != nullptr;
@@ -650,7 +611,7 @@ __global__ __launch_bounds__(64, WAVE_MINW) void k_ctu_wave(const double *__rest
 #if !defined(PYRO_EMU)
                 asm volatile("" : "+v"(wr[4]), "+v"(wu[4]), "+v"(wv[4]), "+v"(wp[4]));
 #endif
-                STAGE_FENCE();
+                PYRO_SCHED_FENCE();
                 if (k - 1 >= i0 + 4 && jout) {      // the update of row k-5, made by iteration k-1
                     const unsigned off = (unsigned)(k - 5 - rbase) * pitch8 + (unsigned)j * 8u;
                     *(double *)(sbase_out + off) = Upend.d; *(double *)(sbase_out + plb + off) = Upend.E;
@@ -659,7 +620,7 @@ __global__ __launch_bounds__(64, WAVE_MINW) void k_ctu_wave(const double *__rest
                 Ucx = loadU(k - 4);                 // (in front of the next row's request: its wait leaves that one out)
                 Upre = loadU(k + 1);
                 prio_publish(k);
-                STAGE_FENCE();
+                PYRO_SCHED_FENCE();
             }
         }
         // ---- flatten_x and limit2_x of row k-2 (window index 2)
@@ -719,8 +680,8 @@ __global__ __launch_bounds__(64, WAVE_MINW) void k_ctu_wave(const double *__rest
             double ym[4], yp[4], l2y[4] = {0, 0, 0, 0};
 #pragma unroll
             for (int n = 0; n < 4; n++) {
-                ym[n] = lane_m1(q0[n]);
-                yp[n] = lane_p1(q0[n]);
+                ym[n] = lane_from_lower(q0[n]);
+                yp[n] = lane_from_upper(q0[n]);
                 if (limiter != 0) l2y[n] = LIMIT2(ym[n], q0[n], yp[n]);
             }
             um = ym[1]; vm = ym[2];
@@ -730,7 +691,7 @@ __global__ __launch_bounds__(64, WAVE_MINW) void k_ctu_wave(const double *__rest
                 // one of the UPWIND neighbour (w.r.t. the pressure gradient)
                 const double fy = flatten_1d_k(lane_m2(q0[3]), ym[3], yp[3], lane_p2(q0[3]), ym[2],
                                                yp[2], FlatKTab{ct});
-                const double fym = lane_m1(fy), fyp = lane_p1(fy);
+                const double fym = lane_from_lower(fy), fyp = lane_from_upper(fy);
                 const double px = (qp[3] - qm[3] > 0) ? fxa : fxn;
                 const double py = (yp[3] - ym[3] > 0) ? fym : fyp;
                 xi = fmin(fmin(fxb, px), fmin(fy, py));
@@ -742,8 +703,8 @@ __global__ __launch_bounds__(64, WAVE_MINW) void k_ctu_wave(const double *__rest
 #pragma unroll
             for (int n = 0; n < 4; n++) {
                 dqx[n] = xi * SLOPE_SHARED(l2a[n], l2b[n], l2n[n], qm[n], q0[n], qp[n], limiter);
-                const double l2m = (limiter == 2) ? lane_m1(l2y[n]) : 0.0;
-                const double l2p = (limiter == 2) ? lane_p1(l2y[n]) : 0.0;
+                const double l2m = (limiter == 2) ? lane_from_lower(l2y[n]) : 0.0;
+                const double l2p = (limiter == 2) ? lane_from_upper(l2y[n]) : 0.0;
                 dqy[n] = xi * SLOPE_SHARED(l2m, l2y[n], l2p, ym[n], q0[n], yp[n], limiter);
             }
             if (yfin) {      // integration.py:120-129, the terms before this stage's own increment
@@ -761,7 +722,7 @@ __global__ __launch_bounds__(64, WAVE_MINW) void k_ctu_wave(const double *__rest
                 }
                 st_put(st, ST_FXT, Yf0);
             }
-            STAGE_FENCE();
+            PYRO_SCHED_FENCE();
             // source terms of the face states (apply_source_terms, unsplit_fluxes.py:247-330)
             Cons Ug{0.0, 0.0, 0.0, 0.0};
             double sgn = 1.0, hp = 0.0;
@@ -782,7 +743,7 @@ __global__ __launch_bounds__(64, WAVE_MINW) void k_ctu_wave(const double *__rest
             // in y (interface.py:366-376: only faces i in [ilo, ihi], j in [jlo, jhi])
             Dn = div_u_vertex_r(q0[1], um, qm[1], up, q0[2], qm[2], vm, vp, UC_EXACT(DX), UC_EXACT(DY),
                                 US(RDX, P.rdx), US(RDY, P.rdy));
-            const double Dn_p = lane_p1(Dn);
+            const double Dn_p = lane_from_upper(Dn);
             double avx = 0.0, avy = 0.0;
             if (i >= g.ilo && (i <= g.ihi || (P.avx_hi && i == g.ihi + 1)) && jin) {
                 const double divU_x = 0.5 * (Dn + Dn_p);
@@ -800,7 +761,7 @@ __global__ __launch_bounds__(64, WAVE_MINW) void k_ctu_wave(const double *__rest
                 avy = UC(CVISC) * fmax(-divU_y * UC(DY), 0.0);
 #endif
             }
-            STAGE_FENCE();
+            PYRO_SCHED_FENCE();
             // -- x states of row c, transverse x flux on its lower face
             Trace lo, hi;
             double gamma = US(GAMMA, P.gamma);
@@ -838,7 +799,7 @@ __global__ __launch_bounds__(64, WAVE_MINW) void k_ctu_wave(const double *__rest
             if (TQ) {
                 st[ST_XPQ * 64] = qxp.un; st[(ST_XPQ + 1) * 64] = qxp.ut; st[(ST_XPQ + 2) * 64] = qxp.p;
             }
-            STAGE_FENCE();
+            PYRO_SCHED_FENCE();
             // -- row f: y states corrected with FxT of rows f, f+1; final y flux
             Cons Fy, Fyh;
             if (frow) {
@@ -856,20 +817,20 @@ __global__ __launch_bounds__(64, WAVE_MINW) void k_ctu_wave(const double *__rest
                 YPc = corr(st_get(st, ST_YP), FxTn, FxTp, hdtV, Ax);
 #endif
                 }
-                Fy = from_nf(riemann_face<SOLVER>(to_nf(lane_m1(YPc), false), to_nf(YMc, false),
+                Fy = from_nf(riemann_face<SOLVER>(to_nf(lane_from_lower(YPc), false), to_nf(YMc, false),
                                                   UC_GASK(), false, P.solid_yl && j == g.jlo), false);
                 // (DELAY: the exact old state of the row, read a second time -- not the rebuilt one)
                 Cons Uv = Uem;
                 if (DELAY) { Uv = Ucx; if (jin) Uv.d = fmax(Uv.d, US(SMALLD, P.small_dens)); }
-                const Cons Umy = lane_m1(Uv);
+                const Cons Umy = lane_from_lower(Uv);
                 Fy.d += avy * (Umy.d - Uv.d);
                 Fy.E += avy * (Umy.E - Uv.E);
                 Fy.mx += avy * (Umy.mx - Uv.mx);
                 Fy.my += avy * (Umy.my - Uv.my);
-                Fyh = lane_p1(Fy);
+                Fyh = lane_from_upper(Fy);
             }
             if (!MOL && xface) st_put(st, ST_FXT, FxTn);
-            STAGE_FENCE();
+            PYRO_SCHED_FENCE();
             // -- y states of row c, transverse y flux on its lower face
             gamma = US(GAMMA, P.gamma);
             if (MOL) {     // (normal / transverse frame of the y direction: un = v, ut = u)
@@ -894,20 +855,20 @@ __global__ __launch_bounds__(64, WAVE_MINW) void k_ctu_wave(const double *__rest
             Cons FyT;
             if (MOL) {
             } else if (TQ) {
-                const FaceQ ql{lane_m1(qyp.un), lane_m1(qyp.ut), lane_m1(qyp.p)};
-                FyT = from_nf(hllc_flux_impl<true>(to_nf(lane_m1(YPn), false), to_nf(YMn, false), ql,
+                const FaceQ ql{lane_from_lower(qyp.un), lane_from_lower(qyp.ut), lane_from_lower(qyp.p)};
+                FyT = from_nf(hllc_flux_impl<true>(to_nf(lane_from_lower(YPn), false), to_nf(YMn, false), ql,
                                                    qym, UC_GASK(), false), false);
             } else
-                FyT = from_nf(riemann_face<SOLVER>(to_nf(lane_m1(YPn), false), to_nf(YMn, false),
+                FyT = from_nf(riemann_face<SOLVER>(to_nf(lane_from_lower(YPn), false), to_nf(YMn, false),
                                                    UC_GASK(), false, P.solid_yl && j == g.jlo), false);
-            STAGE_FENCE();
+            PYRO_SCHED_FENCE();
             // -- transverse correction of the x states of row c, final x flux
             Cons XMc = XMn, XPc = XPn;
 #if !PYRO_FAST
             const double Ay = UC(DX);
 #endif
             if (!MOL) {
-            const Cons FyTh = lane_p1(FyT);            // FyT at (i, j+1)
+            const Cons FyTh = lane_from_upper(FyT);            // FyT at (i, j+1)
 #if PYRO_FAST
             const double ky = US(KY, s_ky);
             XMc = corr_k(XMn, FyTh, FyT, ky);
@@ -934,7 +895,7 @@ __global__ __launch_bounds__(64, WAVE_MINW) void k_ctu_wave(const double *__rest
                 Fxn.my += avx * (Uxm.my - Ue.my);
             }
             st_put(st, ST_XPC, XPc);
-            STAGE_FENCE();
+            PYRO_SCHED_FENCE();
             // -- conservative update of row f + CFL of the new state
             if (frow && jout) {
                 const Cons Fxp = st_get(st, ST_FX);
@@ -1039,39 +1000,6 @@ __global__ __launch_bounds__(64, WAVE_MINW) void k_ctu_wave(const double *__rest
     finish(__shfl(wave_reduce_min(cfl), 0, 64), bad);
 }
 
-// Rows per strip (a strip costs L + 8 iterations, of which the 8 warm-up ones are cheap: ~3 % of
-// the instructions at L = 69).  What matters is the LAST round of resident wavefronts: the
-// launch lasts ceil(wavefronts / slots) strip times, and a last round that fills a third to a
-// half of the slots is the worst case -- measured at 8192^2 (147 column strips, 2048 slots,
-// profiles/r04_march_sweep.txt): 59 rows = 9.98 rounds 2.525 ms, 74 rows = 7.97 rounds 2.525,
-// 75 rows = 7.9 rounds 2.549, 64 rows = 9.19 rounds 2.576, 82 rows = 7.18 rounds 2.588, 69 rows =
-// 8.54 rounds 2.624 (round 3's choice, by (rounds + 1/2)(L + 8) with fractional rounds), 112 rows
-// = 5.31 rounds 2.628, 128 rows 2.688.  So: the strip length in 32 .. 160 rows that minimises
-// (ceil(wavefronts / slots) + 1) x (L + 8) -- WHOLE rounds, plus a strip time for the stragglers of
-// the last one (few long rounds end worse than many short ones: the two wavefronts of a SIMD are
-// served oldest first) --, the shorter strip winning a tie.  One round when everything is resident at once
-// (4096^2: 74 x 27 strips of 152 rows).
-static int wave_rows(int nx, int ncb, int slots)
-{
-    // (round 6: strips down to 8 rows -- grids of 1024^2 ... 1792^2 cells fill the slots with ONE round of
-    // 10- to 28-row strips and pass the tile kernel that way: comp_api.hip: takes_wave_kernel_ctu)
-    if (nx <= 32) return nx;
-    long best_cost = -1;
-    int best = 32;
-    for (int L = 8; L <= 160 && L <= nx; L++) {
-        int nsb = (nx + L - 1) / L;
-        if (nsb > 1 && nx - (nsb - 1) * L < 4) nsb--;        // short last strip joins its predecessor
-        const int Leff = (nx + nsb - 1) / nsb;                // longest strip
-        const long waves = (long)ncb * nsb;
-        const long rounds = (waves + slots - 1) / slots;
-        // strip times: one round when everything is resident at once, otherwise whole rounds
-        // + one more for the stragglers of the last one
-        const long cost = (waves <= slots ? 1 : rounds + 1) * (Leff + 8);
-        if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = L; }
-    }
-    return best;
-}
-
 // Launches of up to two rounds of resident wavefronts: the second wavefront of a SIMD (by
 // its slot number) holds the higher priority six eighths of the time, so that the pair ends
 // together (see the kernel; measured at 4096^2, one round: 0.804 -> 0.736 ms, duty 4 / 5 / 6 /
@@ -1103,10 +1031,11 @@ static WaveGeom wave_geometry(int nx, int ny, int ng, int cus, int march_rows)
 {
     WaveGeom w;
     w.ncb = (ny + WOUT - 1) / WOUT;
-    w.L = wave_rows(nx, w.ncb, 4 * WAVE_MINW * cus);      // slots: wavefronts resident at once
+    // (round 6: strips down to 8 rows -- grids of 1024^2 ... 1792^2 cells fill the slots with ONE round of
+    // 10- to 28-row strips and pass the tile kernel that way: comp_api.hip: takes_wave_kernel_ctu)
+    w.L = wave_strip_rows(nx, w.ncb, 4 * WAVE_MINW * cus, 8);      // slots: wavefronts resident at once
     if (march_rows > 0) w.L = march_rows < nx ? march_rows : nx;
-    w.nsb = (nx + w.L - 1) / w.L;
-    if (w.nsb > 1 && nx - (w.nsb - 1) * w.L < ng) w.nsb--;
+    w.nsb = wave_strip_count(nx, w.L, ng);
     w.overlap = (w.nsb >= 3 && w.L >= ng) ? 1 : 0;
     return w;
 }
@@ -1243,7 +1172,7 @@ int comp_step_wave_ex(pyrohip_state *s, const pyrohip_comp_params *p, double dt,
         // slots for a whole strip time.)
         // old ghost frame -> new buffer, BEFORE the halos land in it (device-side stepping: the
         // fill before this step has written it already, evolve.hip: k_fill_frame2)
-        if (!s->frame_prefilled) fused_copy_frame(s);
+        if (!s->frame_prefilled) state_copy_frame4(s);
         s->frame_prefilled = false;
         hipStream_t bs = nullptr;
         PYRO_TRY(comm_fork_boundary(s, &bs));
@@ -1266,7 +1195,7 @@ int comp_step_wave_ex(pyrohip_state *s, const pyrohip_comp_params *p, double dt,
         const double *dmin;
         PYRO_TRY(fused_tail(s, part, nwg, true, &dmin, S != nullptr));
         int rc = 0;
-        if (S) { fused_swap(s); *dmin_out = dmin; }
+        if (S) { state_swap_alt(s); *dmin_out = dmin; }
         else rc = fused_sync(s, dmin);
         s->halo_pending = (rc == 0);
         return rc;
@@ -1293,7 +1222,7 @@ int comp_step_wave_ex(pyrohip_state *s, const pyrohip_comp_params *p, double dt,
                     WLDS_BYTES, (const double *)Uin, Uout, g, P, s->d_flag, part, S);
         PYRO_CHECK_HIP(hipGetLastError());
         s->frame_prefilled = false;
-        fused_swap(s);
+        state_swap_alt(s);
         *dmin_out = (const double *)(s->d_polmem + 3 * kPolSetWords);
         s->halo_pending = false;
         return 0;
@@ -1304,7 +1233,7 @@ int comp_step_wave_ex(pyrohip_state *s, const pyrohip_comp_params *p, double dt,
     PYRO_LAUNCH(c, "k_ctu_wave", (P.prio_board ? kernels_fb : kernels)[solver][std_rec], dim3(nblocks),
                 dim3(64), WLDS_BYTES, (const double *)Uin, Uout, g, P, s->d_flag, part, S);
     if (post) {        // too few strips to overlap: the exchange follows the whole update
-        if (!s->frame_prefilled) fused_copy_frame(s);
+        if (!s->frame_prefilled) state_copy_frame4(s);
         PYRO_TRY(comm_post_halo(s, Uout));
     }
     const double *dmin;
@@ -1313,7 +1242,7 @@ int comp_step_wave_ex(pyrohip_state *s, const pyrohip_comp_params *p, double dt,
     const bool frame_done = post || s->frame_prefilled;
     s->frame_prefilled = false;
     PYRO_TRY(fused_tail(s, part, nwg, frame_done, &dmin, S != nullptr));
-    if (S) { fused_swap(s); *dmin_out = dmin; s->halo_pending = post; return 0; }
+    if (S) { state_swap_alt(s); *dmin_out = dmin; s->halo_pending = post; return 0; }
     const int rc = fused_sync(s, dmin);
     s->halo_pending = post && rc == 0;
     return rc;
@@ -1446,18 +1375,18 @@ int comp_rk_step_wave(pyrohip_state *s, const pyrohip_comp_params *p, pyrohip_st
                     kst->d + (size_t)(4 * st) * g.plane, g, P, s->d_flag, part, S);
     }
     PYRO_CHECK_HIP(hipGetLastError());
-    if (!prefilled) fused_copy_frame(s);  // ghost frame of the state -> the new buffer
+    if (!prefilled) state_copy_frame4(s);  // ghost frame of the state -> the new buffer
     s->cfl_is_global = false;
     if (S && nwg <= 128 * kMinStageBlocks) {
         // device-side run: the next policy launch takes the minimum of the partials itself (fused_tail)
         s->pend_part = part;
         s->pend_n = nwg;
-        fused_swap(s);
+        state_swap_alt(s);
         *dmin_out = part + nwg + kMinStageBlocks;
         return 0;
     }
     const double *dmin = launch_min_reduce(c->stream, part, nwg);
-    if (S) { fused_swap(s); *dmin_out = dmin; return 0; }
+    if (S) { state_swap_alt(s); *dmin_out = dmin; return 0; }
     const int rc = fused_sync(s, dmin);   // flag + minimum read back; swap if the state was valid
     if (rc == 0) s->cfl_kind = 1;         // (the minimum is compressible_rk's CFL quantity)
     return rc;

@@ -321,6 +321,14 @@ int state_alt(pyrohip_state *s)
     return 0;
 }
 
+void state_swap_alt(pyrohip_state *s)
+{
+    double *old_base = s->base;
+    s->base = s->alt_base;
+    s->alt_base = old_base;
+    s->d = s->base + geom_lead(s->g);
+}
+
 int evolve_begin(pyrohip_state *s, const pyrohip_dt_policy *pol, double cfl, double dx, double dy,
                  int max_steps, StepScalars *H)
 {

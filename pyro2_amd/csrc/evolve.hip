@@ -64,6 +64,42 @@ __global__ __launch_bounds__(256) void k_fill_frame2(const double *src, double *
     fill_frame2_piece<NV>(src, cur, alt, g, bc, (int)blockIdx.x, (int)threadIdx.x);
 }
 
+// ghost frame of all 4 planes old -> new (the reference updates in place, so
+// ghost cells keep their pre-step values)
+__global__ void k_copy_frame4(const double *__restrict__ src, double *__restrict__ dst, Geom g)
+{
+    // 1-d grid (frame_pieces): the 2 ng full ghost rows in pieces of 256 columns, then the ghost columns of
+    // the interior rows (a 2-d grid whose column part ran in block column 0 only launched
+    // 33 thousand workgroups at 16384^2 for 1024 that had work)
+    const int ng = g.ng;
+    const int nxb = (g.qy + 255) / 256, nrowblk = 2 * ng * nxb;
+    const int b = blockIdx.x;
+    int i, j;
+    if (b < nrowblk) {                              // a piece of a full ghost row
+        const int rr = b / nxb;
+        i = (rr < ng) ? rr : g.ihi + 1 + (rr - ng);
+        j = (b - rr * nxb) * 256 + (int)threadIdx.x;
+        if (j >= g.qy) return;
+    } else {                                        // ghost columns of interior rows
+        const int t = threadIdx.x;                  // 256 threads: 2*ng columns x rows
+        const int rows_per_block = 256 / (2 * ng);
+        const int r = (b - nrowblk) * rows_per_block + t / (2 * ng);
+        const int kx = t % (2 * ng);
+        if (r >= g.nx || t >= rows_per_block * 2 * ng) return;
+        i = g.ilo + r;
+        j = (kx < ng) ? kx : g.jhi + 1 + (kx - ng);
+    }
+    const size_t k = (size_t)i * g.pitch + j;
+#pragma unroll
+    for (int n = 0; n < 4; n++) dst[n * g.plane + k] = src[n * g.plane + k];
+}
+void pyro::state_copy_frame4(pyrohip_state *s)
+{
+    const Geom &g = s->g;
+    hipLaunchKernelGGL(k_copy_frame4, dim3(frame_pieces(g)), dim3(256), 0, s->ctx->stream,
+                       (const double *)s->d, s->alt_base + geom_lead(g), g);
+}
+
 constexpr int kPolicyThreads = 1024;
 // The driver's compute_timestep (simulation_null.py:222-244) between two steps of a run that
 // advances on the device (dt_policy_apply, common.h), from the CFL minimum the previous step
@@ -306,12 +342,7 @@ int evolve_close(EvolveRun &r, pyrohip_dt_policy *pol, int *steps_done, double *
     const bool invalid = (*(int *)(hb + sizeof(StepScalars)) & 1) || H.dead;
     const double lastmin = *(double *)(hb + sizeof(StepScalars) + 8);
     // max_steps swaps were made; the last state that advanced sits H.steps swaps from the start
-    if ((max_steps - H.steps) % 2) {
-        double *old_base = s->base;
-        s->base = s->alt_base;
-        s->alt_base = old_base;
-        s->d = s->base + geom_lead(g);
-    }
+    if ((max_steps - H.steps) % 2) state_swap_alt(s);
     // the set: one exchange of its two buffers per step that advanced (a failing advance stored
     // nothing in the live one)
     const bool part_error = *perr != 0;

@@ -68,7 +68,6 @@ __device__ __forceinline__ bool odd_sides(unsigned m)
 }
 
 // host side, defined in comp_fused.hip
-__global__ void k_copy_frame4(const double *__restrict__ src, double *__restrict__ dst, Geom g);
 int fused_prepare(pyrohip_state *s, const pyrohip_comp_params *p, double dt, FP &P, double *&Uin,
                   double *&Uout, bool reset_flag = true, bool second_buffer = true);
 // after the step kernel(s): ghost frame, minimum of the CFL partials (all-reduced over
@@ -77,10 +76,6 @@ int fused_tail(pyrohip_state *s, double *part, int nparts, bool frame_copied, co
                bool defer = false);
 // single-step API: read the minimum and the positivity flag back, swap the buffers
 int fused_sync(pyrohip_state *s, const double *dmin);
-// device-side run: swap the buffers without looking (the kernels freeze the state
-// themselves once the flag is up)
-void fused_swap(pyrohip_state *s);
-void fused_copy_frame(pyrohip_state *s);
 
 __device__ __forceinline__ ConsN to_nf(const Cons &U, bool x)
 {
@@ -131,37 +126,13 @@ __device__ __forceinline__ double slope_shared(double l2m, double l20, double l2
 }
 
 #if PYRO_FAST
-// Contracted build, row-marching kernel (round 6): the MC-limited slopes as HALF slopes in signed
-// min / max form -- no sign copy, no product of the one-sided differences, no compare + selects.
-// With lo = min(dl, dr), hi = max(dl, dr), a = max(lo, 0), b = min(hi, 0):
-//     limit2 / 2 = max(min((ap - am) / 4, a), b)
-// (both differences positive: b = 0 and min(dc / 2, lo) > 0; both negative: a = 0, min(dc / 2, 0) =
-// dc / 2 and max(dc / 2, hi); of opposite signs or one of them zero: a = b = 0 and the result is 0),
-// and the same with the fourth-order centred slope of limit4 in place of (ap - am) / 4 -- stencil.h
-// (mc_select_l4) shows that where dl dr > 0 it shares their sign.  Scaling by the power of two is
-// exact: 2 x the result equals limit2 / limit4 of stencil.h up to the rounding of the centred
-// difference's factors ((2/3) x vs 2 (1/3) x).  12 + 7 -> 10 + 5 instructions per variable and direction.
-__device__ __forceinline__ void half_clip(double dl, double dr, double &a, double &b)
-{
-    a = fmax(fmin(dl, dr), 0.0);
-    b = fmin(fmax(dl, dr), 0.0);
-}
-__device__ __forceinline__ double half_limit2(double am, double a0, double ap)
-{
-    double a, b;
-    half_clip(ap - a0, a0 - am, a, b);
-    return fmax(fmin(0.25 * (ap - am), a), b);
-}
-// half of slope_shared(): h2m / h20 / h2p = half_limit2 of the lower neighbour, the cell, the upper one
+// half of slope_shared() (stencil.h: the half slopes): h2m / h20 / h2p = half_limit2 of the lower neighbour, the cell, the upper one
 __device__ __forceinline__ double half_slope_shared(double h2m, double h20, double h2p, double am1,
                                                     double a0, double ap1, int limiter)
 {
     if (limiter == 0) return 0.25 * (ap1 - am1);
     if (limiter == 1) return h20;
-    double a, b;
-    half_clip(ap1 - a0, a0 - am1, a, b);
-    const double hc = (1. / 3.) * (ap1 - am1 - 0.5 * (h2p + h2m));
-    return fmax(fmin(hc, a), b);
+    return half_limit4_from(h2m, h2p, am1, a0, ap1);
 }
 #endif
 

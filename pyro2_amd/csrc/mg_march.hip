@@ -26,25 +26,11 @@
 // the boundary selects (the selects would be a third of its instructions).
 #include "mg_march.h"
 #include "stencil.h"
+#include "wave_march.h"
 #include <type_traits>
 
 namespace pyro {
 namespace {
-
-#if !defined(PYRO_EMU)
-template <int CTRL> __device__ __forceinline__ double mgm_dpp(double v)
-{
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xf, 0xf, true);
-    hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double from_lower(double v) { return mgm_dpp<0x13C>(v); }   // wave_ror:1
-__device__ __forceinline__ double from_upper(double v) { return mgm_dpp<0x134>(v); }   // wave_rol:1
-#else
-__device__ __forceinline__ double from_lower(double v) { return __shfl_up(v, 1, 64); }
-__device__ __forceinline__ double from_upper(double v) { return __shfl_down(v, 1, 64); }
-#endif
 
 // a / b with rb = RN(1 / b): the correctly rounded quotient (multigrid.hip: div_by)
 __device__ __forceinline__ double quot(double a, double b, double rb)
@@ -259,7 +245,7 @@ __device__ __forceinline__ void mgm_march(const MGMarch &A, const Part &P, doubl
                 }
                 // k_mg_prolong_add's expression for fine cell (fi, fj) = (row - 1, column - 1):
                 // (q0 -+ 0.25 m_x) -+ 0.25 m_y, + for odd fi / fj; 0.25 (0.5 d) == 0.125 d
-                const double west = from_lower(cw[1][0]), east = from_upper(cw[1][1]);
+                const double west = lane_from_lower(cw[1][0]), east = lane_from_upper(cw[1][1]);
 #pragma unroll
                 for (int q = 0; q < 2; q++) {
                     const double tx = 0.125 * (cw[2][q] - cw[0][q]);
@@ -285,7 +271,7 @@ __device__ __forceinline__ void mgm_march(const MGMarch &A, const Part &P, doubl
             const double me = v[SR][Q];
             const double up = v[SU][Q], dn = v[SD][Q];
             const double own = v[SR][Q ^ 1];
-            const double oth = Q ? from_upper(v[SR][0]) : from_lower(v[SR][1]);
+            const double oth = Q ? lane_from_upper(v[SR][0]) : lane_from_lower(v[SR][1]);
             const double e = Q ? oth : own, w = Q ? own : oth;
             double sj, si;                       // e + w, up + dn with the ghost cells' values
             if (!EDGEJ) sj = e + w;
@@ -337,7 +323,7 @@ __device__ __forceinline__ void mgm_march(const MGMarch &A, const Part &P, doubl
             const int gi = g0 + k - NP - 1;
             if (gi >= P.ra && gi <= P.rb) {
                 const bool bot = EDGEI && !per_i && gi == 1, top = EDGEI && !per_i && gi == n;
-                const double fromW = from_lower(v[SB][1]), fromE = from_upper(v[SB][0]);
+                const double fromW = lane_from_lower(v[SB][1]), fromE = lane_from_upper(v[SB][0]);
                 double rr[2];
 #pragma unroll
                 for (int q = 0; q < 2; q++) {
@@ -358,7 +344,7 @@ __device__ __forceinline__ void mgm_march(const MGMarch &A, const Part &P, doubl
                     // k_mg_restrict's order (r00 + r10 + r01 + r11)
                     if constexpr ((U + 1) & 1) { rodd[0] = rr[0]; rodd[1] = rr[1]; }   // gi is odd
                     else {
-                        const double r01 = from_upper(rodd[0]), r11 = from_upper(rr[0]);
+                        const double r01 = lane_from_upper(rodd[0]), r11 = lane_from_upper(rr[0]);
                         const double c = 0.25 * (rodd[1] + rr[1] + r01 + r11);
                         if (st[1])
                             A.cf[(unsigned)(gi >> 1) * (unsigned)A.cfpitch + (unsigned)((gj0 >> 1) + ln + 1)] = c;

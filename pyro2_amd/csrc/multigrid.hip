@@ -28,6 +28,7 @@
 #include "mg_march.h"
 #include "reduce.h"
 #include "stencil.h"
+#include "wave_march.h"
 #include <cmath>
 #include <type_traits>
 
@@ -601,22 +602,7 @@ __global__ __launch_bounds__(NT, LPC ? 8 : 1) void k_mg_smooth_tile(MGTile A)
 // only carries the two band-edge rows to the neighbouring waves: 2 reads + 2 writes
 // per pass and thread instead of 20 + 4.
 // ---------------------------------------------------------------------------
-#if !defined(PYRO_EMU)
-template <int CTRL> __device__ __forceinline__ double mgb_dpp(double v)
-{
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xf, 0xf, true);
-    hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double mgb_from_lower(double v) { return mgb_dpp<0x13C>(v); }   // wave_ror:1
-__device__ __forceinline__ double mgb_from_upper(double v) { return mgb_dpp<0x134>(v); }   // wave_rol:1
-#define MGB_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
-#else
-#define MGB_SCHED_FENCE() ((void)0)
-__device__ __forceinline__ double mgb_from_lower(double v) { return __shfl_up(v, 1, 64); }
-__device__ __forceinline__ double mgb_from_upper(double v) { return __shfl_down(v, 1, 64); }
-#endif
+// (the lane moves and the scheduling fence: wave_march.h)
 
 // Ghost cells are not kept at all: a cell next to a physical boundary takes
 // ghost_h(its own value) where the stencil asks for the ghost cell -- what the
@@ -708,7 +694,7 @@ __global__ __launch_bounds__(64 * (MGW_RI / R), (PROL || R == 8) ? 4 : 8) void k
                 v[m][q] = A.vin_zero ? 0.0 : x;
                 f[m][q] = POW2 ? y * A.rdenom : y;                // exact: see mg_pow2
             }
-        MGB_SCHED_FENCE();
+        PYRO_SCHED_FENCE();
     }
     if (PROL) {
         // k_mg_prolong_add's expression for the thread's R x 2 fine cells.  They lie over 2-3
@@ -829,7 +815,7 @@ __global__ __launch_bounds__(64 * (MGW_RI / R), (PROL || R == 8) ? 4 : 8) void k
             double dn = (m > 0) ? v[m > 0 ? m - 1 : 0][q] : below;     // row r - 1
             // the thread's other cell and the neighbouring lane's
             const double own = v[m][q ^ 1];
-            const double oth = q ? mgb_from_upper(v[m][0]) : mgb_from_lower(v[m][1]);
+            const double oth = q ? lane_from_upper(v[m][0]) : lane_from_lower(v[m][1]);
             double e = q ? oth : own, w = q ? own : oth;               // columns c + 1, c - 1
             if (EDGE == 2) {
                 up = isTop[m] ? ghost_h(c1, me) : up;
@@ -848,7 +834,7 @@ __global__ __launch_bounds__(64 * (MGW_RI / R), (PROL || R == 8) ? 4 : 8) void k
                 v[m][q] = fma(A.ky, sj, fma(A.kx, si, f[m][q]));
             else
                 v[m][q] = div_by(f[m][q] + A.xc * si + A.yc * sj, A.denom, A.rdenom);
-            if (m % 4 == 3) MGB_SCHED_FENCE();             // four rows interleaved, not R (VGPR budget)
+            if (m % 4 == 3) PYRO_SCHED_FENCE();             // four rows interleaved, not R (VGPR budget)
         }
         V[(PAR & 1) ? w01 : w00] = v[0][PAR & 1];
         V[((PAR + R - 1) & 1) ? w31 : w30] = v[R - 1][(PAR + R - 1) & 1];
@@ -1096,8 +1082,8 @@ __device__ __forceinline__ void mgc_sweeps_lean(double *V, const double *F, int 
 // whole-wave DPP rotation, the edge rows through LDS (E), ghost values as +-(own value) in one
 // fma (mirror sides; a side with value-0 ghosts takes mgc_sweeps_lean).
 #if !defined(PYRO_EMU)
-__device__ __forceinline__ double mgc_rot_from_lower(double v) { return mgb_from_lower(v); }   // lane 0 <- 63
-__device__ __forceinline__ double mgc_rot_from_upper(double v) { return mgb_from_upper(v); }
+__device__ __forceinline__ double mgc_rot_from_lower(double v) { return lane_from_lower(v); }   // lane 0 <- 63
+__device__ __forceinline__ double mgc_rot_from_upper(double v) { return lane_from_upper(v); }
 #else
 __device__ __forceinline__ double mgc_rot_from_lower(double v) { return __shfl(v, (int)((threadIdx.x + 63) & 63), 64); }
 __device__ __forceinline__ double mgc_rot_from_upper(double v) { return __shfl(v, (int)((threadIdx.x + 1) & 63), 64); }
@@ -1391,7 +1377,7 @@ template <int S> __device__ __forceinline__ double mgw_from_lower(double v, int 
 #if defined(PYRO_EMU)
     else return __shfl(v, (ln & ~15) | ((ln - S) & 15), 64);
 #else
-    else return mgb_dpp<0x120 + S>(v);          // row_ror:S
+    else return lane_dpp<0x120 + S>(v);          // row_ror:S
 #endif
 }
 template <int S> __device__ __forceinline__ double mgw_from_upper(double v, int ln)
@@ -1400,7 +1386,7 @@ template <int S> __device__ __forceinline__ double mgw_from_upper(double v, int 
 #if defined(PYRO_EMU)
     else return __shfl(v, (ln & ~15) | ((ln + S) & 15), 64);
 #else
-    else return mgb_dpp<0x120 + 16 - S>(v);     // row_ror:(16 - S)
+    else return lane_dpp<0x120 + 16 - S>(v);     // row_ror:(16 - S)
 #endif
 }
 

@@ -75,6 +75,35 @@ __device__ __forceinline__ double limit4_from(double l2m, double l2p, double am1
     return mc_select_l4(dc, ap1 - a0, a0 - am1);
 }
 
+// Contracted builds of the row-marching kernels (round 6): the MC-limited slopes as HALF slopes in signed
+// min / max form -- no sign copy, no product of the one-sided differences, no compare + selects.
+// With lo = min(dl, dr), hi = max(dl, dr), a = max(lo, 0), b = min(hi, 0):
+//     limit2 / 2 = max(min((ap - am) / 4, a), b)
+// (both differences positive: b = 0 and min(dc / 2, lo) > 0; both negative: a = 0, min(dc / 2, 0) =
+// dc / 2 and max(dc / 2, hi); of opposite signs or one of them zero: a = b = 0 and the result is 0),
+// and the same with the fourth-order centred slope of limit4 in place of (ap - am) / 4 -- mc_select_l4
+// above shows that where dl dr > 0 it shares their sign.  Scaling by the power of two is
+// exact: 2 x the result equals limit2 / limit4 up to the rounding of the centred
+// difference's factors ((2/3) x vs 2 (1/3) x).  12 + 7 -> 10 + 5 instructions per variable and direction.
+__device__ __forceinline__ void half_clip(double dl, double dr, double &a, double &b)
+{
+    a = fmax(fmin(dl, dr), 0.0);
+    b = fmin(fmax(dl, dr), 0.0);
+}
+__device__ __forceinline__ double half_limit2(double am, double a0, double ap)
+{
+    double a, b;
+    half_clip(ap - a0, a0 - am, a, b);
+    return fmax(fmin(0.25 * (ap - am), a), b);
+}
+// half of limit4_from(): h2m / h2p = half_limit2 of the lower neighbour, the upper one
+__device__ __forceinline__ double half_limit4_from(double h2m, double h2p, double am1, double a0, double ap1)
+{
+    double a, b;
+    half_clip(ap1 - a0, a0 - am1, a, b);
+    return fmax(fmin((1. / 3.) * (ap1 - am1 - 0.5 * (h2p + h2m)), a), b);
+}
+
 // blockIdx -> logical tile id such that each XCD (blocks are dealt round-robin
 // to the 8 XCDs, MI355X_MICROARCH.md "block b runs on XCD b % 8") works on a
 // contiguous band of tiles and halo re-reads hit its own L2.  Performance

@@ -28,6 +28,7 @@
 #include "hydro.h"     // pdiv / psqrt: the IEEE quotient / root without the expansion's scaling (bit-identical)
 #include "reduce.h"
 #include "stencil.h"
+#include "wave_march.h"
 
 namespace pyro {
 namespace PYRO_SWNS {
@@ -126,7 +127,7 @@ __device__ __forceinline__ void sw_trace(const double q[4], const double dq[4], 
     lo[0] += br2 * q[0]; lo[in] += br2 * cs; lo[it] += br1 * dq[it]; lo[3] += br1 * dq[3];
 }
 // the same from HALF slopes hq = dq / 2 (round 6, the one-launch kernel: the limited slopes in the
-// signed min / max form of half_limit2 below): the factors 1/2 of the projections and of the
+// signed min / max form of stencil.h's half_limit2): the factors 1/2 of the projections and of the
 // reference states disappear into hq, the 2 of (sign + 1) into the wave factors
 __device__ __forceinline__ void sw_trace_h(const double q[4], const double hq[4], double g,
                                            double dtdx, bool x, double lo[4], double hi[4])
@@ -151,25 +152,6 @@ __device__ __forceinline__ void sw_trace_h(const double q[4], const double hq[4]
     const double br1 = -dtdx3 * cs * (4.0 - pl1);
     hi[0] += bl0 * q[0]; hi[in] -= bl0 * cs; hi[it] += bl1 * hq[it]; hi[3] += bl1 * hq[3];
     lo[0] += br2 * q[0]; lo[in] += br2 * cs; lo[it] += br1 * hq[it]; lo[3] += br1 * hq[3];
-}
-// MC-limited slopes as half slopes (the compressible kernel's: fused_common.h half_limit2 /
-// half_slope_shared -- signed min / max, no sign copy, product, compare or select)
-__device__ __forceinline__ void sw_half_clip(double dl, double dr, double &a, double &b)
-{
-    a = fmax(fmin(dl, dr), 0.0);
-    b = fmin(fmax(dl, dr), 0.0);
-}
-__device__ __forceinline__ double sw_half_limit2(double am, double a0, double ap)
-{
-    double a, b;
-    sw_half_clip(ap - a0, a0 - am, a, b);
-    return fmax(fmin(0.25 * (ap - am), a), b);
-}
-__device__ __forceinline__ double sw_half_limit4_from(double h2m, double h2p, double am1, double a0, double ap1)
-{
-    double a, b;
-    sw_half_clip(ap1 - a0, a0 - am1, a, b);
-    return fmax(fmin((1. / 3.) * (ap1 - am1 - 0.5 * (h2p + h2m)), a), b);
 }
 #else
 __device__ __forceinline__ void sw_trace(const double q[4], const double dq[4], double g,
@@ -531,39 +513,21 @@ __global__ __launch_bounds__(256) void k_sw_cfl(const double *__restrict__ U, Ge
 // doubles per cell.  The new time level goes to the state's second buffer (neighbouring
 // chunks still read the old one); the ghost frame is carried over.
 constexpr int SWW_OUT = 58, SWW_REACH = 3;
-// stage boundary: the scheduler may not move instructions across it (left alone it
-// interleaves the four Riemann problems of an iteration for ILP and spills: comp_wave.hip)
-#if defined(PYRO_EMU)
-#define SWW_FENCE() do {} while (0)
-#else
-#define SWW_FENCE() __builtin_amdgcn_sched_barrier(0)
-#endif
 struct SWW {
     double dx, dy, dt, g;
     int limiter;
     int ncb, L, nunits;
     int prio_duty;      // eighths of the time the second wavefront of a SIMD holds the priority (0: age decides)
-    int nsb, n_extra;   // row strips; column strips [0, n_extra) are cut into nsb + 1 (common.h: wave_fill_extra)
-    int *prio_board;    // rows-left board of the SIMD pairs (comp_wave.hip; nullptr: turns by prio_duty) and the launch's tag
+    int nsb, n_extra;   // row strips; column strips [0, n_extra) are cut into nsb + 1 (wave_march.h: wave_fill_extra)
+    int *prio_board;    // rows-left board of the SIMD pairs (wave_march.h; nullptr: turns by prio_duty) and the launch's tag
     int prio_tag;
 };
 
-#if !defined(PYRO_EMU)
-template <int CTRL> __device__ __forceinline__ double sww_dpp(double v)
-{
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xf, 0xf, true);
-    hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double sww_m1(double v) { return sww_dpp<0x13C>(v); }   // wave_ror:1
-__device__ __forceinline__ double sww_p1(double v) { return sww_dpp<0x134>(v); }   // wave_rol:1
-#else
-__device__ __forceinline__ double sww_m1(double v) { return __shfl_up(v, 1, 64); }
-__device__ __forceinline__ double sww_p1(double v) { return __shfl_down(v, 1, 64); }
-#endif
-__device__ __forceinline__ V4 sww_m1(const V4 &v) { return V4{{sww_m1(v.a[0]), sww_m1(v.a[1]), sww_m1(v.a[2]), sww_m1(v.a[3])}}; }
-__device__ __forceinline__ V4 sww_p1(const V4 &v) { return V4{{sww_p1(v.a[0]), sww_p1(v.a[1]), sww_p1(v.a[2]), sww_p1(v.a[3])}}; }
+// lane l-1 / l+1 (wave_march.h) of a 4-vector
+using pyro::lane_from_lower;
+using pyro::lane_from_upper;
+__device__ __forceinline__ V4 lane_from_lower(const V4 &v) { return V4{{lane_from_lower(v.a[0]), lane_from_lower(v.a[1]), lane_from_lower(v.a[2]), lane_from_lower(v.a[3])}}; }
+__device__ __forceinline__ V4 lane_from_upper(const V4 &v) { return V4{{lane_from_upper(v.a[0]), lane_from_upper(v.a[1]), lane_from_upper(v.a[2]), lane_from_upper(v.a[3])}}; }
 
 template <int RS>
 __device__ __forceinline__ V4 sww_riemann(const V4 &Ul, const V4 &Ur, double g, bool x, double sg)
@@ -585,8 +549,8 @@ __device__ __forceinline__ V4 sww_riemann(const V4 &Ul, const V4 &Ur, double g, 
 // fetched from the neighbouring lanes -- instead of twice per direction (round 6: 8 of the 16
 // limit2 evaluations per cell and row, and the two-cells-away DPP moves; bit-identical).
 #if PYRO_FAST
-#define SW_LIMIT2 sw_half_limit2
-#define SW_LIMIT4_FROM sw_half_limit4_from
+#define SW_LIMIT2 half_limit2
+#define SW_LIMIT4_FROM half_limit4_from
 #else
 #define SW_LIMIT2 limit2
 #define SW_LIMIT4_FROM limit4_from
@@ -615,8 +579,8 @@ __global__ __launch_bounds__(64, 2) void k_sw_wave(const double *__restrict__ Ui
     int i0 = g.ilo + sb * P.L;                              // rows [i0, i1)
     int i1 = (i0 + P.L < g.ihi + 1) ? i0 + P.L : g.ihi + 1;
     if (cb < P.n_extra) {      // nsb + 1 strips of equal length (to a row)
-        i0 = g.ilo + (int)((long)sb * g.nx / (P.nsb + 1));
-        i1 = g.ilo + (int)((long)(sb + 1) * g.nx / (P.nsb + 1));
+        i0 = wave_extra_row(sb, P.nsb, g.nx, g.ilo);
+        i1 = wave_extra_row(sb + 1, P.nsb, g.nx, g.ilo);
     }
     const int j = g.jlo - SWW_REACH + cb * SWW_OUT + l;
     const int jc = j < 0 ? 0 : (j < g.qy ? j : g.qy - 1);
@@ -686,44 +650,11 @@ __global__ __launch_bounds__(64, 2) void k_sw_wave(const double *__restrict__ Ui
 #endif
     };
     double l2a[4] = {0.0, 0.0, 0.0, 0.0}, l2b[4] = {0.0, 0.0, 0.0, 0.0};   // L4: limit2 along x centred on rows k-3, k-2
-#if !defined(PYRO_EMU)
-    unsigned hw_id;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw_id));
-    const int wslot = (int)(hw_id & 1u);
-    // (comp_wave.hip: the two wavefronts of a SIMD tell each other their rows left, the one behind takes the priority)
-    const bool prio_fb = P.prio_board != nullptr;
-    int *prio_mine = nullptr, *prio_other = nullptr;
-    int prio_seen = 0;
-    if (prio_fb) {
-        unsigned xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        int *const pair = P.prio_board + 2 * (int)(((xcc & 15u) << 12) | ((hw_id >> 4) & 0xfffu));
-        prio_mine = pair + wslot;
-        prio_other = pair + (wslot ^ 1);
-    }
-    auto prio_publish = [&](int k) {      // (behind the request of the next row)
-        if (!prio_fb) return;
-        __hip_atomic_store(prio_mine, (P.prio_tag << 16) | (i1 + 2 - k), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        prio_seen = __hip_atomic_load(prio_other, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    };
-#else
-    auto prio_publish = [](int) {};
-#endif
+    // the two wavefronts of a SIMD take turns at the priority (wave_march.h): by the pair's rows-left board where the
+    // launch has one -- the one behind takes it --, by phase and duty otherwise
+    WavePrio prio = wave_prio_begin(P.prio_board, P.prio_tag, true);
     for (int k = i0 - 3; k <= i1 + 2; k++) {
-#if !defined(PYRO_EMU)
-        if (prio_fb) {
-            const int seen = __builtin_amdgcn_readfirstlane(prio_seen);
-            const int left = i1 + 2 - k;
-            const int other_left = ((seen >> 16) == P.prio_tag) ? (seen & 0xffff) : left;
-            if (left > other_left) __builtin_amdgcn_s_setprio(1);
-            else if (left < other_left) __builtin_amdgcn_s_setprio(0);
-        } else
-        if (P.prio_duty > 0) {     // the two wavefronts of a SIMD take turns at the priority (comp_wave.hip)
-            const int phase = ((k - i0) >> 1) & 7;
-            if (wslot ? (phase < P.prio_duty) : (phase >= P.prio_duty)) __builtin_amdgcn_s_setprio(1);
-            else __builtin_amdgcn_s_setprio(0);
-        }
-#endif
+        wave_prio_turn(prio, k, i0, i1 + 2, P.prio_duty);
         // ---- row k arrives: primitives (k_sw_prim)
 #pragma unroll
         for (int r = 0; r < 4; r++) {
@@ -735,7 +666,7 @@ __global__ __launch_bounds__(64, 2) void k_sw_wave(const double *__restrict__ Ui
         if (!SWW_DELAY) {
         Upre = loadU(k + 1);
         Urep = loadU(k - 2);
-        prio_publish(k);
+        wave_prio_publish(prio, i1 + 2 - k);
         }
         q[4][0] = Uk.a[0];
         q[4][1] = sw_vel(Uk.a[1], Uk.a[0]);
@@ -745,12 +676,12 @@ __global__ __launch_bounds__(64, 2) void k_sw_wave(const double *__restrict__ Ui
 #if !defined(PYRO_EMU)
             asm volatile("" : "+v"(q[4][0]), "+v"(q[4][1]), "+v"(q[4][2]), "+v"(q[4][3]));   // (the arrived row is consumed HERE)
 #endif
-            SWW_FENCE();
+            PYRO_SCHED_FENCE();
             if (k - 1 - 2 >= i0 + 1 && jout) store_row(Upend, k - 4);      // the update iteration k-1 made (row c-1 = k-4)
             Uold = loadU(k - 3);                 // (in front of the next row's request: its wait leaves that one out)
             Upre = loadU(k + 1);
-            prio_publish(k);
-            SWW_FENCE();
+            wave_prio_publish(prio, i1 + 2 - k);
+            PYRO_SCHED_FENCE();
         }
         const int c = k - 2;                 // window row 2
         double l2n[4], l2m_[4];              // L4: limit2 along x centred on row k-1 = c+1, on row c-1
@@ -767,15 +698,15 @@ __global__ __launch_bounds__(64, 2) void k_sw_wave(const double *__restrict__ Ui
 #pragma unroll
         for (int n = 0; n < 4; n++) {
             qc[n] = q[2][n];
-            const double m1 = sww_m1(qc[n]), p1 = sww_p1(qc[n]);
+            const double m1 = lane_from_lower(qc[n]), p1 = lane_from_upper(qc[n]);
             if (L4) {
                 // (contracted build: half slopes, traced by sw_trace_h)
                 dqx[n] = 1.0 * SW_LIMIT4_FROM(l2m_[n], l2n[n], q[1][n], q[2][n], q[3][n]);
                 const double l2y = SW_LIMIT2(m1, qc[n], p1);
-                dqy[n] = 1.0 * SW_LIMIT4_FROM(sww_m1(l2y), sww_p1(l2y), m1, qc[n], p1);
+                dqy[n] = 1.0 * SW_LIMIT4_FROM(lane_from_lower(l2y), lane_from_upper(l2y), m1, qc[n], p1);
             } else {
                 dqx[n] = 1.0 * limited_slope(q[0][n], q[1][n], q[2][n], q[3][n], q[4][n], P.limiter);
-                dqy[n] = 1.0 * limited_slope(sww_m1(m1), m1, qc[n], p1, sww_p1(p1), P.limiter);
+                dqy[n] = 1.0 * limited_slope(lane_from_lower(m1), m1, qc[n], p1, lane_from_upper(p1), P.limiter);
             }
         }
         double lo[4], hi[4];
@@ -789,28 +720,28 @@ __global__ __launch_bounds__(64, 2) void k_sw_wave(const double *__restrict__ Ui
 #endif
         sw_trace(qc, dqy, P.g, P.dt / P.dy, false, lo, hi);
         const V4 YM = sw_prim_to_cons(lo), YP = sw_prim_to_cons(hi);
-        SWW_FENCE();
+        PYRO_SCHED_FENCE();
         // ---- transverse Riemann problems on the lower faces of row c (k_sw_riemann_t)
         const V4 XPm = get(S_XP);
         const V4 FXT = sww_riemann<RS>(XPm, XM, P.g, true, sg);
-        SWW_FENCE();
-        const V4 FYT = sww_riemann<RS>(sww_m1(YP), YM, P.g, false, sg);
-        const V4 FYT_p = sww_p1(FYT);
-        SWW_FENCE();
+        PYRO_SCHED_FENCE();
+        const V4 FYT = sww_riemann<RS>(lane_from_lower(YP), YM, P.g, false, sg);
+        const V4 FYT_p = lane_from_upper(FYT);
+        PYRO_SCHED_FENCE();
         if (c >= i0) {
             // ---- final x flux on the lower face of row c (k_sw_final)
             const V4 FYTm = get(S_FYT);
-            const V4 Uxl = sw_corrected(XPm, sww_p1(FYTm), FYTm, hdtdy);
+            const V4 Uxl = sw_corrected(XPm, lane_from_upper(FYTm), FYTm, hdtdy);
             const V4 Uxr = sw_corrected(XM, FYT_p, FYT, hdtdy);
             const V4 Fx = sww_riemann<RS>(Uxl, Uxr, P.g, true, sg);
-            SWW_FENCE();
+            PYRO_SCHED_FENCE();
             if (c >= i0 + 1) {
                 // ---- row r = c-1: final y flux, conservative update (k_sw_final, k_sw_update)
                 const V4 FXTm = get(S_FXT);
-                const V4 Uyl = sww_m1(sw_corrected(get(S_YP), FXT, FXTm, hdtdx));
+                const V4 Uyl = lane_from_lower(sw_corrected(get(S_YP), FXT, FXTm, hdtdx));
                 const V4 Uyr = sw_corrected(get(S_YM), FXT, FXTm, hdtdx);
                 const V4 Fy = sww_riemann<RS>(Uyl, Uyr, P.g, false, sg);
-                const V4 Fy_p = sww_p1(Fy);
+                const V4 Fy_p = lane_from_upper(Fy);
                 const V4 Fxm = get(S_FX);
                 if (jout) {
                     V4 Un;
@@ -842,7 +773,7 @@ __global__ __launch_bounds__(64, 2) void k_sw_wave(const double *__restrict__ Ui
 
 // rows per chunk of the fused step (a chunk costs L + 6 iterations): whole rounds of resident
 // wavefronts (two per SIMD) + one chunk time for the stragglers of the last round; ONE round when
-// everything is resident at once -- the rule of the compressible kernel (comp_wave.hip: wave_rows).
+// everything is resident at once -- the rule of the compressible kernel (wave_march.h: wave_strip_rows).
 // (Round 5 left the one-round case out: without turns at the priority a single round ends with
 // every SIMD's younger wavefront alone -- 4096^2: one round of 147 rows 1.26 ms, 1.5 rounds of 96
 // rows 1.21.  Round 6, with the turns (sww_prio_duty): 96 rows 0.614 ms, 147 rows 0.620 / 0.581 /
@@ -878,33 +809,6 @@ static SwwGeom sww_geometry(int nx, int ny, int cus)
     return w;
 }
 
-// ghost frame of the four planes from one buffer to the other (1-d grid: 2 ng blocks of
-// columns for the ghost rows, then row blocks for the ghost columns)
-__global__ __launch_bounds__(256) void k_sw_copy_frame(const double *__restrict__ src,
-                                                        double *__restrict__ dst, Geom g)
-{
-    const int ng = g.ng, ncolb = (g.qy + 255) / 256, nrowb = 2 * ng * ncolb;
-    const int b = blockIdx.x;
-    int i, j;
-    if (b < nrowb) {
-        const int gr = b / ncolb;                       // ghost row index 0 .. 2 ng - 1
-        i = gr < ng ? gr : g.ihi + 1 + (gr - ng);
-        j = (b % ncolb) * 256 + (int)threadIdx.x;
-        if (j >= g.qy) return;
-    } else {
-        const int rpb = 256 / (2 * ng);                 // interior rows per block
-        const int t = (int)threadIdx.x;
-        if (t >= rpb * 2 * ng) return;
-        i = g.ilo + (b - nrowb) * rpb + t / (2 * ng);
-        if (i > g.ihi) return;
-        const int gc = t % (2 * ng);
-        j = gc < ng ? gc : g.jhi + 1 + (gc - ng);
-    }
-    const size_t k = (size_t)i * g.pitch + j;
-#pragma unroll
-    for (int n = 0; n < 4; n++) dst[(size_t)n * g.plane + k] = src[(size_t)n * g.plane + k];
-}
-
 // one step by the one-launch kernel: new time level into the second buffer, ghost frame carried
 // over (unless the caller has filled both frames: frame_done), buffers swapped.  S / part: see
 // k_sw_wave; *nparts = wavefronts of the launch
@@ -920,7 +824,7 @@ int swe_step_wave(pyrohip_state *s, double dx, double dy, double grav, int limit
     P.ncb = w.ncb; P.L = w.L; P.nsb = w.nsb; P.n_extra = w.n_extra; P.nunits = w.nunits;
     if (nparts) *nparts = P.nunits;
     // one round of resident wavefronts: the pair of a SIMD ends together -- the one with more rows left
-    // takes the priority (GPU; comp_wave.hip), turns by phase otherwise
+    // takes the priority (GPU; wave_march.h), turns by phase otherwise
     P.prio_duty = (P.nunits <= slots) ? 6 : 0;
 #if !defined(PYRO_EMU)
     if (P.prio_duty > 0) PYRO_TRY(prio_board_acquire(c, &P.prio_board, &P.prio_tag));
@@ -934,14 +838,10 @@ int swe_step_wave(pyrohip_state *s, double dx, double dy, double grav, int limit
                 (const double *)s->d, Uout, g, P, S, part);
     if (!frame_done) {
         // the ghost frame is carried over (the reference updates the interior in place)
-        hipLaunchKernelGGL(k_sw_copy_frame, dim3(frame_pieces(g)), dim3(256), 0, c->stream, (const double *)s->d,
-                           Uout, g);
+        state_copy_frame4(s);
     }
     PYRO_CHECK_HIP(hipGetLastError());
-    double *old_base = s->base;       // the buffers change places
-    s->base = s->alt_base;
-    s->alt_base = old_base;
-    s->d = s->base + geom_lead(g);
+    state_swap_alt(s);
     s->next_cfl_min = -1.0;
     s->ghost_by_rules = false;
     s->stages_valid = false;       // the one-launch kernel keeps no stage planes

@@ -1443,6 +1443,110 @@ def test_bench_rank_geometry_16384(dev):
             assert g["overlap"] == int(g["row_strips"] >= 3 and g["rows_per_strip"] >= ng)
 
 
+# (nx, ny, num_cus, comp_wave_geometry with march_rows 0, with march_rows 16, swe_wave_geometry): each as
+# the tuple of the dict's values in its order, ng = 4 -- recorded on the commit in front of csrc/wave_march.h
+WAVE_GEOMETRY_PINNED = [
+    (8, 64, 0, (2, 8, 1, 0, 2, 2048), (2, 8, 1, 0, 2, 2048), (2, 8, 1, 0, 2, 2048)),
+    (8, 64, 4, (2, 8, 1, 0, 2, 32), (2, 8, 1, 0, 2, 32), (2, 8, 1, 0, 2, 32)),
+    (8, 64, 256, (2, 8, 1, 0, 2, 2048), (2, 8, 1, 0, 2, 2048), (2, 8, 1, 0, 2, 2048)),
+    (8, 4096, 0, (74, 8, 1, 0, 74, 2048), (74, 8, 1, 0, 74, 2048), (71, 8, 1, 0, 71, 2048)),
+    (8, 4096, 4, (74, 8, 1, 0, 74, 32), (74, 8, 1, 0, 74, 32), (71, 8, 1, 0, 71, 32)),
+    (8, 4096, 256, (74, 8, 1, 0, 74, 2048), (74, 8, 1, 0, 74, 2048), (71, 8, 1, 0, 71, 2048)),
+    (31, 64, 0, (2, 31, 1, 0, 2, 2048), (2, 16, 2, 0, 4, 2048), (2, 16, 2, 2, 6, 2048)),
+    (31, 64, 4, (2, 31, 1, 0, 2, 32), (2, 16, 2, 0, 4, 32), (2, 16, 2, 2, 6, 32)),
+    (31, 64, 256, (2, 31, 1, 0, 2, 2048), (2, 16, 2, 0, 4, 2048), (2, 16, 2, 2, 6, 2048)),
+    (31, 4096, 0, (74, 31, 1, 0, 74, 2048), (74, 16, 2, 0, 148, 2048), (71, 16, 2, 71, 213, 2048)),
+    (31, 4096, 4, (74, 31, 1, 0, 74, 32), (74, 16, 2, 0, 148, 32), (71, 16, 2, 0, 142, 32)),
+    (31, 4096, 256, (74, 31, 1, 0, 74, 2048), (74, 16, 2, 0, 148, 2048), (71, 16, 2, 71, 213, 2048)),
+    (32, 64, 0, (2, 32, 1, 0, 2, 2048), (2, 16, 2, 0, 4, 2048), (2, 16, 2, 2, 6, 2048)),
+    (32, 64, 4, (2, 32, 1, 0, 2, 32), (2, 16, 2, 0, 4, 32), (2, 16, 2, 2, 6, 32)),
+    (32, 64, 256, (2, 32, 1, 0, 2, 2048), (2, 16, 2, 0, 4, 2048), (2, 16, 2, 2, 6, 2048)),
+    (32, 4096, 0, (74, 32, 1, 0, 74, 2048), (74, 16, 2, 0, 148, 2048), (71, 16, 2, 71, 213, 2048)),
+    (32, 4096, 4, (74, 32, 1, 0, 74, 32), (74, 16, 2, 0, 148, 32), (71, 16, 2, 0, 142, 32)),
+    (32, 4096, 256, (74, 32, 1, 0, 74, 2048), (74, 16, 2, 0, 148, 2048), (71, 16, 2, 71, 213, 2048)),
+    (33, 64, 0, (2, 8, 4, 1, 8, 2048), (2, 16, 2, 0, 4, 2048), (2, 16, 3, 2, 8, 2048)),
+    (33, 64, 4, (2, 8, 4, 1, 8, 32), (2, 16, 2, 0, 4, 32), (2, 16, 3, 2, 8, 32)),
+    (33, 64, 256, (2, 8, 4, 1, 8, 2048), (2, 16, 2, 0, 4, 2048), (2, 16, 3, 2, 8, 2048)),
+    (33, 4096, 0, (74, 8, 4, 1, 296, 2048), (74, 16, 2, 0, 148, 2048), (71, 16, 3, 71, 284, 2048)),
+    (33, 4096, 4, (74, 15, 2, 0, 148, 32), (74, 16, 2, 0, 148, 32), (71, 17, 2, 0, 142, 32)),
+    (33, 4096, 256, (74, 8, 4, 1, 296, 2048), (74, 16, 2, 0, 148, 2048), (71, 16, 3, 71, 284, 2048)),
+    (64, 64, 0, (2, 8, 8, 1, 16, 2048), (2, 16, 4, 1, 8, 2048), (2, 16, 4, 2, 10, 2048)),
+    (64, 64, 4, (2, 8, 8, 1, 16, 32), (2, 16, 4, 1, 8, 32), (2, 16, 4, 2, 10, 32)),
+    (64, 64, 256, (2, 8, 8, 1, 16, 2048), (2, 16, 4, 1, 8, 2048), (2, 16, 4, 2, 10, 2048)),
+    (64, 4096, 0, (74, 8, 8, 1, 592, 2048), (74, 16, 4, 1, 296, 2048), (71, 16, 4, 71, 355, 2048)),
+    (64, 4096, 4, (74, 21, 3, 1, 222, 32), (74, 16, 4, 1, 296, 32), (71, 16, 4, 0, 284, 32)),
+    (64, 4096, 256, (74, 8, 8, 1, 592, 2048), (74, 16, 4, 1, 296, 2048), (71, 16, 4, 71, 355, 2048)),
+    (100, 64, 0, (2, 8, 13, 1, 26, 2048), (2, 16, 7, 1, 14, 2048), (2, 16, 7, 2, 16, 2048)),
+    (100, 64, 4, (2, 8, 13, 1, 26, 32), (2, 16, 7, 1, 14, 32), (2, 16, 7, 2, 16, 32)),
+    (100, 64, 256, (2, 8, 13, 1, 26, 2048), (2, 16, 7, 1, 14, 2048), (2, 16, 7, 2, 16, 2048)),
+    (100, 4096, 0, (74, 8, 13, 1, 962, 2048), (74, 16, 7, 1, 518, 2048), (71, 16, 7, 71, 568, 2048)),
+    (100, 4096, 4, (74, 33, 3, 1, 222, 32), (74, 16, 7, 1, 518, 32), (71, 25, 4, 0, 284, 32)),
+    (100, 4096, 256, (74, 8, 13, 1, 962, 2048), (74, 16, 7, 1, 518, 2048), (71, 16, 7, 71, 568, 2048)),
+    (257, 64, 0, (2, 8, 32, 1, 64, 2048), (2, 16, 16, 1, 32, 2048), (2, 16, 17, 2, 36, 2048)),
+    (257, 64, 4, (2, 16, 16, 1, 32, 32), (2, 16, 16, 1, 32, 32), (2, 17, 16, 0, 32, 32)),
+    (257, 64, 256, (2, 8, 32, 1, 64, 2048), (2, 16, 16, 1, 32, 2048), (2, 16, 17, 2, 36, 2048)),
+    (257, 4096, 0, (74, 10, 26, 1, 1924, 2048), (74, 16, 16, 1, 1184, 2048), (71, 16, 17, 71, 1278, 2048)),
+    (257, 4096, 4, (74, 85, 3, 1, 222, 32), (74, 16, 16, 1, 1184, 32), (71, 65, 4, 0, 284, 32)),
+    (257, 4096, 256, (74, 10, 26, 1, 1924, 2048), (74, 16, 16, 1, 1184, 2048), (71, 16, 17, 71, 1278, 2048)),
+    (1024, 64, 0, (2, 8, 128, 1, 256, 2048), (2, 16, 64, 1, 128, 2048), (2, 16, 64, 2, 130, 2048)),
+    (1024, 64, 4, (2, 64, 16, 1, 32, 32), (2, 16, 64, 1, 128, 32), (2, 64, 16, 0, 32, 32)),
+    (1024, 64, 256, (2, 8, 128, 1, 256, 2048), (2, 16, 64, 1, 128, 2048), (2, 16, 64, 2, 130, 2048)),
+    (1024, 4096, 0, (74, 38, 27, 1, 1998, 2048), (74, 16, 64, 1, 4736, 2048), (71, 37, 28, 60, 2048, 2048)),
+    (1024, 4096, 4, (74, 114, 9, 1, 666, 32), (74, 16, 64, 1, 4736, 32), (71, 114, 9, 0, 639, 32)),
+    (1024, 4096, 256, (74, 38, 27, 1, 1998, 2048), (74, 16, 64, 1, 4736, 2048), (71, 37, 28, 60, 2048, 2048)),
+    (1792, 64, 0, (2, 8, 224, 1, 448, 2048), (2, 16, 112, 1, 224, 2048), (2, 16, 112, 2, 226, 2048)),
+    (1792, 64, 4, (2, 112, 16, 1, 32, 32), (2, 16, 112, 1, 224, 32), (2, 112, 16, 0, 32, 32)),
+    (1792, 64, 256, (2, 8, 224, 1, 448, 2048), (2, 16, 112, 1, 224, 2048), (2, 16, 112, 2, 226, 2048)),
+    (1792, 4096, 0, (74, 67, 27, 1, 1998, 2048), (74, 16, 112, 1, 8288, 2048), (71, 64, 28, 60, 2048, 2048)),
+    (1792, 4096, 4, (74, 112, 16, 1, 1184, 32), (74, 16, 112, 1, 8288, 32), (71, 138, 13, 0, 923, 32)),
+    (1792, 4096, 256, (74, 67, 27, 1, 1998, 2048), (74, 16, 112, 1, 8288, 2048), (71, 64, 28, 60, 2048, 2048)),
+    (2048, 64, 0, (2, 8, 256, 1, 512, 2048), (2, 16, 128, 1, 256, 2048), (2, 16, 128, 2, 258, 2048)),
+    (2048, 64, 4, (2, 128, 16, 1, 32, 32), (2, 16, 128, 1, 256, 32), (2, 128, 16, 0, 32, 32)),
+    (2048, 64, 256, (2, 8, 256, 1, 512, 2048), (2, 16, 128, 1, 256, 2048), (2, 16, 128, 2, 258, 2048)),
+    (2048, 4096, 0, (74, 76, 27, 1, 1998, 2048), (74, 16, 128, 1, 9472, 2048), (71, 74, 28, 60, 2048, 2048)),
+    (2048, 4096, 4, (74, 128, 16, 1, 1184, 32), (74, 16, 128, 1, 9472, 32), (71, 114, 18, 0, 1278, 32)),
+    (2048, 4096, 256, (74, 76, 27, 1, 1998, 2048), (74, 16, 128, 1, 9472, 2048), (71, 74, 28, 60, 2048, 2048)),
+    (3072, 64, 0, (2, 8, 384, 1, 768, 2048), (2, 16, 192, 1, 384, 2048), (2, 16, 192, 2, 386, 2048)),
+    (3072, 64, 4, (2, 32, 96, 1, 192, 32), (2, 16, 192, 1, 384, 32), (2, 32, 96, 0, 192, 32)),
+    (3072, 64, 256, (2, 8, 384, 1, 768, 2048), (2, 16, 192, 1, 384, 2048), (2, 16, 192, 2, 386, 2048)),
+    (3072, 4096, 0, (74, 114, 27, 1, 1998, 2048), (74, 16, 192, 1, 14208, 2048), (71, 110, 28, 60, 2048, 2048)),
+    (3072, 4096, 4, (74, 140, 22, 1, 1628, 32), (74, 16, 192, 1, 14208, 32), (71, 140, 22, 0, 1562, 32)),
+    (3072, 4096, 256, (74, 114, 27, 1, 1998, 2048), (74, 16, 192, 1, 14208, 2048), (71, 110, 28, 60, 2048, 2048)),
+    (4096, 64, 0, (2, 8, 512, 1, 1024, 2048), (2, 16, 256, 1, 512, 2048), (2, 16, 256, 2, 514, 2048)),
+    (4096, 64, 4, (2, 43, 96, 1, 192, 32), (2, 16, 256, 1, 512, 32), (2, 32, 128, 0, 256, 32)),
+    (4096, 64, 256, (2, 8, 512, 1, 1024, 2048), (2, 16, 256, 1, 512, 2048), (2, 16, 256, 2, 514, 2048)),
+    (4096, 4096, 0, (74, 152, 27, 1, 1998, 2048), (74, 16, 256, 1, 18944, 2048), (71, 147, 28, 60, 2048, 2048)),
+    (4096, 4096, 4, (74, 128, 32, 1, 2368, 32), (74, 16, 256, 1, 18944, 32), (71, 152, 27, 0, 1917, 32)),
+    (4096, 4096, 256, (74, 152, 27, 1, 1998, 2048), (74, 16, 256, 1, 18944, 2048), (71, 147, 28, 60, 2048, 2048)),
+    (8192, 64, 0, (2, 8, 1024, 1, 2048, 2048), (2, 16, 512, 1, 1024, 2048), (2, 16, 512, 2, 1026, 2048)),
+    (8192, 64, 4, (2, 64, 128, 1, 256, 32), (2, 16, 512, 1, 1024, 32), (2, 57, 144, 0, 288, 32)),
+    (8192, 64, 256, (2, 8, 1024, 1, 2048, 2048), (2, 16, 512, 1, 1024, 2048), (2, 16, 512, 2, 1026, 2048)),
+    (8192, 4096, 0, (74, 50, 164, 1, 12136, 2048), (74, 16, 512, 1, 37888, 2048), (71, 41, 200, 0, 14200, 2048)),
+    (8192, 4096, 4, (74, 152, 54, 1, 3996, 32), (74, 16, 512, 1, 37888, 32), (71, 152, 54, 0, 3834, 32)),
+    (8192, 4096, 256, (74, 50, 164, 1, 12136, 2048), (74, 16, 512, 1, 37888, 2048), (71, 41, 200, 0, 14200, 2048)),
+    (16384, 64, 0, (2, 16, 1024, 1, 2048, 2048), (2, 16, 1024, 1, 2048, 2048), (2, 16, 1024, 0, 2048, 2048)),
+    (16384, 64, 4, (2, 79, 208, 1, 416, 32), (2, 16, 1024, 1, 2048, 32), (2, 64, 256, 0, 512, 32)),
+    (16384, 64, 256, (2, 16, 1024, 1, 2048, 2048), (2, 16, 1024, 1, 2048, 2048), (2, 16, 1024, 0, 2048, 2048)),
+    (16384, 4096, 0, (74, 66, 249, 1, 18426, 2048), (74, 16, 1024, 1, 75776, 2048), (71, 57, 288, 0, 20448, 2048)),
+    (16384, 4096, 4, (74, 152, 108, 1, 7992, 32), (74, 16, 1024, 1, 75776, 32), (71, 158, 104, 0, 7384, 32)),
+    (16384, 4096, 256, (74, 66, 249, 1, 18426, 2048), (74, 16, 1024, 1, 75776, 2048), (71, 57, 288, 0, 20448, 2048)),
+]
+
+
+def test_wave_geometry_pinned():
+    """the launch geometry of the row-marching compressible and shallow-water kernels (no kernel
+    runs) is what it was before the strip rules moved into csrc/wave_march.h (wave_strip_rows,
+    wave_strip_count, wave_fill_extra): strips from 8 rows to 16384, a column strip or 74 of them,
+    the default / 4 / 256 compute units, the library's strip length and a caller's 16 rows"""
+    from conftest import _get_ctx
+    _get_ctx("emu")
+    assert len(WAVE_GEOMETRY_PINNED) == 14 * 2 * 3
+    for nx, ny, cus, c0, c16, sw in WAVE_GEOMETRY_PINNED:
+        assert tuple(device.comp_wave_geometry(nx, ny, 4, cus, 0).values()) == c0, (nx, ny, cus)
+        assert tuple(device.comp_wave_geometry(nx, ny, 4, cus, 16).values()) == c16, (nx, ny, cus)
+        assert tuple(device.swe_wave_geometry(nx, ny, 4, cus).values()) == sw, (nx, ny, cus)
+
+
 @pytest.mark.parametrize("riemann", ["HLLC", "CGF", "HLLC_lm"])
 @pytest.mark.parametrize("nx,ny,grav,lim,flat,rows", [
     (40, 130, 0.0, 2, 1, 0), (33, 57, -1.5, 2, 1, 7), (64, 64, -1.5, 1, 0, 16)])
