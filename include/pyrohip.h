@@ -397,6 +397,15 @@ int pyrohip_comp_step(pyrohip_state *s, const pyrohip_comp_params *p,
    wavefronts per launch, wavefronts resident at once }.  For callers that decompose a grid
    (decomp.py; bench.py's scaling line records it per rank).                            */
 int pyrohip_comp_wave_geometry(int nx, int ny, int ng, int num_cus, int march_rows, int *out6);
+/* the launch geometry of the row-marching SphericalPolar step (k_sph_wave: kernel_set 2 on a state
+   with a geometry) on an nx x ny grid on a device of num_cus compute units (<= 0: 256) with the
+   caller's march_rows (0: the library's strips), without launching anything: out7 = { column
+   strips (56 updated columns each), rows per regular row strip, row strips (a last strip of fewer
+   than ng rows joins its predecessor), n_extra (the column strips [0, n_extra) are cut into row
+   strips + 1 equal parts instead), wavefronts per launch, wavefronts resident at once, the duty
+   value of the priority turns (0: more wavefronts than two rounds of resident ones; no priority
+   board is taken) }.  The code the step itself goes by.                                    */
+int pyrohip_sph_wave_geometry(int nx, int ny, int ng, int num_cus, int march_rows, int *out7);
 /* the driver's time-step policy, NullSimulation.compute_timestep
    (simulation_null.py:222-244): dt = cfl * min, scaled by init_tstep_factor on
    the first step (n == 0), growth capped by max_dt_change * dt_old, fix_dt > 0

@@ -39,6 +39,7 @@ int comp_rk_step_wave(pyrohip_state *, const pyrohip_comp_params *, pyrohip_stat
                       const double *, double, const StepScalars *, const double **);
 int comp_rk_cfl_min_device(pyrohip_state *, const pyrohip_comp_params *, const double **);
 int comp_wave_geometry(int, int, int, int, int, int *);
+int sph_wave_geometry(int, int, int, int, int, int *);
 int state_from_centers(pyrohip_state *, int, double, double, double *);
 int comp_sdc_update(pyrohip_state *, const pyrohip_state *, const pyrohip_state *, int, int, const int *,
                     const double *, double);
@@ -719,6 +720,12 @@ int pyrohip_comp_stage_dump(pyrohip_state *s, int stage_id, double *out)
 }
 
 }  // extern "C"
+
+extern "C" int pyrohip_sph_wave_geometry(int nx, int ny, int ng, int num_cus, int march_rows, int *out7)
+{
+    PYRO_REQUIRE(out7 && nx > 0 && ny > 0 && ng >= 0 && march_rows >= 0, "bad argument");
+    return pyro::exact::sph_wave_geometry(nx, ny, ng, num_cus, march_rows, out7);
+}
 
 extern "C" int pyrohip_comp_wave_geometry(int nx, int ny, int ng, int num_cus, int march_rows, int *out6)
 {

@@ -568,6 +568,35 @@ __global__ __launch_bounds__(64, 2) void k_sph_wave(const double *__restrict__ U
 
 }  // namespace
 
+// the launch geometry of k_sph_wave on an nx x ny grid with `cus` compute units (<= 0: 256) and the
+// caller's march_rows (0: the library's strips): what the step and pyrohip_sph_wave_geometry go by
+struct SphwGeom { int ncb, L, nsb, n_extra, nunits, slots, prio_duty; };
+static SphwGeom sphw_geometry(int nx, int ny, int ng, int cus, int march_rows)
+{
+    SphwGeom w;
+    if (cus <= 0) cus = 256;
+    w.slots = 8 * cus;                                    // (two wavefronts per SIMD)
+    w.ncb = (ny + SWOUT - 1) / SWOUT;
+    w.L = wave_strip_rows(nx, w.ncb, w.slots, 32);
+    if (march_rows > 0) w.L = march_rows < nx ? march_rows : nx;
+    w.nsb = wave_strip_count(nx, w.L, ng);
+    // (one round: as many strips as wavefront slots; the pairs of the SIMDs told their rows left: wave_march.h)
+    w.n_extra = march_rows > 0 ? 0 : wave_fill_extra(w.ncb, w.nsb, nx, w.slots);
+    w.nunits = w.ncb * w.nsb + w.n_extra;
+    // (up to two rounds of resident wavefronts: the pair of a SIMD takes turns; beyond, age decides)
+    w.prio_duty = (w.nunits <= 2 * w.slots) ? 5 : 0;
+    return w;
+}
+// (for callers that want to know before they launch: the tests that pick shapes for every path of
+// the kernel's unit decoding)  out: ncb, L, nsb, n_extra, wavefronts, resident slots, duty
+int sph_wave_geometry(int nx, int ny, int ng, int cus, int march_rows, int *out)
+{
+    const SphwGeom w = sphw_geometry(nx, ny, ng, cus, march_rows);
+    out[0] = w.ncb; out[1] = w.L; out[2] = w.nsb; out[3] = w.n_extra; out[4] = w.nunits; out[5] = w.slots;
+    out[6] = w.prio_duty;
+    return 0;
+}
+
 // SphericalPolar grid, one step in ONE launch of the row-marching kernel.  The caller checked what
 // the tile kernel needs too (comp_api.hip: comp_can_fuse_sph: CGF, outflow / reflect / periodic
 // sides) and has FILLED the state's ghost cells.  S == nullptr: one step with the host's dt;
@@ -591,15 +620,9 @@ int comp_step_wave_sph_ex(pyrohip_state *s, const pyrohip_comp_params *p, double
     const SphG G{h.Lx, h.Ly, h.Ax, h.Ay, h.V, h.dlAx, h.dlAy, h.x2d, h.sint, h.sinb, h.sinc, h.xmin,
                  h.rowf, h.colf, (int)h.qxp, (int)h.qyp};
     const int fac = (h.rowf && h.colf) ? 1 : 0;       // the caller handed the 1-d factors over
-    const int cus = c->num_cus > 0 ? c->num_cus : 256;
-    P.ncb = (g.ny + SWOUT - 1) / SWOUT;
-    P.L = wave_strip_rows(g.nx, P.ncb, 8 * cus, 32);      // (slots: two wavefronts per SIMD)
-    if (p->march_rows > 0) P.L = p->march_rows < g.nx ? p->march_rows : g.nx;
-    P.nsb = wave_strip_count(g.nx, P.L, g.ng);
-    // (one round: as many strips as wavefront slots; the pairs of the SIMDs told their rows left: wave_march.h)
-    P.n_extra = p->march_rows > 0 ? 0 : wave_fill_extra(P.ncb, P.nsb, g.nx, 8 * cus);
-    P.nunits = P.ncb * P.nsb + P.n_extra;
-    P.prio_duty = (P.nunits <= 2 * 8 * cus) ? 5 : 0;
+    const SphwGeom w = sphw_geometry(g.nx, g.ny, g.ng, c->num_cus, p->march_rows);
+    P.ncb = w.ncb; P.L = w.L; P.nsb = w.nsb; P.n_extra = w.n_extra; P.nunits = w.nunits;
+    P.prio_duty = w.prio_duty;
 #if !defined(PYRO_EMU)
     if (P.prio_duty > 0) PYRO_TRY(prio_board_acquire(c, &P.prio_board, &P.prio_tag));
 #endif

@@ -190,12 +190,16 @@ __device__ __forceinline__ double pdivr(double a, double b, double rb) { (void)r
 // quotient above is the IEEE one except for the SIGN of a zero quotient (-0 / d gives +0: the
 // Markstein correction adds +0), and the characteristic tracing takes copysign(1, u)
 // (interface.py:198-201) -- a cell at rest whose momentum is -0.0 (an odd reflection of +0.0)
-// would trace the other way than the reference.  One compare + select, bit-faithful build only.
+// would trace the other way than the reference.  The zero takes the sign of the IEEE quotient, the
+// momentum's sign times the density's: a ghost cell beyond an ODDLY reflecting boundary (the
+// spherical Sedov set-up's reflect-odd) has a negative density, and -0 / d is +0 there
+// (tests/test_sph_oracle.py: gas at rest beside such a boundary, unlimited slopes).  Two compares +
+// two selects, bit-faithful build only.
 __device__ __forceinline__ double pvel(double m, double d, double rd)
 {
     const double q = pdivr(m, d, rd);
 #if !PYRO_FAST && !defined(PYRO_EMU)
-    return (m == 0.0) ? m : q;
+    return (m == 0.0) ? ((d < 0.0) ? -m : m) : q;
 #else
     return q;
 #endif

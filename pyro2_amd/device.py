@@ -36,6 +36,19 @@ def swe_wave_geometry(nx, ny, ng=4, num_cus=0):
                     (int(v) for v in out)))
 
 
+def sph_wave_geometry(nx, ny, ng=4, num_cus=0, march_rows=0):
+    """launch geometry of the row-marching SphericalPolar step (k_sph_wave) on an nx x ny grid
+    (pyrohip_sph_wave_geometry, no kernel runs): dict of column strips, rows per regular row
+    strip, row strips, n_extra (the first n_extra column strips are cut into row_strips + 1 equal
+    parts), wavefronts per launch, resident wavefront slots, and the duty value of the priority
+    turns (0: more wavefronts than two rounds of slots, no priority board is taken)"""
+    out = (C.c_int * 7)()
+    check(_lib.lib().pyrohip_sph_wave_geometry(int(nx), int(ny), int(ng), int(num_cus),
+                                                 int(march_rows), out))
+    return dict(zip(("col_strips", "rows_per_strip", "row_strips", "n_extra", "wavefronts", "slots",
+                     "prio_duty"), (int(v) for v in out)))
+
+
 def _check_run(rc, dts):
     """check() for a device-side run: the error carries what the run did before it stopped
     (steps_done, dts: the steps that advanced the state, which is the one before the failing step)"""
