@@ -387,7 +387,20 @@ int pyrohip_comp_dt(pyrohip_state *s, const pyrohip_comp_params *p, double cfl,
    apply_artificial_viscosity, conservative update, source corrector
    (unsplit_fluxes.py:134-549, interface.py:5-378, riemann.py:596-860).
    Ghost cells must be filled.  PYROHIP_ERR_STATE mirrors the reference's
-   positivity assert (simulation.py:68-71). */
+   positivity assert (simulation.py:68-71).
+
+   PASSIVE SCALARS.  Plane order of a compressible state: 0 density, 1 energy, 2 x-momentum,
+   3 y-momentum, then -- for pyrohip_comp_step, pyrohip_comp_dt and pyrohip_comp_dt_is_cached
+   only -- up to two passive scalars as partial densities rho X in planes 4 and 5 (nvar 5 or 6;
+   what the reference's compressible_react carries as "fuel" and "ash").  They are advected with
+   the gas in the same launch of the tile kernel (kernel_set 1 or -1, at every grid size): the
+   hydro planes and the time step come out bit for bit as without them.  With scalars the step
+   needs riemann 0 (HLLC) or 2 (HLLC_lm), a single Cartesian domain, outflow / reflect / periodic
+   sides on every variable (give the scalars the density's codes), no sponge, no heating profile
+   and no host-evaluated source; fuse_fill is honoured as for four planes.  Everything else
+   answers PYROHIP_ERR_ARG with a message that says "passive scalars".  Every other entry point
+   that takes a compressible state (pyrohip_comp_evolve, _comp_rk_*, _comp_fv4_rhs, ...) requires
+   exactly 4 planes. */
 int pyrohip_comp_step(pyrohip_state *s, const pyrohip_comp_params *p,
                       double dt);
 /* the launch geometry kernel_set 2 (the row-marching kernel) takes for an nx x ny grid or

@@ -28,6 +28,9 @@ def derive_primitives(myd, varnames):
             out.append(p)
         elif var == "primitive":
             out += [dens, u, v, p]
+            # the passive scalars' mass fractions behind them (nq > 4)
+            out += [myd.get_var(n) / dens for n in myd.names
+                    if n not in ("density", "energy", "x-momentum", "y-momentum")]
         elif var == "soundspeed":
             out.append(np.sqrt(gamma * p / dens))
         elif var == "machnumber":

@@ -8,6 +8,10 @@ D2H).  Scope of the device path: Cartesian
 grid, HLLC or CGF Riemann solver, gamma-law gas, limiter 0/1/2, flattening,
 artificial viscosity, gravity, sponge, standard boundary types plus the
 hse / ambient user boundaries.
+
+Passive scalars (initialize(extra_vars=...), one or two: what compressible_react carries) ride on
+the one-launch tile kernel: partial densities rho X behind the four hydro variables, on a single
+Cartesian domain with HLLC or HLLC_lm and outflow / reflect / periodic sides.
 """
 import numpy as np
 
@@ -48,6 +52,8 @@ def cons_to_prim(U, gamma, ivars, myg):
     e = np.divide(U[:, :, ivars.iener] - 0.5 * rho * (q[:, :, ivars.iu]**2 + q[:, :, ivars.iv]**2),
                   rho, out=np.zeros_like(rho), where=ok)
     q[:, :, ivars.ip] = eos.pres(gamma, rho, e)
+    for nq, nu in zip(range(ivars.ix, ivars.ix + ivars.naux), range(ivars.irhox, ivars.irhox + ivars.naux)):
+        q[:, :, nq] = U[:, :, nu] / rho          # mass fractions of the passive scalars (:75-78)
     return q
 
 
@@ -58,14 +64,51 @@ def prim_to_cons(q, gamma, ivars, myg):
     U[:, :, ivars.iymom] = q[:, :, ivars.iv] * U[:, :, ivars.idens]
     U[:, :, ivars.iener] = eos.rhoe(gamma, q[:, :, ivars.ip]) + \
         0.5 * q[:, :, ivars.irho] * (q[:, :, ivars.iu]**2 + q[:, :, ivars.iv]**2)
+    for nq, nu in zip(range(ivars.ix, ivars.ix + ivars.naux), range(ivars.irhox, ivars.irhox + ivars.naux)):
+        U[:, :, nu] = q[:, :, nq] * q[:, :, ivars.irho]
     return U
 
 
 class Simulation(NullSimulation):
     spherical_ok = True   # derived solvers without the geometry terms clear this
     decomposable = True   # x-slabs, one process per GPU (derived solvers with other steps clear this)
+    scalars_ok = True     # derived solvers whose kernels carry the four hydro variables only clear this
+
+    def _check_scalars(self, extra_vars):
+        """what a run with passive scalars excludes (the tile kernel carries them: DESIGN.md 3.7);
+        every message names the option"""
+        opt = self._rp_opt
+        if not type(self).scalars_ok:
+            msg.fail(f"ERROR: passive scalars (extra_vars) are not carried by {self.solver_name}: "
+                     "the compressible solver steps them")
+        if len(extra_vars) > 2:
+            msg.fail("ERROR: passive scalars: at most two are carried (extra_vars has "
+                     f"{len(extra_vars)})")
+        if opt("compressible.riemann", "HLLC") == "CGF":
+            msg.fail("ERROR: passive scalars need compressible.riemann = HLLC or HLLC_lm "
+                     "(the reference's CGF path cannot run with them either)")
+        if opt("mesh.grid_type", "Cartesian2d") == "SphericalPolar":
+            msg.fail("ERROR: passive scalars are not carried on a SphericalPolar grid (mesh.grid_type)")
+        from .. import decomp
+        if int(opt("gpu.decompose", -1)) == 1 or decomp.active_decomposition(self.rp) is not None:
+            msg.fail("ERROR: passive scalars run on a single domain (gpu.decompose / slabs are not carried)")
+        for side in ("xlboundary", "xrboundary", "ylboundary", "yrboundary"):
+            b = opt("mesh." + side, "outflow")
+            if b in ("hse", "ambient", "ramp"):
+                msg.fail(f"ERROR: passive scalars are not carried with the {b} boundary (mesh.{side}): "
+                         "outflow / reflect / periodic sides only")
+        if opt("sponge.do_sponge", 0):
+            msg.fail("ERROR: passive scalars are not carried with the sponge (sponge.do_sponge)")
+        if getattr(self, "problem_heating", None) is not None or self.problem_source is not None:
+            msg.fail("ERROR: passive scalars are not carried with a problem source "
+                     "(heating profile / host-evaluated source_terms)")
+        if int(opt("gpu.kernel_set", -1)) not in (-1, 1):
+            msg.fail("ERROR: passive scalars step on the tile kernel: gpu.kernel_set must be -1 or 1")
 
     def initialize(self, *, extra_vars=None, ng=4):
+        extra_vars = list(extra_vars or [])
+        if extra_vars:
+            self._check_scalars(extra_vars)
         my_grid = grid_setup(self.rp, ng=ng, spherical_ok=type(self).spherical_ok,
                              decomposable=type(self).decomposable)
         my_data = self.data_class(my_grid)
@@ -88,8 +131,8 @@ class Simulation(NullSimulation):
         my_data.register_var("energy", bc)
         my_data.register_var("x-momentum", bc_xodd)
         my_data.register_var("y-momentum", bc_yodd)
-        if extra_vars:
-            msg.fail("ERROR: passive scalars are not carried by the device path yet")
+        for v in extra_vars:       # :228-231: partial densities, with the density's boundary types
+            my_data.register_var(v, bc)
         my_data.set_aux("gamma", self.rp.get_param("eos.gamma"))
         my_data.set_aux("grav", self.rp.get_param("compressible.grav"))
         my_data.create()
@@ -266,7 +309,7 @@ class Simulation(NullSimulation):
         watching the data (a SphericalPolar grid: its one-launch step, i.e. no heating profile
         either)."""
         cc = self.cc_data
-        if self._host_source():
+        if self._host_source() or self.ivars.naux > 0:      # (scalars: single steps)
             return False
         if self.particles is not None and (cc.grid.coord_type != 0 or self._device_particle_source() is None):
             return False
@@ -320,7 +363,7 @@ class Simulation(NullSimulation):
         import matplotlib.pyplot as plt
         plt.clf()
         g = self.cc_data.grid
-        rho, u, v, p = self.cc_data.get_var("primitive")
+        rho, u, v, p = self.cc_data.get_var("primitive")[:4]
         fields = [rho, np.sqrt(u**2 + v**2), p, p / ((self.rp.get_param("eos.gamma") - 1.0) * rho)]
         names = [r"$\rho$", "U", "p", "e"]
         for n, (f, nm) in enumerate(zip(fields, names)):

@@ -14,6 +14,7 @@ from ..util import msg
 class Simulation(CompressibleSimulation):
     spherical_ok = False   # compressible_rk/fluxes.py has no geometry terms
     decomposable = False   # (the stages would each need a halo exchange: single domain)
+    scalars_ok = False     # (the method-of-lines kernels carry the four hydro variables)
 
     def initialize(self, *, extra_vars=None, ng=4):
         # reconstruction.py:24-25 (the reference stops there, in its first right-hand side)

@@ -91,21 +91,23 @@ static bool takes_wave_kernel(const Geom &g, const pyrohip_comp_params *p)
 // kernel passes the tile kernel there: 1024^2 78.3 -> 71.0 us per step, 1152^2 90.9 -> 78.4, 1536^2 148.6 ->
 // 136.6, 1792^2 190.4 -> 155.7; 896^2 a tie, below it and in the bit-faithful build the tile kernel stays ahead
 // up to 2048^2: 1024^2 104.8 vs 114.6 us, 1536^2 203.5 vs 226.9)
-static bool takes_wave_kernel_ctu(const Geom &g, const pyrohip_comp_params *p)
+// (a state with passive scalars, nvar > 4, steps on the tile kernel at every size)
+static bool takes_wave_kernel_ctu(const Geom &g, const pyrohip_comp_params *p, int nvar = 4)
 {
+    if (nvar > 4) return false;
     const double cells = (double)g.nx * (double)g.ny;
     return p->kernel_set == 2 || (p->kernel_set == -1 && g.nx >= 512 && g.ny >= 512 &&
                                   cells >= (p->fast_math ? 1024.0 * 1024.0 : 2048.0 * 2048.0));
 }
 
-// All four variables follow the same kind of index map on every side: outflow, reflect (even or
+// All variables (the four hydro ones and the passive scalars) follow the same kind of index map on every side: outflow, reflect (even or
 // odd), periodic -- or, where halo_ok, rows that arrived with a halo exchange (they are data).
 // (they do for bc / bc_xodd / bc_yodd, simulation_null.py:72-112)
 static bool same_index_map_kinds(const pyrohip_state *s, bool halo_ok)
 {
     for (int sd = 0; sd < 4; sd++) {
         int kind0 = -1;
-        for (int n = 0; n < 4; n++) {
+        for (int n = 0; n < s->nvar; n++) {
             const int b = s->bc[n * 4 + sd];
             const int kind = (b == PYROHIP_BC_OUTFLOW) ? 0
                              : (b == PYROHIP_BC_REFLECT_EVEN || b == PYROHIP_BC_REFLECT_ODD) ? 1
@@ -156,14 +158,44 @@ static bool strat_fill_ok(const pyrohip_state *s)
     return true;
 }
 
-static int check_comp(pyrohip_state *s, const pyrohip_comp_params *p)
+// max_scalars: passive scalars the entry point carries behind the four hydro planes (pyrohip_comp_step,
+// pyrohip_comp_dt: 2; every other entry point: none)
+static int check_comp(pyrohip_state *s, const pyrohip_comp_params *p, int max_scalars = 0)
 {
     PYRO_REQUIRE(s && p, "NULL argument");
-    PYRO_REQUIRE(s->nvar == 4, "compressible state must have 4 variables "
-                               "(density, energy, x-momentum, y-momentum)");
+    if (max_scalars > 0)
+        PYRO_REQUIRE(s->nvar >= 4 && s->nvar <= 4 + max_scalars,
+                     "compressible state must have 4 variables (density, energy, x-momentum, y-momentum) "
+                     "and at most 2 passive scalars behind them");
+    else
+        PYRO_REQUIRE(s->nvar == 4, "compressible state must have 4 variables "
+                                   "(density, energy, x-momentum, y-momentum); passive scalars are "
+                                   "carried by pyrohip_comp_step / pyrohip_comp_dt only");
     PYRO_REQUIRE(s->g.ng >= 4, "compressible needs ng >= 4 (compressible/simulation.py:194)");
     PYRO_REQUIRE(p->limiter >= 0 && p->limiter <= 2, "limiter must be 0, 1 or 2");
     PYRO_REQUIRE(p->dx > 0 && p->dy > 0 && p->gamma > 1.0, "bad dx/dy/gamma");
+    return 0;
+}
+
+// What a state with passive scalars (planes 4, 5: partial densities rho X) excludes: they are carried
+// by the tile kernel alone, with the upwinding of the HLLC solvers (the reference's CGF path cannot
+// run with species: consFlux on an array of states does not broadcast, riemann.py:1163, 1177)
+static int check_scalars(const pyrohip_state *s, const pyrohip_comp_params *p)
+{
+    if (s->nvar == 4) return 0;
+    PYRO_REQUIRE(p->riemann != 1, "passive scalars: compressible.riemann = CGF is not carried "
+                                  "(the reference cannot run it either); use HLLC or HLLC_lm");
+    PYRO_REQUIRE(!s->sph, "passive scalars: SphericalPolar grids are not carried");
+    PYRO_REQUIRE(!s->nb_set && !s->ctx->global_cfl, "passive scalars: decomposed runs (gpu.decompose, slabs) are not carried");
+    PYRO_REQUIRE(!s->user_bc && !s->ramp_bc, "passive scalars: hse / ambient / ramp boundaries are not carried");
+    PYRO_REQUIRE(!p->do_sponge, "passive scalars: the sponge (sponge.do_sponge) is not carried");
+    PYRO_REQUIRE(!s->heat && !s->ext_old, "passive scalars: heating profiles and host-evaluated sources are not carried");
+    PYRO_REQUIRE(p->kernel_set == 1 || p->kernel_set == -1,
+                 "passive scalars: gpu.kernel_set 0 and 2 are not carried (the tile kernel, kernel_set 1, steps them)");
+    PYRO_REQUIRE(s->g.nx >= 4 && s->g.ny >= 4, "passive scalars: the tile kernel needs at least 4 cells each way");
+    for (size_t k = 0; k < s->bc.size(); k++)
+        PYRO_REQUIRE(bc_is_index_map(s->bc[k], true),
+                     "passive scalars: outflow / reflect / periodic boundaries only");
     return 0;
 }
 
@@ -375,7 +407,7 @@ int pyrohip_comp_evolve(pyrohip_state *s, const pyrohip_comp_params *p, double c
 
 int pyrohip_comp_dt(pyrohip_state *s, const pyrohip_comp_params *p, double cfl, double *dt_out)
 {
-    PYRO_TRY(check_comp(s, p));
+    PYRO_TRY(check_comp(s, p, 2));      // (the CFL minimum reads the four hydro planes)
     PYRO_REQUIRE(dt_out, "dt_out is NULL");
     if (s->sph) {
         // (cached by the one-launch spherical step: whole-array minimum of the new state; every
@@ -410,7 +442,7 @@ int pyrohip_comp_dt_is_global(pyrohip_state *s, int *flag)
 
 int pyrohip_comp_step(pyrohip_state *s, const pyrohip_comp_params *p, double dt)
 {
-    PYRO_TRY(check_comp(s, p));
+    PYRO_TRY(check_comp(s, p, 2));
     PYRO_REQUIRE(dt > 0.0, "dt must be positive");
     PYRO_REQUIRE(!p->well_balanced, "well_balanced is carried by pyrohip_comp_rk_rhs only (compressible_rk, "
                                     "stage by stage on the staged kernels)");
@@ -419,12 +451,13 @@ int pyrohip_comp_step(pyrohip_state *s, const pyrohip_comp_params *p, double dt)
     int rc;
     PYRO_REQUIRE(!s->ext_pending, "the corrector of the host-evaluated source has not run "
                                   "(pyrohip_comp_source_correct)");
+    PYRO_TRY(check_scalars(s, p));
     pyrohip_comp_params pf = *p;
     if (p->fuse_fill) {
         // ghost cells not filled by the caller: folded into the tile kernel where that
         // works, the ordinary fill first everywhere else
         // (the spherical one-launch kernel reads every ghost cell through the boundary rules)
-        const bool wave = !s->sph && takes_wave_kernel_ctu(s->g, p);
+        const bool wave = !s->sph && takes_wave_kernel_ctu(s->g, p, s->nvar);
         if (!comp_can_fuse_fill(s, p, wave) && !comp_can_fuse_sph(s, p)) {
             PYRO_TRY(pyrohip_fill_bc(s, -1));
             pf.fuse_fill = 0;
@@ -456,7 +489,7 @@ int pyrohip_comp_step(pyrohip_state *s, const pyrohip_comp_params *p, double dt)
         PYRO_REQUIRE(!s->heat && !s->ramp_bc, "a host-evaluated source excludes the heating "
                      "profile and the ramp boundary (which zeroes the source arrays, BC.py:198-200)");
         return p->fast_math ? fastm::comp_step_staged(s, p, dt) : exact::comp_step_staged(s, p, dt);
-    } else if (takes_wave_kernel_ctu(s->g, p))
+    } else if (takes_wave_kernel_ctu(s->g, p, s->nvar))
         rc = p->fast_math ? fastm::comp_step_wave(s, p, dt) : exact::comp_step_wave(s, p, dt);
     else if (p->kernel_set == 1 || p->kernel_set == -1)
         rc = p->fast_math ? fastm::comp_step_fused(s, p, dt) : exact::comp_step_fused(s, p, dt);

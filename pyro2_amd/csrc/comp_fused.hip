@@ -48,9 +48,15 @@ constexpr int FTJ = FBJ - 2;
 constexpr int FQH = FBI + 6;            // Q tile rows  (tile + 4 apron)
 constexpr int FQW = FBJ + 6;
 constexpr int FQN = FQH * FQW;          // cells in the Q tile
-constexpr int FBUF0 = (4 * FQN > 8 * FNT) ? 4 * FQN : 8 * FNT;   // Q | FT | F
-constexpr int FLDS_DOUBLES = FBUF0 + 8 * FNT + FNT;
-constexpr size_t FLDS_BYTES = (size_t)FLDS_DOUBLES * sizeof(double);
+// ... with `na` passive scalars beside the four hydro variables (k_ctu_fused<.., NA>)
+constexpr int fbuf0(int na) { return ((4 + na) * FQN > 2 * (4 + na) * FNT) ? (4 + na) * FQN : 2 * (4 + na) * FNT; }
+constexpr int flds_doubles(int na) { return fbuf0(na) + 2 * (4 + na) * FNT + FNT; }
+constexpr size_t flds_bytes(int na) { return (size_t)flds_doubles(na) * sizeof(double); }
+constexpr int FBUF0 = fbuf0(0);   // Q | FT | F
+constexpr int FLDS_DOUBLES = flds_doubles(0);
+constexpr size_t FLDS_BYTES = flds_bytes(0);
+static_assert(FBUF0 == 8 * FNT && FLDS_BYTES == 68 * 1024 && flds_bytes(1) == 84 * 1024 &&
+              flds_bytes(2) == 100 * 1024, "LDS budget of the tile kernel");
 
 #include "fused_common.h"
 
@@ -81,6 +87,80 @@ __device__ __forceinline__ void lds_put(double *b, int t, const Cons &U)
 {
     b[t] = U.d; b[FNT + t] = U.E; b[2 * FNT + t] = U.mx; b[3 * FNT + t] = U.my;
 }
+
+// ---- passive scalars (k_ctu_fused<.., NA>): planes 4 .. 4 + NA - 1 of the state hold the partial
+// densities rho X.  They ride on the hydro step: the same ghost images, slopes and flattening, a
+// wave of their own that moves with the fluid, the upwind side of the face's hydro Riemann problem.
+// Plane 4 + a of cell (gi, gj) as load_cons_bc reads the first four.
+__device__ __forceinline__ double load_aux_bc(const double *__restrict__ Uin, const Geom &g, const FP &P,
+                                              int gi, int gj, int a)
+{
+    const int si = bc_src(P.mr, gi, g.ilo, g.ihi), sj = bc_src(P.mc, gj, g.jlo, g.jhi);
+    const unsigned sd = (gi < g.ilo ? 1u : 0u) | (gi > g.ihi ? 2u : 0u) | (gj < g.jlo ? 4u : 0u) |
+                        (gj > g.jhi ? 8u : 0u);
+    const double X = Uin[(size_t)(4 + a) * g.plane + (size_t)si * g.pitch + sj];
+    return odd_sides((P.odd >> (4 * (4 + a))) & sd) ? -X : X;
+}
+// Contracted build: -ffp-contract=fast lets the compiler fuse a product into whatever sum it feeds,
+// and it chooses per instance -- the NA = 1 and NA = 2 kernels gave a scalar's plane one unit in
+// the last place apart (measured: 5.6e-17 in one case of tests/test_comp_scalars.py).  So the
+// scalars' arithmetic leaves it no choice there: every fused multiply-add is written out and a
+// flux, once formed, is opaque (fp_keep, stencil.h).  The bit-faithful build contracts nothing.
+__device__ __forceinline__ double aux_keep(double x)
+{
+#if PYRO_FAST
+    return fp_keep(x);
+#else
+    return x;
+#endif
+}
+// F += av (Um - Uc): the artificial viscosity on one more component
+__device__ __forceinline__ double avisc1(double F, double av, double Um, double Uc)
+{
+#if PYRO_FAST
+    return aux_keep(fma(av, Um - Uc, F));
+#else
+    return F + av * (Um - Uc);
+#endif
+}
+// the conservative update of one more component (simulation.py:377-384)
+__device__ __forceinline__ double update1(double U, double dtdV, double Fx, double Fxh, double Ax,
+                                          double Fy, double Fyh, double Ay)
+{
+#if PYRO_FAST
+    return fma(dtdV, fma(Ay, Fy - Fyh, aux_keep(Ax * (Fx - Fxh))), U);
+#else
+    return U + dtdV * (Fx * Ax - Fxh * Ax + Fy * Ay - Fyh * Ay);
+#endif
+}
+// corr() for one more component
+__device__ __forceinline__ double corr1(double U, double Fhi, double Flo, double hdtV, double A)
+{
+#if PYRO_FAST
+    return aux_keep(fma(-hdtV * A, Fhi - Flo, U));
+#else
+    return U + (-hdtV * (Fhi * A - Flo * A));
+#endif
+}
+// The Riemann problem of the face below the thread's cell: the upper state of the lower neighbour
+// (slot tl of the LDS planes Sl) against the cell's own lower state UM; aUM / aF: the scalars'
+// lower states and, on return, their fluxes.
+template <int SOLVER, int NA>
+__device__ __forceinline__ Cons face_flux(const double *Sl, int tl, const Cons &UM, const double *aUM,
+                                          double gamma, bool x, bool wall, double *aF)
+{
+    const Cons UL = lds_get(Sl, tl);
+    if constexpr (NA == 0) {
+        return from_nf(riemann_face<SOLVER>(to_nf(UL, x), to_nf(UM, x), gamma, x, wall), x);
+    } else {
+        FaceUpwind w;
+        const Cons F = from_nf(riemann_face<SOLVER>(to_nf(UL, x), to_nf(UM, x), gamma, x, wall, &w), x);
+#pragma unroll
+        for (int a = 0; a < NA; a++)
+            aF[a] = aux_keep(passive_flux<SOLVER>(w, F.d, UL.d, UM.d, Sl[(4 + a) * FNT + tl], aUM[a]));
+        return F;
+    }
+}
 // developer timing aid (tools/fused_phases.py): -DPYRO_FUSED_STOP=k ends the
 // kernel after phase k, storing one value that depends on the phase's results
 #ifndef PYRO_FUSED_STOP
@@ -103,13 +183,20 @@ constexpr int FUSED_MINW = 4;
 // eight limited slopes (3.84 -> 3.61 ms at 8192^2; also making "no sources" a
 // constant gave 3.59 and was not kept: problems with gravity use this instance
 // too); STD = false reads both from the parameters
-template <int SOLVER, bool STD = false>   // compressible.riemann: 0 HLLC, 1 CGF, 2 HLLC_lm
-__global__ __launch_bounds__(FNT, FUSED_MINW) void k_ctu_fused(const double *__restrict__ Uin,
+//
+// NA: passive scalars carried beside the four hydro variables (0, 1 or 2; HLLC and HLLC_lm).  Every
+// LDS buffer grows by NA planes: 84 KiB (NA = 1) and 100 KiB (NA = 2) against 68 KiB, i.e. ONE
+// workgroup per CU -- those instances may use the 256 VGPRs that leaves a wavefront.  NA = 0 is the
+// kernel as it was: everything below that concerns scalars stands under `if constexpr (NA > 0)`.
+template <int SOLVER, bool STD = false, int NA = 0>   // compressible.riemann: 0 HLLC, 1 CGF, 2 HLLC_lm
+__global__ __launch_bounds__(FNT, (NA > 0 ? 2 : FUSED_MINW)) void k_ctu_fused(const double *__restrict__ Uin,
                                                    double *__restrict__ Uout, Geom g, FP P_in,
                                                    int *__restrict__ flag,
                                                    double *__restrict__ partial,
                                                    const StepScalars *__restrict__ SC)
 {
+    constexpr int NV = 4 + NA;                 // planes of the state
+    constexpr int NAX = NA > 0 ? NA : 1;       // (array bounds)
     HIP_DYNAMIC_SHARED(double, lds)
     FP P = P_in;
     if (SC) {   // device-side run: this step's dt lives in device memory
@@ -122,9 +209,11 @@ __global__ __launch_bounds__(FNT, FUSED_MINW) void k_ctu_fused(const double *__r
         }
         P.dt = SC->dt; P.dtdx = SC->dtdx; P.dtdy = SC->dtdy; P.hdtV = SC->hdtV; P.dtdV = SC->dtdV;
     }
-    double *B0 = lds;                 // Q (phase 0-1) | FT (2-3) | F (4-5)
-    double *S = lds + FBUF0;          // upper face states XP(0..3), YP(4..7)
-    double *D = S + 8 * FNT;          // vertex div(U)
+    double *B0 = lds;                 // Q (phase 0-1) | FT (2-3) | F (4-5): x planes, then y planes
+    double *S = lds + fbuf0(NA);      // upper face states XP(0..NV-1), YP(NV..2 NV-1)
+    double *SY = S + NV * FNT;
+    double *BY = B0 + NV * FNT;       // the y fluxes
+    double *D = S + 2 * NV * FNT;     // vertex div(U)
 
     // (a walk that keeps every XCD on a contiguous band of tiles for ANY tile
     // count -- xcd_tile falls back to the identity when it is not divisible by
@@ -151,6 +240,7 @@ __global__ __launch_bounds__(FNT, FUSED_MINW) void k_ctu_fused(const double *__r
     {
         constexpr int NIT = (FQN + FNT - 1) / FNT;
         Cons Ul[NIT];
+        double Al[NIT][NAX];
         bool act[NIT], interior[NIT];
 #pragma unroll
         for (int n = 0; n < NIT; n++) {
@@ -169,6 +259,10 @@ __global__ __launch_bounds__(FNT, FUSED_MINW) void k_ctu_fused(const double *__r
             const Cons U = load_cons_bc(Uin, g, P, gi, gj, sd);
             Ul[n] = U;
             interior[n] = (sd == 0);
+            if constexpr (NA > 0) {
+#pragma unroll
+                for (int a = 0; a < NA; a++) Al[n][a] = load_aux_bc(Uin, g, P, gi, gj, a);
+            }
             // the ghost frame of the new state: what the old state's ghost cells hold
             // (after the fill, when it is folded in) -- as in the reference, where the
             // update leaves the ghost cells of the array alone.  Tiles whose aprons
@@ -176,6 +270,10 @@ __global__ __launch_bounds__(FNT, FUSED_MINW) void k_ctu_fused(const double *__r
             if (inarr && sd != 0) {
                 const size_t ko = (size_t)gi * p + gj;
                 Uout[ko] = U.d; Uout[pl + ko] = U.E; Uout[2 * pl + ko] = U.mx; Uout[3 * pl + ko] = U.my;
+                if constexpr (NA > 0) {
+#pragma unroll
+                    for (int a = 0; a < NA; a++) Uout[(4 + a) * pl + ko] = Al[n][a];
+                }
             }
         }
 #pragma unroll
@@ -189,6 +287,10 @@ __global__ __launch_bounds__(FNT, FUSED_MINW) void k_ctu_fused(const double *__r
             if (act[n] && interior[n] && (!ok || dnan)) bad = true;
             if (act[n]) {
                 B0[idx] = q.r; B0[FQN + idx] = q.u; B0[2 * FQN + idx] = q.v; B0[3 * FQN + idx] = q.p;
+                if constexpr (NA > 0) {   // X = rho X / rho, the floored rho (simulation.py:75-78)
+#pragma unroll
+                    for (int a = 0; a < NA; a++) B0[(4 + a) * FQN + idx] = pdiv(Al[n][a], U.d);
+                }
             }
         }
     }
@@ -198,6 +300,7 @@ __global__ __launch_bounds__(FNT, FUSED_MINW) void k_ctu_fused(const double *__r
 
     // ---- phase 1: xi, slopes, tracing for the thread's own cell --------
     Cons XM, XP, YM, YP;
+    double aXM[NAX], aXP[NAX], aYM[NAX], aYP[NAX];   // ... of the scalars
     {
         const int qc = (ti + 3) * FQW + (tj + 3);   // own cell in the Q tile
         const double *Qr = B0, *Qu = B0 + FQN, *Qv = B0 + 2 * FQN, *Qp = B0 + 3 * FQN;
@@ -221,9 +324,9 @@ __global__ __launch_bounds__(FNT, FUSED_MINW) void k_ctu_fused(const double *__r
                                          Qv[cy - 1], Qv[cy + 1], P.z0, P.z1, P.delta);
             xi = fmin(fmin(xix, px), fmin(xiy, py));
         }
-        double q0[4], dqx[4], dqy[4];
+        double q0[NV], dqx[NV], dqy[NV];
 #pragma unroll
-        for (int n = 0; n < 4; n++) {
+        for (int n = 0; n < NV; n++) {
             const double *a = B0 + n * FQN;
             q0[n] = a[qc];
             dqx[n] = xi * limited_slope(a[qc - 2 * FQW], a[qc - FQW], a[qc], a[qc + FQW],
@@ -240,6 +343,18 @@ __global__ __launch_bounds__(FNT, FUSED_MINW) void k_ctu_fused(const double *__r
                      P.dtdy, lo, hi);
         YM = prim_to_cons(Prim{lo.r, lo.ut, lo.un, lo.p}, gamma);
         YP = prim_to_cons(Prim{hi.r, hi.ut, hi.un, hi.p}, gamma);
+        if constexpr (NA > 0) {
+            // the scalars' face states: traced with the fluid, then rho X = X rho of the face state
+            // (prim_to_cons, simulation.py:101-104); no source term touches them
+#pragma unroll
+            for (int a = 0; a < NA; a++) {
+                double xl, xh;
+                trace_passive(q0[0], q0[1], q0[3], q0[4 + a], dqx[4 + a], gamma, P.dtdx, xl, xh);
+                aXM[a] = aux_keep(xl * XM.d); aXP[a] = aux_keep(xh * XP.d);
+                trace_passive(q0[0], q0[2], q0[3], q0[4 + a], dqy[4 + a], gamma, P.dtdy, xl, xh);
+                aYM[a] = aux_keep(xl * YM.d); aYP[a] = aux_keep(xh * YP.d);
+            }
+        }
         // vertex divergence at (i-1/2, j-1/2), interface.py:312-330
         D[t] = div_u_vertex(Qu[qc], Qu[qc - 1], Qu[qc - FQW], Qu[qc - FQW - 1], Qv[qc],
                             Qv[qc - FQW], Qv[qc - 1], Qv[qc - FQW - 1], P.dx, P.dy);
@@ -262,22 +377,28 @@ __global__ __launch_bounds__(FNT, FUSED_MINW) void k_ctu_fused(const double *__r
             add_grav_to_state(YP, Ug, P.grav, P.dt, sgn, P.heat_rate, hp);
         }
         lds_put(S, t, XP);
-        lds_put(S + 4 * FNT, t, YP);
+        lds_put(SY, t, YP);
+        if constexpr (NA > 0) {
+#pragma unroll
+            for (int a = 0; a < NA; a++) { S[(4 + a) * FNT + t] = aXP[a]; SY[(4 + a) * FNT + t] = aYP[a]; }
+        }
     }
     __syncthreads();   // Q is dead from here on; B0 becomes the flux buffer
     PYRO_PHASE_END(1, XM.d + XM.E + XM.mx + XM.my + YM.d + YM.E + YM.mx + YM.my + S[t] + S[7 * FNT + t] + D[t])
 
     // ---- phase 2: transverse Riemann problems on the lower faces --------
     Cons FxT{0, 0, 0, 0}, FyT{0, 0, 0, 0};
+    double aFxT[NAX] = {}, aFyT[NAX] = {};
     if (ti >= 1)
-        FxT = from_nf(riemann_face<SOLVER>(to_nf(lds_get(S, t - FBJ), true), to_nf(XM, true), gamma,
-                                           true, P.solid_xl && i == g.ilo), true);
+        FxT = face_flux<SOLVER, NA>(S, t - FBJ, XM, aXM, gamma, true, P.solid_xl && i == g.ilo, aFxT);
     if (tj >= 1)
-        FyT = from_nf(riemann_face<SOLVER>(to_nf(lds_get(S + 4 * FNT, t - 1), false),
-                                           to_nf(YM, false), gamma, false,
-                                           P.solid_yl && j == g.jlo), false);
+        FyT = face_flux<SOLVER, NA>(SY, t - 1, YM, aYM, gamma, false, P.solid_yl && j == g.jlo, aFyT);
     lds_put(B0, t, FxT);
-    lds_put(B0 + 4 * FNT, t, FyT);
+    lds_put(BY, t, FyT);
+    if constexpr (NA > 0) {
+#pragma unroll
+        for (int a = 0; a < NA; a++) { B0[(4 + a) * FNT + t] = aFxT[a]; BY[(4 + a) * FNT + t] = aFyT[a]; }
+    }
     __syncthreads();
     PYRO_PHASE_END(2, FxT.d + FxT.E + FxT.mx + FxT.my + FyT.d + FyT.E + FyT.mx + FyT.my + XM.d + YM.E)
 
@@ -285,19 +406,39 @@ __global__ __launch_bounds__(FNT, FUSED_MINW) void k_ctu_fused(const double *__r
     const double hdtV = P.hdtV;                          // hdt / V
     const double Ax = P.dy, Ay = P.dx;
     if (tj >= 1 && tj <= FBJ - 2) {
-        const Cons Fhi = lds_get(B0 + 4 * FNT, t + 1);   // F_yT at (i, j+1)
+        const Cons Fhi = lds_get(BY, t + 1);             // F_yT at (i, j+1)
         XM = corr(XM, Fhi, FyT, hdtV, Ay);
         XP = corr(XP, Fhi, FyT, hdtV, Ay);
+        if constexpr (NA > 0) {
+#pragma unroll
+            for (int a = 0; a < NA; a++) {
+                const double fh = BY[(4 + a) * FNT + t + 1];
+                aXM[a] = corr1(aXM[a], fh, aFyT[a], hdtV, Ay);
+                aXP[a] = corr1(aXP[a], fh, aFyT[a], hdtV, Ay);
+            }
+        }
     }
     if (ti >= 1 && ti <= FBI - 2) {
         const Cons Fhi = lds_get(B0, t + FBJ);           // F_xT at (i+1, j)
         YM = corr(YM, Fhi, FxT, hdtV, Ax);
         YP = corr(YP, Fhi, FxT, hdtV, Ax);
+        if constexpr (NA > 0) {
+#pragma unroll
+            for (int a = 0; a < NA; a++) {
+                const double fh = B0[(4 + a) * FNT + t + FBJ];
+                aYM[a] = corr1(aYM[a], fh, aFxT[a], hdtV, Ax);
+                aYP[a] = corr1(aYP[a], fh, aFxT[a], hdtV, Ax);
+            }
+        }
     }
     // (all reads of the uncorrected upper states happened before the barrier
     // that closed phase 2; phase 3 itself only reads the flux buffer)
     lds_put(S, t, XP);
-    lds_put(S + 4 * FNT, t, YP);
+    lds_put(SY, t, YP);
+    if constexpr (NA > 0) {
+#pragma unroll
+        for (int a = 0; a < NA; a++) { S[(4 + a) * FNT + t] = aXP[a]; SY[(4 + a) * FNT + t] = aYP[a]; }
+    }
     __syncthreads();
     PYRO_PHASE_END(3, XM.d + XM.E + XM.mx + XM.my + YM.d + YM.E + YM.mx + YM.my + S[t] + S[7 * FNT + t])
 
@@ -316,6 +457,15 @@ __global__ __launch_bounds__(FNT, FUSED_MINW) void k_ctu_fused(const double *__r
     // covered by them.  k - p / k - 1 are inside the array for every thread.
     Cons Umx = load_cons_bc(Uin, g, P, ic - 1, jc, sdc);
     Cons Umy = load_cons_bc(Uin, g, P, ic, jc - 1, sdc);
+    double aUc[NAX], aUmx[NAX], aUmy[NAX], aFx[NAX] = {}, aFy[NAX] = {};
+    if constexpr (NA > 0) {
+#pragma unroll
+        for (int a = 0; a < NA; a++) {
+            aUc[a] = load_aux_bc(Uin, g, P, ic, jc, a);
+            aUmx[a] = load_aux_bc(Uin, g, P, ic - 1, jc, a);
+            aUmy[a] = load_aux_bc(Uin, g, P, ic, jc - 1, a);
+        }
+    }
     double avx = 0.0, avy = 0.0;
     // interface.py:366-376: only faces i in [ilo, ihi], j in [jlo, jhi]
     if (ti >= 1 && tj >= 1 && tj <= FBJ - 2 && i >= g.ilo &&
@@ -333,24 +483,33 @@ __global__ __launch_bounds__(FNT, FUSED_MINW) void k_ctu_fused(const double *__r
     if (i >= g.ilo && i <= g.ihi && j - 1 >= g.jlo && j - 1 <= g.jhi)
         Umy.d = fmax(Umy.d, P.small_dens);
     if (ti >= 1 && tj >= 1 && tj <= FBJ - 2) {           // x face (i, j)
-        Fx = from_nf(riemann_face<SOLVER>(to_nf(lds_get(S, t - FBJ), true), to_nf(XM, true), gamma,
-                                          true, P.solid_xl && i == g.ilo), true);
+        Fx = face_flux<SOLVER, NA>(S, t - FBJ, XM, aXM, gamma, true, P.solid_xl && i == g.ilo, aFx);
         Fx.d += avx * (Umx.d - Uc.d);
         Fx.E += avx * (Umx.E - Uc.E);
         Fx.mx += avx * (Umx.mx - Uc.mx);
         Fx.my += avx * (Umx.my - Uc.my);
+        if constexpr (NA > 0) {
+#pragma unroll
+            for (int a = 0; a < NA; a++) aFx[a] = avisc1(aFx[a], avx, aUmx[a], aUc[a]);
+        }
     }
     if (tj >= 1 && ti >= 1 && ti <= FBI - 2) {           // y face (i, j)
-        Fy = from_nf(riemann_face<SOLVER>(to_nf(lds_get(S + 4 * FNT, t - 1), false),
-                                          to_nf(YM, false), gamma, false,
-                                          P.solid_yl && j == g.jlo), false);
+        Fy = face_flux<SOLVER, NA>(SY, t - 1, YM, aYM, gamma, false, P.solid_yl && j == g.jlo, aFy);
         Fy.d += avy * (Umy.d - Uc.d);
         Fy.E += avy * (Umy.E - Uc.E);
         Fy.mx += avy * (Umy.mx - Uc.mx);
         Fy.my += avy * (Umy.my - Uc.my);
+        if constexpr (NA > 0) {
+#pragma unroll
+            for (int a = 0; a < NA; a++) aFy[a] = avisc1(aFy[a], avy, aUmy[a], aUc[a]);
+        }
     }
     lds_put(B0, t, Fx);            // FT was last read before the barrier above
-    lds_put(B0 + 4 * FNT, t, Fy);
+    lds_put(BY, t, Fy);
+    if constexpr (NA > 0) {
+#pragma unroll
+        for (int a = 0; a < NA; a++) { B0[(4 + a) * FNT + t] = aFx[a]; BY[(4 + a) * FNT + t] = aFy[a]; }
+    }
     __syncthreads();
     PYRO_PHASE_END(4, Fx.d + Fx.E + Fx.mx + Fx.my + Fy.d + Fy.E + Fy.mx + Fy.my)
 
@@ -359,7 +518,7 @@ __global__ __launch_bounds__(FNT, FUSED_MINW) void k_ctu_fused(const double *__r
     if (ti >= 1 && ti <= FBI - 2 && tj >= 1 && tj <= FBJ - 2 && cell_interior) {
         const double dtdV = P.dtdV;
         const Cons Fxh = lds_get(B0, t + FBJ);
-        const Cons Fyh = lds_get(B0 + 4 * FNT, t + 1);
+        const Cons Fyh = lds_get(BY, t + 1);
         Cons Un;   // simulation.py:377-384
         Un.d = Uc.d + dtdV * (Fx.d * Ax - Fxh.d * Ax + Fy.d * Ay - Fyh.d * Ay);
         Un.E = Uc.E + dtdV * (Fx.E * Ax - Fxh.E * Ax + Fy.E * Ay - Fyh.E * Ay);
@@ -368,6 +527,13 @@ __global__ __launch_bounds__(FNT, FUSED_MINW) void k_ctu_fused(const double *__r
         if (P.have_src)   // simulation.py:406-423
             grav_update(Un, Uc, P.grav, P.dt, P.heat_rate, P.heat ? P.heat[k] : 0.0);
         Uout[k] = Un.d; Uout[pl + k] = Un.E; Uout[2 * pl + k] = Un.mx; Uout[3 * pl + k] = Un.my;
+        if constexpr (NA > 0) {   // the same update; no source term, and the CFL minimum is the hydro one
+#pragma unroll
+            for (int a = 0; a < NA; a++) {
+                const double fxh = B0[(4 + a) * FNT + t + FBJ], fyh = BY[(4 + a) * FNT + t + 1];
+                Uout[(4 + a) * pl + k] = update1(aUc[a], dtdV, aFx[a], fxh, Ax, aFy[a], fyh, Ay);
+            }
+        }
         cfl = cfl_cell(Un, gamma, P.dx, P.dy);
     }
     cfl = block_reduce_min(cfl);
@@ -806,12 +972,18 @@ int comp_step_fused_ex(pyrohip_state *s, const pyrohip_comp_params *p, double dt
     PYRO_TRY(fused_prepare(s, p, dt, P, Uin, Uout, S == nullptr));
     if (p->fuse_fill) {
         // the caller checked comp_can_fuse_fill(): outflow / reflect / periodic / halo sides
-        // (the same kinds for all four variables; halo rows are data), no source terms
+        // (the same kinds for every variable; halo rows are data), no source terms
         P.mr = bc_map(g.ilo, g.ihi, g.ng, s->bc[0], s->bc[1], true);
         P.mc = bc_map(g.jlo, g.jhi, g.ng, s->bc[2], s->bc[3], true);
-        for (int n = 0; n < 4; n++)
+        for (int n = 0; n < s->nvar; n++)
             for (int sd = 0; sd < 4; sd++)
                 if (s->bc[n * 4 + sd] == PYROHIP_BC_REFLECT_ODD) P.odd |= 1u << (4 * n + sd);
+    }
+    // passive scalars: planes 4 and 5 of the state (pyrohip_comp_step checked what they exclude)
+    const int na = s->nvar - 4;
+    if (na < 0 || na > 2 || (na > 0 && p->riemann != 0 && p->riemann != 2)) {
+        set_error("the tile kernel carries 0 to 2 passive scalars, with HLLC or HLLC_lm");
+        return PYROHIP_ERR_ARG;
     }
     const int nti = (g.nx + FTI - 1) / FTI;
     P.ntj = (g.ny + FTJ - 1) / FTJ;
@@ -825,6 +997,10 @@ int comp_step_fused_ex(pyrohip_state *s, const pyrohip_comp_params *p, double dt
         {k_ctu_fused<0, false>, k_ctu_fused<0, true>},
         {k_ctu_fused<1, false>, k_ctu_fused<1, true>},
         {k_ctu_fused<2, false>, k_ctu_fused<2, true>}};
+    // ... with scalars: [HLLC | HLLC_lm][NA - 1], the generic reconstruction only
+    static const KernelT kernels_na[2][2] = {
+        {k_ctu_fused<0, false, 1>, k_ctu_fused<0, false, 2>},
+        {k_ctu_fused<2, false, 1>, k_ctu_fused<2, false, 2>}};
 #ifndef PYRO_EMU
     static bool attr_set = false;
     if (!attr_set) {
@@ -833,10 +1009,18 @@ int comp_step_fused_ex(pyrohip_state *s, const pyrohip_comp_params *p, double dt
                 PYRO_CHECK_HIP(hipFuncSetAttribute((const void *)kernels[a][b],
                                                    hipFuncAttributeMaxDynamicSharedMemorySize,
                                                    (int)FLDS_BYTES));
+        for (int a = 0; a < 2; a++)
+            for (int b = 0; b < 2; b++)
+                PYRO_CHECK_HIP(hipFuncSetAttribute((const void *)kernels_na[a][b],
+                                                   hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                   (int)flds_bytes(b + 1)));
         attr_set = true;
     }
 #endif
-    {
+    if (na > 0) {
+        PYRO_LAUNCH(c, "k_ctu_fused", kernels_na[p->riemann == 2 ? 1 : 0][na - 1], dim3(P.ntiles),
+                    dim3(FBJ, FBI), flds_bytes(na), (const double *)Uin, Uout, g, P, s->d_flag, part, S);
+    } else {
         const int solver = (p->riemann == 1 || p->riemann == 2) ? p->riemann : 0;
         const int std_rec = (p->limiter == 2 && p->use_flattening) ? 1 : 0;
         const KernelT kern = kernels[solver][std_rec];

@@ -461,6 +461,40 @@ __device__ __forceinline__ void trace_states(double r, double un, double ut, dou
 }
 #endif
 
+// The same tracing for a passive scalar X (a species mass fraction): eigenvalue un and a unit
+// eigenvector of its own (interface.py:145-149, 167-171), i.e. the reference state plus the one
+// wave that moves with the fluid -- term for term what trace_states() does to `ut`.
+// r, un, p: the cell's density, normal velocity and pressure (the sound speed of :122).
+__device__ __forceinline__ void trace_passive(double r, double un, double p, double X, double dX,
+                                              double gamma, double dtdx, double &lo, double &hi)
+{
+#if PYRO_FAST
+    double rcs;
+    const double cs = psqrt_r(gamma * p * prcp(r), rcs);
+    (void)rcs;
+    const double hh = 0.5 * dtdx;
+    const double e0 = un - cs, e3 = un + cs;
+    const double fl = fma(-hh, fmax(e3, 0.0), 0.5);
+    const double fr = fma(hh, fmin(e0, 0.0), 0.5);
+    const double w = hh * cs;
+    const bool pos = !__builtin_signbit(un);
+    const double gp = pos ? w : 0.0, gm = pos ? 0.0 : w;     // (= w - gp, without an operation to fuse)
+    hi = fma(gp, dX, fma(fl, dX, X));
+    lo = fma(-gm, dX, fma(-fr, dX, X));
+#else
+    const double dtdx4 = 0.25 * dtdx;
+    const double cs = psqrt(pdiv(gamma * p, r));
+    const double e0 = un - cs, e1 = un, e3 = un + cs;
+    const double fl = 0.5 * (1.0 - dtdx * fmax(e3, 0.0));
+    const double fr = 0.5 * (1.0 + dtdx * fmin(e0, 0.0));
+    const double s1 = copysign(1.0, e1);
+    const double bl = dtdx4 * (e3 - e1) * (s1 + 1.0) * dX;     // :193-201 with l . dq = dX
+    const double br = dtdx4 * (e0 - e1) * (1.0 - s1) * dX;
+    hi = (X + fl * dX) + bl;
+    lo = (X - fr * dX) + br;
+#endif
+}
+
 // Wave-speed estimate, compressible/riemann.py:596-678 (quirk: S_r uses
 // (gamma+1)/(2/gamma), :675)
 // gamma and the uniform quotients of it the HLLC solver uses, evaluated once
@@ -576,6 +610,22 @@ __device__ __forceinline__ ConsN cons_flux_n(const ConsN &U, double gamma, bool 
 // conserved form is also at hand
 struct FaceQ { double un, ut, p; };
 
+// What a passive scalar needs from the HLLC / HLLC_lm solve of its face (passive_flux() below):
+// the region of the wave fan the face lies in and that region's speeds.  The solvers fill it
+// where a caller hands one over (the record's TYPE decides at compile time: every other caller's
+// instance of the solver is the code it was); nothing of the hydro flux depends on it.
+// region: 0 right state, 1 right star state, 2 left star state, 3 left state
+struct NoUpwind { static constexpr bool on = false; };
+struct FaceUpwind {
+    static constexpr bool on = true;
+    int region;
+    double un;       // normal velocity of the region's outer state as consFlux takes it
+    double S;        // star regions: the outer wave's speed (S_r / S_l)
+    double f;        // ... HLLC: the star density rho (S - un) / (S - S_c)
+    double Sc, den;  // ... HLLC_lm: the contact speed and S - S_c
+    double sp0;      // ... HLLC_lm: S p* D with D = 0 (riemann.py:1005-1009)
+};
+
 // HAVEQ (fast build only): the primitive face states ql / qr are given (the
 // characteristic tracing produced them; prim_to_cons turned them into Ul / Ur),
 // so velocities and pressure are not recovered from the conserved states again.
@@ -642,9 +692,10 @@ __device__ __forceinline__ void estimate_wave_speed_fast(double rho_l, double u_
     }
 }
 
-template <bool HAVEQ, class KT>
+template <bool HAVEQ, class KT, class UP = NoUpwind>
 __device__ __forceinline__ ConsN hllc_flux_impl(const ConsN &Ul, const ConsN &Ur, const FaceQ &ql,
-                                                const FaceQ &qr, const KT &K, bool normal_is_x)
+                                                const FaceQ &qr, const KT &K, bool normal_is_x,
+                                                UP *up = nullptr)
 {
     (void)normal_is_x;
     const double gamma = K.g();
@@ -697,15 +748,17 @@ __device__ __forceinline__ ConsN hllc_flux_impl(const ConsN &Ul, const ConsN &Ur
         return F;
     };
     // riemann.py:784-856: S_r <= 0 | S_c <= 0 < S_r | S_l < 0 < S_c | else
+    if constexpr (UP::on) up->region = (S_r <= 0.0) ? 0 : (S_c <= 0.0) ? 1 : (S_l < 0.0) ? 2 : 3;
     if (__builtin_expect(S_r <= 0.0, 0)) return outer(Ur, un_r, ut_r, pf_r);
     if (S_c <= 0.0) return star(un_r, ut_r, p_r, Ur.E, S_r, d_r, a_r);
     if (__builtin_expect(S_l < 0.0, 1)) return star(un_l, ut_l, p_l, Ul.E, S_l, d_l, a_l);
     return outer(Ul, un_l, ut_l, pf_l);
 }
 #else
-template <bool HAVEQ, class KT>
+template <bool HAVEQ, class KT, class UP = NoUpwind>
 __device__ __forceinline__ ConsN hllc_flux_impl(const ConsN &Ul, const ConsN &Ur, const FaceQ &ql,
-                                                const FaceQ &qr, const KT &K, bool normal_is_x)
+                                                const FaceQ &qr, const KT &K, bool normal_is_x,
+                                                UP *up = nullptr)
 {
     const double gamma = K.g();
     const double smallc = 1.e-10, smallp = 1.e-10;
@@ -755,6 +808,7 @@ __device__ __forceinline__ ConsN hllc_flux_impl(const ConsN &Ul, const ConsN &Ur
     ConsN F;
     if (S_r <= 0.0) {
         F = side_flux(Ur, un_r, pf_r);
+        if constexpr (UP::on) { up->region = 0; up->un = (Ur.d != 0.0) ? un_r : 0.0; }
     } else if (S_c <= 0.0 && 0.0 < S_r) {
 #if PYRO_FAST && !defined(PYRO_EMU)
         const double a = rho_r * (S_r - un_r), b = S_r - S_c;
@@ -774,6 +828,7 @@ __device__ __forceinline__ ConsN hllc_flux_impl(const ConsN &Ul, const ConsN &Ur
         F.mn = F.mn + S_r * (Us.mn - Ur.mn);
         F.mt = F.mt + S_r * (Us.mt - Ur.mt);
         F.E = F.E + S_r * (Us.E - Ur.E);
+        if constexpr (UP::on) { up->region = 1; up->un = (Ur.d != 0.0) ? un_r : 0.0; up->S = S_r; up->f = f; }
     } else if (S_l < 0.0 && 0.0 < S_c) {
 #if PYRO_FAST && !defined(PYRO_EMU)
         const double a = rho_l * (S_l - un_l), b = S_l - S_c;
@@ -793,18 +848,20 @@ __device__ __forceinline__ ConsN hllc_flux_impl(const ConsN &Ul, const ConsN &Ur
         F.mn = F.mn + S_l * (Us.mn - Ul.mn);
         F.mt = F.mt + S_l * (Us.mt - Ul.mt);
         F.E = F.E + S_l * (Us.E - Ul.E);
+        if constexpr (UP::on) { up->region = 2; up->un = (Ul.d != 0.0) ? un_l : 0.0; up->S = S_l; up->f = f; }
     } else {
         F = side_flux(Ul, un_l, pf_l);
+        if constexpr (UP::on) { up->region = 3; up->un = (Ul.d != 0.0) ? un_l : 0.0; }
     }
     return F;
 }
 #endif
-template <class KT>
+template <class KT, class UP = NoUpwind>
 __device__ __forceinline__ ConsN hllc_flux(const ConsN &Ul, const ConsN &Ur, const KT &K,
-                                           bool normal_is_x)
+                                           bool normal_is_x, UP *up = nullptr)
 {
     const FaceQ none{0.0, 0.0, 0.0};
-    return hllc_flux_impl<false, KT>(Ul, Ur, none, none, K, normal_is_x);
+    return hllc_flux_impl<false, KT, UP>(Ul, Ur, none, none, K, normal_is_x, up);
 }
 
 
@@ -813,9 +870,9 @@ __device__ __forceinline__ ConsN hllc_flux(const ConsN &Ul, const ConsN &Ur, con
 // chi = min(1, max|v| / max c), and the star fluxes are written in the
 // (S_c (S U - F) + S p* D) / (S - S_c) form with D = (0, S_c, 1, 0) in
 // (density, energy, normal momentum, transverse momentum).
-template <class KT>
+template <class KT, class UP = NoUpwind>
 __device__ __forceinline__ ConsN hllc_lm_flux(const ConsN &Ul, const ConsN &Ur, const KT &K,
-                                              bool normal_is_x)
+                                              bool normal_is_x, UP *up = nullptr)
 {
     const double gamma = K.g();
     const double smallc = 1.e-10, smallp = 1.e-10;
@@ -842,6 +899,17 @@ __device__ __forceinline__ ConsN hllc_lm_flux(const ConsN &Ul, const ConsN &Ur, 
     const double phi = chi * (2.0 - chi);
     const double pstar = 0.5 * (p_l + p_r) + 0.5 * phi * (rho_l * (S_l - un_l) * (S_c - un_l) +
                                                           rho_r * (S_r - un_r) * (S_c - un_r));
+    if constexpr (UP::on) {
+        // (the velocities consFlux takes: zero where the density is, riemann.py:1133-1137)
+        const double cu_l = (Ul.d != 0.0) ? un_l : 0.0, cu_r = (Ur.d != 0.0) ? un_r : 0.0;
+        up->Sc = S_c;
+        if (S_r <= 0.0) { up->region = 0; up->un = cu_r; }
+        else if (S_c <= 0.0 && 0.0 < S_r) {
+            up->region = 1; up->un = cu_r; up->S = S_r; up->den = S_r - S_c; up->sp0 = S_r * pstar * 0.0;
+        } else if (S_l < 0.0 && 0.0 < S_c) {
+            up->region = 2; up->un = cu_l; up->S = S_l; up->den = S_l - S_c; up->sp0 = S_l * pstar * 0.0;
+        } else { up->region = 3; up->un = cu_l; }
+    }
     if (S_r <= 0.0) return cons_flux_n(Ur, gamma, normal_is_x);
     if (S_c <= 0.0 && 0.0 < S_r) {
         const ConsN Fr = cons_flux_n(Ur, gamma, normal_is_x);
@@ -1020,19 +1088,43 @@ __device__ __forceinline__ ConsN cgf_flux(const ConsN &Ul, const ConsN &Ur, doub
 }
 
 // compressible.riemann dispatch: SOLVER 0 = HLLC, 1 = CGF, 2 = HLLC_lm
-template <int SOLVER, class KT>
+// up: where the face lies in the wave fan, for the passive scalars (HLLC and HLLC_lm only)
+template <int SOLVER, class KT, class UP = NoUpwind>
 __device__ __forceinline__ ConsN riemann_face(const ConsN &Ul, const ConsN &Ur, const KT &K,
-                                              bool normal_is_x, bool wall_zero)
+                                              bool normal_is_x, bool wall_zero, UP *up = nullptr)
 {
     if (SOLVER == 1) return cgf_flux(Ul, Ur, K.g(), normal_is_x, wall_zero);
-    if (SOLVER == 2) return hllc_lm_flux(Ul, Ur, K, normal_is_x);
-    return hllc_flux(Ul, Ur, K, normal_is_x);
+    if (SOLVER == 2) return hllc_lm_flux(Ul, Ur, K, normal_is_x, up);
+    return hllc_flux(Ul, Ur, K, normal_is_x, up);
 }
-template <int SOLVER>
+template <int SOLVER, class UP = NoUpwind>
 __device__ __forceinline__ ConsN riemann_face(const ConsN &Ul, const ConsN &Ur, double gamma,
-                                              bool normal_is_x, bool wall_zero)
+                                              bool normal_is_x, bool wall_zero, UP *up = nullptr)
 {
-    return riemann_face<SOLVER>(Ul, Ur, make_gask(gamma), normal_is_x, wall_zero);
+    return riemann_face<SOLVER>(Ul, Ur, make_gask(gamma), normal_is_x, wall_zero, up);
+}
+
+// Flux of a passive scalar's partial density (rho X: Xl, Xr on the two sides) through a face whose
+// hydro problem riemann_face() solved: the scalar rides on that solve -- no second Riemann problem.
+// Bit-faithful build: the reference's expressions, term for term (HLLC riemann.py:784-856 with the
+// star states of :809-811, :838-840; HLLC_lm :985-1013; consFlux :1162-1163, :1176-1177).
+// Contracted build: every one of those forms is Fd X / rho of the upwind side (Fd: the mass
+// flux of the same face), which is what it evaluates.  Linear in X either way.
+template <int SOLVER>
+__device__ __forceinline__ double passive_flux(const FaceUpwind &w, double Fd, double rho_l, double rho_r,
+                                               double Xl, double Xr)
+{
+    const bool right = w.region <= 1;
+    const double X = right ? Xr : Xl, rho = right ? rho_r : rho_l;
+#if PYRO_FAST
+    return Fd * (X * prcp(rho));
+#else
+    (void)Fd;
+    const double FX = X * w.un;                      // consFlux of the outer state
+    if (w.region == 0 || w.region == 3) return FX;
+    if (SOLVER == 2) return pdiv(w.Sc * (w.S * X - FX) + w.sp0, w.den);
+    return FX + w.S * (pdiv(w.f * X, rho) - X);
+#endif
 }
 
 // Sponge, compressible/simulation.py:164-184 and :427-441 (acts on every

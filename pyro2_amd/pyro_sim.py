@@ -26,7 +26,7 @@ from .util.runparams import RuntimeParameters, _get_val
 valid_solvers = ["advection", "burgers", "compressible", "compressible_rk", "diffusion", "swe",
                  "incompressible", "incompressible_viscous", "burgers_viscous", "compressible_fv4",
                  "compressible_sdc", "lm_atm", "advection_nonuniform", "advection_rk", "advection_fv4",
-                 "advection_weno"]
+                 "advection_weno", "compressible_react"]
 # a solver that keeps its inputs files in another solver's problem directory
 problem_home = {"compressible_rk": "compressible", "compressible_fv4": "compressible",
                 "compressible_sdc": "compressible", "advection_rk": "advection",

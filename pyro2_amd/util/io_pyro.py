@@ -9,6 +9,20 @@ from ..mesh import boundary as bnd
 from ..mesh.patch import Cartesian2d, CellCenterData2d, SphericalPolar
 
 
+def _state_order(names, solver_name):
+    """the variables of a file in the order the solver registered them, where that matters: a
+    compressible state with passive scalars keeps density, energy and the momenta in front of
+    them (compressible.Variables counts on it; the file lists its groups by name), the scalars in
+    the order the solver names (compressible_react: fuel, ash), any other by name"""
+    hydro = ["density", "energy", "x-momentum", "y-momentum"]
+    if len(names) <= 4 or any(h not in names for h in hydro):
+        return names
+    if isinstance(solver_name, bytes):
+        solver_name = solver_name.decode()
+    known = [n for n in {"compressible_react": ["fuel", "ash"]}.get(solver_name, []) if n in names]
+    return hydro + known + [n for n in names if n not in hydro + known]
+
+
 def read(filename):
     from . import h5lite
     with h5lite.open_file(filename, "r") as f:
@@ -20,7 +34,7 @@ def read(filename):
         grid_class = SphericalPolar if g.get("coord_type", 0) == 1 else Cartesian2d   # io_pyro.py:52-60
         myg = grid_class(int(g["nx"]), int(g["ny"]), ng=int(g["ng"]), xmin=g["xmin"],
                          xmax=g["xmax"], ymin=g["ymin"], ymax=g["ymax"])
-        names = list(f["state"])
+        names = _state_order(list(f["state"]), solver_name)
         dt, dt_old = f.attrs.get("dt"), f.attrs.get("dt_old")
         params = dict(f["runtime parameters"].attrs.items()) \
             if "runtime parameters" in f else {}
