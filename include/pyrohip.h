@@ -681,6 +681,31 @@ int pyrohip_state_from_centers(pyrohip_state *s, int var, double dx, double dy);
 int pyrohip_comp_sdc_update(pyrohip_state *dst, const pyrohip_state *src,
                             const pyrohip_state *k, int slot_new, int slot_old,
                             const int *slots_q, const double *cq, double dt);
+/* Up to max_steps steps of the compressible_fv4 / compressible_sdc driver loop (ghost fill, CFL
+   minimum of pyrohip_comp_rk_dt, dt policy, step) without a host round trip per step or per
+   stage, as pyrohip_comp_rk_evolve: one synchronisation at the end, bit-identical to the same
+   steps taken singly (pyrohip_comp_fv4_rhs + pyrohip_state_lincomb / pyrohip_comp_sdc_update +
+   pyrohip_fill_bc) in both arithmetic builds.
+   fv4: stage (4 planes) and k (>= 4 nstages planes) are scratch states of y's geometry, a / b the
+   Butcher tableau as for pyrohip_comp_rk_step.  sdc: node1 / node2 (4 planes each) and k (>= 20
+   planes: five slots of A).  The scratch states must differ from y and from each other; a heating
+   profile is read from the state a right-hand side is taken of (set it on y, stage, node1, node2).
+   Carried: a single Cartesian domain with outflow / reflect / periodic sides, nx, ny >= ng,
+   gravity, the sponge, a heating profile.  Refused with "device-side stepping:" in the message:
+   hse / ambient / ramp sides, a slab, well_balanced, a host-evaluated source, a tracer set
+   (the _p forms of DESIGN.md 15.1 exist to say so).
+   PYROHIP_ERR_STATE: a stage or node state failed cons_to_prim's assert; *steps_done steps were
+   taken, y is the state before the failing step as that single step leaves it (the density
+   floor of its first right-hand side written, its own ghost cells filled), policy stands there. */
+int pyrohip_comp_fv4_evolve(pyrohip_state *y, const pyrohip_comp_params *p,
+                            pyrohip_state *stage, pyrohip_state *k, int nstages,
+                            const double *a, const double *b, double cfl,
+                            pyrohip_dt_policy *policy, int max_steps, int *steps_done,
+                            double *dts_out);
+int pyrohip_comp_sdc_evolve(pyrohip_state *y, const pyrohip_comp_params *p,
+                            pyrohip_state *node1, pyrohip_state *node2, pyrohip_state *k,
+                            double cfl, pyrohip_dt_policy *policy, int max_steps,
+                            int *steps_done, double *dts_out);
 
 /* ---- shallow water (pyro/swe) -------------------------
    state: 4 variables height, x-momentum, y-momentum, fuel (ng >= 4).
@@ -941,6 +966,19 @@ int pyrohip_bg_evolve_p(pyrohip_state *s, int iu, int iv, double dx, double dy, 
                         double cfl, pyrohip_dt_policy *policy, int max_steps, int *steps_done,
                         double *dts_out, pyrohip_particles *particles,
                         const pyrohip_particle_params *pparams);
+/* compressible_fv4 / compressible_sdc carry no set: with particles != NULL these refuse
+   ("device-side stepping:", the driver then steps singly); with NULL they are the calls above */
+int pyrohip_comp_fv4_evolve_p(pyrohip_state *y, const pyrohip_comp_params *p,
+                              pyrohip_state *stage, pyrohip_state *k, int nstages,
+                              const double *a, const double *b, double cfl,
+                              pyrohip_dt_policy *policy, int max_steps, int *steps_done,
+                              double *dts_out, pyrohip_particles *particles,
+                              const pyrohip_particle_params *pparams);
+int pyrohip_comp_sdc_evolve_p(pyrohip_state *y, const pyrohip_comp_params *p,
+                              pyrohip_state *node1, pyrohip_state *node2, pyrohip_state *k,
+                              double cfl, pyrohip_dt_policy *policy, int max_steps,
+                              int *steps_done, double *dts_out, pyrohip_particles *particles,
+                              const pyrohip_particle_params *pparams);
 
 /* ---- multi-GPU: x-slab decomposition, one process per GPU, RCCL -------- */
 #define PYROHIP_UNIQUE_ID_BYTES 128

@@ -280,6 +280,14 @@ _PROTOS = {
                               _IP, _DP, _VP, C.POINTER(ParticleParams)],
     "pyrohip_comp_rk_evolve_p": [_VP, C.POINTER(CompParams), _VP, C.c_int, _DP, _DP, C.c_double,
                                  C.POINTER(DtPolicyC), C.c_int, _IP, _DP, _VP, C.POINTER(ParticleParams)],
+    "pyrohip_comp_fv4_evolve": [_VP, C.POINTER(CompParams), _VP, _VP, C.c_int, _DP, _DP, C.c_double,
+                                C.POINTER(DtPolicyC), C.c_int, _IP, _DP],
+    "pyrohip_comp_fv4_evolve_p": [_VP, C.POINTER(CompParams), _VP, _VP, C.c_int, _DP, _DP, C.c_double,
+                                  C.POINTER(DtPolicyC), C.c_int, _IP, _DP, _VP, C.POINTER(ParticleParams)],
+    "pyrohip_comp_sdc_evolve": [_VP, C.POINTER(CompParams), _VP, _VP, _VP, C.c_double,
+                                C.POINTER(DtPolicyC), C.c_int, _IP, _DP],
+    "pyrohip_comp_sdc_evolve_p": [_VP, C.POINTER(CompParams), _VP, _VP, _VP, C.c_double,
+                                  C.POINTER(DtPolicyC), C.c_int, _IP, _DP, _VP, C.POINTER(ParticleParams)],
     "pyrohip_swe_evolve_p": [_VP, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_double,
                              C.POINTER(DtPolicyC), C.c_int, _IP, _DP, _VP, C.POINTER(ParticleParams)],
     "pyrohip_bg_evolve_p": [_VP, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double,

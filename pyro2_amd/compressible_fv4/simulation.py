@@ -5,10 +5,13 @@ ghost fill, pyrohip_comp_fv4_rhs (density floor, averages -> centres, primitives
 limited 4th-order face states, CGF on primitive states, face-centred fluxes, artificial
 viscosity, sources at centres brought back to averages, sponge) -- one launch of the tile
 kernel behind a light check launch; the stage starts and the final update are
-pyrohip_state_lincomb launches.  The data are cell averages (mesh/fv.py FV2d)."""
+pyrohip_state_lincomb launches.  The data are cell averages (mesh/fv.py FV2d).  Batches of
+steps run on the device without a host round trip per stage (evolve_many:
+pyrohip_comp_fv4_evolve)."""
 from .. import device
 from ..compressible_rk.simulation import Simulation as RKSimulation
 from ..mesh import fv
+from ..mesh import integration
 from ..mesh import patch
 from ..util import msg
 
@@ -80,5 +83,67 @@ class Simulation(RKSimulation):
         """the one-call Runge-Kutta step is compressible_rk's scheme: never for this one"""
         return False
 
+    def _own_step(self):
+        """the evolve / substep this class steps with: a subclass that replaces either steps singly"""
+        return RKSimulation.evolve, Simulation.substep
+
     def can_evolve_many(self):
-        return False
+        """batches of steps on the device (pyrohip_comp_fv4_evolve): a single
+        Cartesian domain with outflow / reflect / periodic sides and at least ng cells each way,
+        gravity, the sponge and a heating profile included; no tracer set, nothing watching the
+        data, no host-side boundary callback, the solver's own evolve and substep"""
+        cc = self.cc_data
+        if cc._views_alive() or self.particles is not None or cc.slab is not None:
+            return False
+        if getattr(self, "_device_stepping_refused", False):
+            return False
+        if (type(self).evolve, type(self).substep) != self._own_step():
+            return False
+        simple = ("outflow", "reflect-even", "reflect-odd", "periodic")
+        if not all(b in simple for n in cc.names for b in cc.BCs[n].sides()):
+            return False
+        if any(cc._has_host_bc(n) for n in cc.names):
+            return False
+        g = cc.grid
+        return g.nx >= g.ng and g.ny >= g.ng
+
+    def _with_heating(self, states):
+        """the heating profile on the states a right-hand side is taken of, as evolve() sets it"""
+        h = self._heating()
+        if h is not None:
+            for st in states:
+                if not getattr(st, "_heating_set", False):
+                    st.set_heating(h[1])
+                    st._heating_set = True
+
+    def _loop_start(self):
+        st = self._device_state()
+        self.cc_data.take_pending_fill()     # (the loop fills the state's ghost cells itself)
+        return st
+
+    def evolve_many(self, nsteps):
+        """up to nsteps of fill_BC_all + compute_timestep + evolve on the device: no host round
+        trip per step or per stage.  Returns the time steps taken."""
+        method = self.rp.get_param("compressible.temporal_method")
+        nst = len(integration.b[method])
+
+        def call(st, pol, cfl, n, particles):
+            if self._rk_scratch is not None and self._rk_scratch[1].nvar != 4 * nst:
+                self._rk_scratch = None
+            rk = integration.RKIntegrator(self.cc_data.t, 0.0, method=method)
+            self._rk_scratch = rk.set_start(st, self._rk_scratch)
+            stage, k = self._rk_scratch
+            self._with_heating([stage])
+            return st.comp_fv4_evolve(self._params(), stage, k, integration.a[method], integration.b[method],
+                                      cfl, pol, n, particles=particles)
+        n0, entered = self.n, True
+        try:
+            dts = self._evolve_by_device_policy(nsteps, self._loop_start, call, refusable=True)
+            entered = self.n > n0
+            return dts
+        finally:
+            # evolve() asks for the fill of its first stage itself, and where fill_BC_all defers
+            # fills that request outlives the step: the host then sees the new state's own images
+            cc = self.cc_data
+            if entered and cc.lazy_fill and cc._lazy_fill_ok():
+                cc.fill_BC_all()

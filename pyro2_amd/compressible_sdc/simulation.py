@@ -2,7 +2,8 @@
 pyro/compressible_sdc/simulation.py:9-127.  One step = 9 right-hand sides
 (pyrohip_comp_fv4_rhs) and 8 node updates (pyrohip_comp_sdc_update, each followed by a
 ghost fill).  The advective terms A of the nodes are slots of one device k-state: the old
-and new iterations swap slots instead of copying."""
+and new iterations swap slots instead of copying.  Batches of steps run on the device without a
+host round trip per right-hand side (evolve_many: pyrohip_comp_sdc_evolve)."""
 from .. import device
 from ..compressible_fv4.simulation import Simulation as FV4Simulation
 from ..util import msg
@@ -65,6 +66,19 @@ class Simulation(FV4Simulation):
         cc.t += self.dt
         self.n += 1
         tm.end()
+
+    def _own_step(self):
+        return Simulation.evolve, FV4Simulation.substep
+
+    def evolve_many(self, nsteps):
+        """up to nsteps of fill_BC_all + compute_timestep + evolve on the device
+        (pyrohip_comp_sdc_evolve): the 9 right-hand sides and 8 node updates of every step without a
+        host round trip.  Returns the time steps taken."""
+        def call(st, pol, cfl, n, particles):
+            (n1, n2), k = self._scratch(st)
+            self._with_heating([n1, n2])
+            return st.comp_sdc_evolve(self._params(), n1, n2, k, cfl, pol, n, particles=particles)
+        return self._evolve_by_device_policy(nsteps, self._loop_start, call, refusable=True)
 
     def sdc_integral(self, m_start, m_end, As):
         """host form of the quadrature (analysis; the step runs pyrohip_comp_sdc_update)"""

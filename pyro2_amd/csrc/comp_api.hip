@@ -40,6 +40,15 @@ int comp_rk_step_wave(pyrohip_state *, const pyrohip_comp_params *, pyrohip_stat
 int comp_rk_cfl_min_device(pyrohip_state *, const pyrohip_comp_params *, const double **);
 int comp_wave_geometry(int, int, int, int, int, int *);
 int sph_wave_geometry(int, int, int, int, int, int *);
+int comp_fv4_rhs_run(pyrohip_state *, const pyrohip_comp_params *, pyrohip_state *, int, const StepScalars *, int *);
+int fv4_stage_start(pyrohip_state *, const pyrohip_state *, const pyrohip_state *, const double *, int,
+                    const StepScalars *);
+int fv4_final_parts(const Geom &);
+int fv4_final(pyrohip_state *, const pyrohip_state *, const pyrohip_state *, const double *, int,
+              const pyrohip_comp_params *, const StepScalars *, double *);
+int fv4_sdc_node(pyrohip_state *, const pyrohip_state *, const pyrohip_state *, int, int, const int *,
+                 const double *, const StepScalars *, const int *);
+int fv4_copy_frame(pyrohip_state *, const double *);
 int state_from_centers(pyrohip_state *, int, double, double, double *);
 int comp_sdc_update(pyrohip_state *, const pyrohip_state *, const pyrohip_state *, int, int, const int *,
                     const double *, double);
@@ -47,6 +56,7 @@ int comp_sdc_update(pyrohip_state *, const pyrohip_state *, const pyrohip_state 
 namespace fastm {
 int comp_rk_rhs(pyrohip_state *, const pyrohip_comp_params *, pyrohip_state *, int);
 int comp_fv4_rhs(pyrohip_state *, const pyrohip_comp_params *, pyrohip_state *, int);
+int comp_fv4_rhs_run(pyrohip_state *, const pyrohip_comp_params *, pyrohip_state *, int, const StepScalars *, int *);
 int comp_rk_rhs_wave(pyrohip_state *, const pyrohip_comp_params *, pyrohip_state *, int);
 int comp_rk_step_wave(pyrohip_state *, const pyrohip_comp_params *, pyrohip_state *, int, const double *,
                       const double *, double, const StepScalars *, const double **);
@@ -744,6 +754,187 @@ int pyrohip_comp_sdc_update(pyrohip_state *dst, const pyrohip_state *src, const 
     dst->next_cfl_min = -1.0;
     dst->ghost_by_rules = false;
     return 0;
+}
+
+}  // extern "C"
+
+// ---- compressible_fv4 / compressible_sdc: batches of steps on the device ----
+// What both loops ask of the state that is stepped and of a state that stands beside it (stage state,
+// node states, the k state); `fn` names the entry point in the messages.
+static int check_fv4_run(pyrohip_state *y, const pyrohip_comp_params *p, const char *fn)
+{
+    PYRO_TRY(check_comp(y, p));
+    PYRO_REQUIRE(y->g.ng == 4, "compressible_fv4 needs ng = 4 (the reference's grid)");
+    PYRO_REQUIRE(!y->sph, "compressible_fv4 has no SphericalPolar geometry terms");
+    if (p->do_sponge)
+        PYRO_REQUIRE(p->sponge_rho_begin > p->sponge_rho_full,
+                     "sponge_rho_begin must exceed sponge_rho_full (simulation.py:172)");
+    const char *why = nullptr;
+    if (p->well_balanced) why = "compressible.well_balanced is not carried";
+    else if (y->user_bc || y->ramp_bc) why = "hse / ambient / ramp sides are not carried";
+    else if (y->nb_set || y->ctx->global_cfl) why = "a slab of a decomposed run is not carried";
+    else if (y->ext_old) why = "a host-evaluated source is not carried";
+    else if (!same_index_map_kinds(y, false)) why = "outflow / reflect / periodic sides only";
+    else if (y->g.nx < y->g.ng || y->g.ny < y->g.ng) why = "fewer interior cells than ghost cells in a direction";
+    if (why) {
+        set_error(std::string(fn) + ": device-side stepping: " + why);
+        return PYROHIP_ERR_ARG;
+    }
+    return 0;
+}
+static int check_fv4_beside(const pyrohip_state *y, const pyrohip_state *o, int planes, const char *what)
+{
+    PYRO_REQUIRE(o && o->ctx == y->ctx, std::string(what) + " missing or on another context");
+    PYRO_REQUIRE(o != y && o->d != y->d,
+                 std::string(what) + " must not be the state that is stepped: its cells are read while the "
+                                     "other one's are written");
+    PYRO_REQUIRE(o->g.nx == y->g.nx && o->g.ny == y->g.ny && o->g.ng == y->g.ng && o->nvar >= planes,
+                 std::string(what) + " must have the geometry of the state and enough planes");
+    return 0;
+}
+// the run both loops share: open, per iteration the policy and the solver's step, close.  step(S, part)
+// enqueues one step that ends with fv4_final (new state and ghost frame in the other buffer, CFL
+// partials in part); last_frame: the array whose ghost frame the state handed back carries -- nullptr:
+// the other buffer's (the state before the last step), else that array's (the last SDC node)
+template <class Step>
+static int fv4_run(pyrohip_state *s, const pyrohip_comp_params *p, double cfl, pyrohip_dt_policy *pol,
+                   int max_steps, int *steps_done, double *dts_out, const double *last_frame, Step step)
+{
+    pyrohip_ctx *c = s->ctx;
+    PYRO_REQUIRE(pol && steps_done && max_steps >= 1, "NULL argument / max_steps must be positive");
+    PYRO_TRY(state_alt(s));
+    // (as much as comp_rk_cfl_min_device asks for: the buffer must not move while the run is enqueued)
+    const int nparts = exact::fv4_final_parts(s->g);
+    PYRO_TRY(c->reduce.ensure(((size_t)(nparts > 65536 ? nparts : 65536) + 2 * 8 * 128 + 256 + 2) *
+                              sizeof(double)));    // (256: reduce.h's kMinStageBlocks)
+    double *part = (double *)c->reduce.p;
+    EvolveRun r;
+    // the final update writes the ghost frame of the state it leaves and stores nothing on an inactive
+    // iteration: the close neither rebuilds a frame nor fills the state after an invalid step
+    r.own_frames = true;
+    PYRO_TRY(evolve_open(r, s, pol, cfl, 1, p->gamma, p->dx, p->dy, max_steps, false));
+    int rc = 0;
+    for (int m = 0; m < max_steps && rc == 0; m++) {
+        bool frame_done = false;
+        if (m == 0) {
+            // the CFL minimum of the state as handed over: whole array, ghost cells filled (or the one
+            // the previous call's last step left)
+            rc = evolve_fill(r, false, &frame_done);
+            if (r.min_cached) r.dmin = &s->d_scal->min0;
+            else if (rc == 0) rc = exact::comp_rk_cfl_min_device(s, p, &r.dmin);
+            if (rc == 0) rc = evolve_policy(r, 0);
+        } else {
+            rc = evolve_between(r, m, false, false, &frame_done);
+        }
+        if (rc) break;
+        rc = step(r.d_scal, part);
+        // the next policy call takes the minimum of the partials itself and keeps it in the step scalars
+        // (min0), which the close reads back anyway
+        r.pend = part;
+        r.npend = nparts;
+        r.dmin = &s->d_scal->min0;
+        state_swap_alt(s);
+    }
+    PYRO_TRY(rc);
+    rc = evolve_close(r, pol, steps_done, dts_out, false, false);
+    s->cfl_is_global = false;
+    if (rc == 0 && *steps_done >= 1)
+        PYRO_TRY(exact::fv4_copy_frame(s, last_frame ? last_frame : s->alt_base + geom_lead(s->g)));
+    // the minimum of the last launch belongs to the state only if that launch advanced it
+    if (rc == 0 && *steps_done == max_steps) s->next_cfl_min = r.H.min0;
+    return rc;
+}
+static int fv4_rhs_run(pyrohip_state *st, const pyrohip_comp_params *p, pyrohip_state *k, int slot,
+                       const StepScalars *S, int *flag)
+{
+    return p->fast_math ? fastm::comp_fv4_rhs_run(st, p, k, slot, S, flag)
+                        : exact::comp_fv4_rhs_run(st, p, k, slot, S, flag);
+}
+
+extern "C" {
+
+// Up to max_steps steps of the compressible_fv4 driver loop (pyro_sim.py:241-281 with
+// compressible_rk/simulation.py:46-104 and the right-hand side of compressible_fv4) under the run
+// protocol of DESIGN.md 3.6.1.  stage / k: the states RKIntegrator.set_start makes.  particles: none is
+// carried (refused).
+int pyrohip_comp_fv4_evolve_p(pyrohip_state *y, const pyrohip_comp_params *p, pyrohip_state *stage,
+                              pyrohip_state *k, int nstages, const double *a, const double *b, double cfl,
+                              pyrohip_dt_policy *pol, int max_steps, int *steps_done, double *dts_out,
+                              pyrohip_particles *particles, const pyrohip_particle_params *)
+{
+    PYRO_TRY(check_rk(y, p, k, nstages, a, b));
+    PYRO_TRY(check_fv4_beside(y, k, 4 * nstages, "the k state"));
+    PYRO_TRY(check_fv4_beside(y, stage, 4, "the stage state"));
+    PYRO_REQUIRE(stage != k && stage->d != k->d, "k must not be the stage state");
+    PYRO_REQUIRE(!particles, "device-side stepping: compressible_fv4 carries no tracer particles");
+    PYRO_TRY(check_fv4_run(y, p, __func__));
+    return fv4_run(y, p, cfl, pol, max_steps, steps_done, dts_out, nullptr,
+                   [&](const StepScalars *S, double *part) -> int {
+                       PYRO_TRY(fv4_rhs_run(y, p, k, 0, S, y->d_flag));
+                       for (int st = 1; st < nstages; st++) {
+                           PYRO_TRY(exact::fv4_stage_start(stage, y, k, a + st * nstages, st, S));
+                           PYRO_TRY(fv4_rhs_run(stage, p, k, st, S, y->d_flag));
+                       }
+                       return exact::fv4_final(y, y, k, b, nstages, p, S, part);
+                   });
+}
+
+int pyrohip_comp_fv4_evolve(pyrohip_state *y, const pyrohip_comp_params *p, pyrohip_state *stage,
+                            pyrohip_state *k, int nstages, const double *a, const double *b, double cfl,
+                            pyrohip_dt_policy *pol, int max_steps, int *steps_done, double *dts_out)
+{
+    return pyrohip_comp_fv4_evolve_p(y, p, stage, k, nstages, a, b, cfl, pol, max_steps, steps_done, dts_out,
+                                     nullptr, nullptr);
+}
+
+// ... and of compressible_sdc (compressible_sdc/simulation.py:48-127): 9 right-hand sides and 8 node
+// updates per step.  node1 / node2 / k (5 slots of 4 planes): compressible_sdc.Simulation._scratch.
+int pyrohip_comp_sdc_evolve_p(pyrohip_state *y, const pyrohip_comp_params *p, pyrohip_state *node1,
+                              pyrohip_state *node2, pyrohip_state *k, double cfl, pyrohip_dt_policy *pol,
+                              int max_steps, int *steps_done, double *dts_out, pyrohip_particles *particles,
+                              const pyrohip_particle_params *)
+{
+    PYRO_TRY(check_comp(y, p));
+    PYRO_REQUIRE(y->g.ng == 4, "compressible_sdc needs ng = 4 (the reference's grid)");
+    PYRO_TRY(check_fv4_beside(y, k, 4 * 5, "the k state"));
+    PYRO_TRY(check_fv4_beside(y, node1, 4, "the state of node 1"));
+    PYRO_TRY(check_fv4_beside(y, node2, 4, "the state of node 2"));
+    PYRO_REQUIRE(node1 != node2 && node1->d != node2->d && node1->d != k->d && node2->d != k->d,
+                 "the node states and the k state must be three different states");
+    PYRO_REQUIRE(!particles, "device-side stepping: compressible_sdc carries no tracer particles");
+    PYRO_TRY(check_fv4_run(y, p, __func__));
+    // sdc_integral (simulation.py:20-36): dt/24 (c0 A_0 + c1 A_1 + c2 A_2) from node m to m + 1
+    static const double C[2][3] = {{5.0, 8.0, -1.0}, {-1.0, 8.0, 5.0}};
+    return fv4_run(y, p, cfl, pol, max_steps, steps_done, dts_out, (const double *)node2->d,
+                   [&](const StepScalars *S, double *part) -> int {
+                       pyrohip_state *U[3] = {y, node1, node2};
+                       PYRO_TRY(fv4_rhs_run(y, p, k, 0, S, y->d_flag));
+                       int old[3] = {0, 0, 0};          // A_kold[m] -> slot
+                       for (int it = 0; it < 4; it++) {
+                           int nw[3] = {0, 0, 0}, next_free = 1;
+                           for (int m = 0; m < 3; m++) {
+                               if (m > 0) {
+                                   while (next_free == old[1] || next_free == old[2]) next_free++;
+                                   nw[m] = next_free++;
+                                   PYRO_TRY(fv4_rhs_run(U[m], p, k, nw[m], S, y->d_flag));
+                               }
+                               if (m < 2)
+                                   PYRO_TRY(exact::fv4_sdc_node(U[m + 1], U[m], k, nw[m], old[m], old, C[m], S,
+                                                                y->d_flag));
+                           }
+                           old[1] = nw[1]; old[2] = nw[2];
+                       }
+                       // the new solution: the last node, floored by its right-hand side
+                       return exact::fv4_final(y, node2, k, nullptr, 0, p, S, part);
+                   });
+}
+
+int pyrohip_comp_sdc_evolve(pyrohip_state *y, const pyrohip_comp_params *p, pyrohip_state *node1,
+                            pyrohip_state *node2, pyrohip_state *k, double cfl, pyrohip_dt_policy *pol,
+                            int max_steps, int *steps_done, double *dts_out)
+{
+    return pyrohip_comp_sdc_evolve_p(y, p, node1, node2, k, cfl, pol, max_steps, steps_done, dts_out, nullptr,
+                                     nullptr);
 }
 
 int pyrohip_comp_stage_dump(pyrohip_state *s, int stage_id, double *out)

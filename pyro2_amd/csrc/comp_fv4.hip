@@ -21,11 +21,18 @@
 // it: the density floor of the interior (written back, like clean_state) and the two
 // cons_to_prim asserts, so that an invalid state leaves k untouched.
 //
+// Batches of steps on the device (pyrohip_comp_fv4_evolve / pyrohip_comp_sdc_evolve):
+// comp_fv4_rhs_run is the two launches without the host side of the flag; k_fv4_stage_start,
+// k_fv4_sdc_node and k_fv4_final form a stage / node / new state AND its ghost cells in one launch,
+// with dt from the run's step scalars (the bit-faithful part at the end of the file: one instance
+// serves both builds).
+//
 // This file is compiled twice: PYRO_FAST=0 (-ffp-contract=off, the bit-faithful build) and
 // PYRO_FAST=1 (-ffp-contract=fast); pyrohip_comp_fv4_rhs dispatches on fast_math.
 #include "common.h"
 #include "hydro.h"
 #include "fv4_limit.h"
+#include "reduce.h"
 
 #ifndef PYRO_FAST
 #define PYRO_FAST 0
@@ -107,9 +114,12 @@ struct Lds {
 // keep their density) and the two cons_to_prim asserts of fluxes.py:80-81 (U_avg and the masked
 // U_cc, interior only).
 // flag |= 1 on an invalid state.
+// S: the step scalars of a device-side run (nullptr: a single right-hand side) -- an iteration that
+// does not advance (past tmax, after an invalid state) neither floors nor judges what it is given.
 __global__ __launch_bounds__(256) void k_fv4_prep(double *__restrict__ U, Geom g, FP P,
-                                                  int *__restrict__ flag)
+                                                  int *__restrict__ flag, const StepScalars *__restrict__ S)
 {
+    if (S != nullptr && S->active == 0) return;
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     const int i = blockIdx.y;
     if (j >= g.qy) return;
@@ -408,7 +418,13 @@ __global__ __launch_bounds__(NT) void k_fv4_rhs(const double *__restrict__ Ug, d
     }
 }
 
-int comp_fv4_rhs(pyrohip_state *s, const pyrohip_comp_params *p, pyrohip_state *kst, int slot)
+// The two launches of a right-hand side, nothing else: the flag is neither reset in front of them nor
+// read back behind them.  S: the step scalars of a device-side run (pyrohip_comp_fv4_evolve /
+// pyrohip_comp_sdc_evolve reset the flag once, at the open, and read it once, at the close); flag: the
+// flag word of the call -- the state's own, or in a run the one of the state that is stepped, whichever
+// stage or node state the right-hand side is taken of.
+int comp_fv4_rhs_run(pyrohip_state *s, const pyrohip_comp_params *p, pyrohip_state *kst, int slot,
+                     const StepScalars *S, int *flag)
 {
     pyrohip_ctx *c = s->ctx;
     const Geom &g = s->g;
@@ -420,18 +436,25 @@ int comp_fv4_rhs(pyrohip_state *s, const pyrohip_comp_params *p, pyrohip_state *
     P.use_flattening = p->use_flattening;
     P.sponge = p->do_sponge;
     P.rho_begin = p->sponge_rho_begin; P.rho_full = p->sponge_rho_full; P.tau = p->sponge_timescale;
-    PYRO_CHECK_HIP(hipMemsetAsync(s->d_flag, 0, sizeof(int), c->stream));
     PYRO_LAUNCH(c, "k_fv4_prep", k_fv4_prep, dim3((g.qy + 255) / 256, g.qx), dim3(256), 0, s->d, g, P,
-                s->d_flag);
+                flag, S);
     PYRO_CHECK_HIP(hipGetLastError());   // (a refused prep launch must not be lost behind the next)
     const dim3 grid((g.nx + TI - 1) / TI, (g.ny + TJ - 1) / TJ);
     PYRO_LAUNCH(c, "k_fv4_rhs", k_fv4_rhs, grid, dim3(NT), 0, (const double *)s->d,
-                kst->d + (size_t)(4 * slot) * g.plane, g, P, (const int *)s->d_flag);
+                kst->d + (size_t)(4 * slot) * g.plane, g, P, (const int *)flag);
     PYRO_CHECK_HIP(hipGetLastError());
+    s->next_cfl_min = -1.0;
+    return 0;
+}
+
+int comp_fv4_rhs(pyrohip_state *s, const pyrohip_comp_params *p, pyrohip_state *kst, int slot)
+{
+    pyrohip_ctx *c = s->ctx;
+    PYRO_CHECK_HIP(hipMemsetAsync(s->d_flag, 0, sizeof(int), c->stream));
+    PYRO_TRY(comp_fv4_rhs_run(s, p, kst, slot, nullptr, s->d_flag));
     PYRO_CHECK_HIP(hipMemcpyAsync(c->reduce_host, s->d_flag, sizeof(int), hipMemcpyDeviceToHost,
                                   c->stream));
     PYRO_CHECK_HIP(hipStreamSynchronize(c->stream));
-    s->next_cfl_min = -1.0;
     if (*(int *)c->reduce_host & 1) {
         set_error("invalid state: min(rho) <= 0 or min(e) <= 0 on the interior "
                   "(compressible/simulation.py:68-71, called by compressible_fv4/fluxes.py:80-81)");
@@ -498,6 +521,216 @@ int comp_sdc_update(pyrohip_state *dst, const pyrohip_state *src, const pyrohip_
     A.idt = dt / 24.0;
     PYRO_LAUNCH(dst->ctx, "k_sdc_update", k_sdc_update, dim3((g.ny + 255) / 256, g.nx, dst->nvar), dim3(256),
                 0, dst->d, (const double *)src->d, g, dst->nvar, A);
+    PYRO_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---- the step of a device-side run (pyrohip_comp_fv4_evolve / pyrohip_comp_sdc_evolve) -------------
+// Every state a right-hand side is taken of is formed AND ghost-filled by one launch: a thread per
+// cell of the array evaluates the update at the cell's image under the composite x-then-y index map
+// (array_indexer.py:163-274: x over all columns first, so a corner takes its value from an x ghost
+// cell; what k_fill_frame2 does), with the sign of reflect-odd.  The launches read the start state and
+// k and write another array, so a ghost cell never reads what another thread writes.  dt comes from
+// the run's step scalars; an iteration that does not advance, or a raised flag, stores nothing.
+struct Fv4Maps { BcMap mx[4], my[4]; };
+
+static Fv4Maps fv4_maps(const pyrohip_state *s)
+{
+    const Geom &g = s->g;
+    Fv4Maps M;
+    for (int n = 0; n < 4; n++) {
+        M.mx[n] = bc_map(g.ilo, g.ihi, g.ng, s->bc[n * 4 + 0], s->bc[n * 4 + 1], true);
+        M.my[n] = bc_map(g.jlo, g.jhi, g.ng, s->bc[n * 4 + 2], s->bc[n * 4 + 3], true);
+    }
+    return M;
+}
+
+// the interior cell whose value array cell (i, j) of variable n shows; *neg: with the other sign
+__device__ __forceinline__ size_t fv4_image(const Geom &g, const Fv4Maps &M, int n, int i, int j, bool *neg)
+{
+    const BcMap &mx = M.mx[n], &my = M.my[n];
+    const int si = bc_src(mx, i, g.ilo, g.ihi), sj = bc_src(my, j, g.jlo, g.jhi);
+    *neg = ((i < g.ilo && mx.odd_lo) || (i > g.ihi && mx.odd_hi)) !=
+           ((j < g.jlo && my.odd_lo) || (j > g.jhi && my.odd_hi));
+    return (size_t)si * g.pitch + sj;
+}
+
+__device__ __forceinline__ bool fv4_run_goes(const StepScalars *S, const int *flag)
+{
+    return S->active != 0 && *flag == 0;
+}
+
+// RKIntegrator.get_stage_start + the stage's ghost fill: dst = y + (dt c[0]) k_0 + (dt c[1]) k_1 + ...,
+// k_lincomb's terms in its order (ctx.hip), each coefficient the once-rounded product dt * c[s] the
+// host forms for pyrohip_state_lincomb; zero coefficients stay (0 * NaN is NaN)
+struct Fv4Coef { double c[4]; int n; };
+__global__ __launch_bounds__(256) void k_fv4_stage_start(double *__restrict__ dst, const double *__restrict__ y,
+                                                         const double *__restrict__ K, Geom g, Fv4Maps M,
+                                                         Fv4Coef lc, const StepScalars *__restrict__ S,
+                                                         const int *__restrict__ flag)
+{
+    if (!fv4_run_goes(S, flag)) return;
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    const int i = blockIdx.y, n = blockIdx.z;
+    if (j >= g.qy) return;
+    bool neg;
+    const size_t ks = fv4_image(g, M, n, i, j, &neg);
+    const double dt = S->dt;
+    double v = y[(size_t)n * g.plane + ks];
+    for (int s = 0; s < lc.n; s++) {
+        const double c = dt * lc.c[s];
+        v += c * K[(size_t)(4 * s + n) * g.plane + ks];
+    }
+    dst[(size_t)n * g.plane + (size_t)i * g.pitch + j] = neg ? -v : v;
+}
+
+// compressible_rk/simulation.py:46-56 for one cell: k_rk_cfl's expression (compressible.hip)
+__device__ __forceinline__ double fv4_cfl_cell(double d, double E, double mx, double my, double gamma, double dx,
+                                               double dy)
+{
+    const double u = mx / d, v = my / d;
+    const double e = (E - 0.5 * d * (u * u + v * v)) / d;
+    const double pr = d * e * (gamma - 1.0);
+    const double cs = sqrt(gamma * pr / d);
+    return 1.0 / ((fabs(u) + cs) / dx + (fabs(v) + cs) / dy);
+}
+
+// RKIntegrator.compute_final_update (lc.n = nstages) or the copy of the last SDC node (lc.n = 0) into
+// the state's OTHER buffer: the interior, and the ghost frame as the images of the new interior --
+// what the next iteration's fill_BC_all would write.  An update in place could not write the frame: a
+// ghost cell would read interior cells other threads overwrite.  One CFL partial per workgroup over
+// the interior cells it wrote (with index-map ghost cells the interior's minimum is the array's).
+__global__ __launch_bounds__(256) void k_fv4_final(double *__restrict__ dst, const double *__restrict__ y,
+                                                   const double *__restrict__ K, Geom g, Fv4Maps M, Fv4Coef lc,
+                                                   const StepScalars *__restrict__ S,
+                                                   const int *__restrict__ flag, double gamma, double dx,
+                                                   double dy, double *__restrict__ part)
+{
+    const int b = blockIdx.y * gridDim.x + blockIdx.x;
+    if (!fv4_run_goes(S, flag)) {
+        if (threadIdx.x == 0) part[b] = INFINITY;
+        return;
+    }
+    const double dt = S->dt;
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    double m = INFINITY;
+    if (j < g.qy)
+        for (int i = blockIdx.y; i < g.qx; i += gridDim.y) {
+            double w[4];
+#pragma unroll
+            for (int n = 0; n < 4; n++) {
+                bool neg;
+                const size_t ks = fv4_image(g, M, n, i, j, &neg);
+                double v = y[(size_t)n * g.plane + ks];
+                for (int s = 0; s < lc.n; s++) {
+                    const double c = dt * lc.c[s];
+                    v += c * K[(size_t)(4 * s + n) * g.plane + ks];
+                }
+                w[n] = neg ? -v : v;
+                dst[(size_t)n * g.plane + (size_t)i * g.pitch + j] = w[n];
+            }
+            if (i >= g.ilo && i <= g.ihi && j >= g.jlo && j <= g.jhi)
+                m = fmin(m, fv4_cfl_cell(w[0], w[1], w[2], w[3], gamma, dx, dy));
+        }
+    m = block_reduce_min(m);
+    if (threadIdx.x == 0) part[b] = m;
+}
+
+// k_sdc_update with the ghost fill of the destination node; hdt = dt / 2 and idt = dt / 24 from the
+// run's dt, each rounded once as comp_sdc_update forms them on the host
+__global__ __launch_bounds__(256) void k_fv4_sdc_node(double *__restrict__ dst, const double *__restrict__ src,
+                                                      Geom g, Fv4Maps M, SdcArgs A,
+                                                      const StepScalars *__restrict__ S,
+                                                      const int *__restrict__ flag)
+{
+    if (!fv4_run_goes(S, flag)) return;
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    const int i = blockIdx.y, n = blockIdx.z;
+    if (j >= g.qy) return;
+    bool neg;
+    const size_t k = (size_t)n * g.plane + fv4_image(g, M, n, i, j, &neg);
+    const double dt = S->dt;
+    const double hdt = 0.5 * dt, idt = dt / 24.0;
+    const double integral = idt * (A.c0 * A.q0[k] + A.c1 * A.q1[k] + A.c2 * A.q2[k]);
+    const double v = src[k] + hdt * (A.an[k] - A.ao[k]) + integral;
+    dst[(size_t)n * g.plane + (size_t)i * g.pitch + j] = neg ? -v : v;
+}
+
+// ghost frame of the four planes src -> dst (the close of a run: the state handed back carries the
+// filled ghost cells of the state before its last step, as after single steps)
+__global__ __launch_bounds__(256) void k_fv4_copy_frame(double *__restrict__ dst, const double *__restrict__ src,
+                                                        Geom g)
+{
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    const int i = blockIdx.y, n = blockIdx.z;
+    if (j >= g.qy || (i >= g.ilo && i <= g.ihi && j >= g.jlo && j <= g.jhi)) return;
+    const size_t k = (size_t)n * g.plane + (size_t)i * g.pitch + j;
+    dst[k] = src[k];
+}
+
+// stage state <- y + dt sum_j a[j] k_j (nterms terms, zeros included), ghost cells filled
+int fv4_stage_start(pyrohip_state *stage, const pyrohip_state *y, const pyrohip_state *k, const double *a,
+                    int nterms, const StepScalars *S)
+{
+    const Geom &g = y->g;
+    Fv4Coef lc;
+    lc.n = nterms;
+    for (int s = 0; s < 4; s++) lc.c[s] = s < nterms ? a[s] : 0.0;
+    PYRO_LAUNCH(y->ctx, "k_fv4_stage_start", k_fv4_stage_start, dim3((g.qy + 255) / 256, g.qx, 4), dim3(256), 0,
+                stage->d, (const double *)y->d, (const double *)k->d, g, fv4_maps(y), lc, S,
+                (const int *)y->d_flag);
+    PYRO_CHECK_HIP(hipGetLastError());
+    stage->next_cfl_min = -1.0;
+    stage->ghost_by_rules = false;
+    return 0;
+}
+
+// workgroups of k_fv4_final: pieces of 256 columns x at most 512 row slots (4608 partials at 2048^2)
+int fv4_final_parts(const Geom &g) { return ((g.qy + 255) / 256) * (g.qx < 512 ? g.qx : 512); }
+
+// the other buffer of y <- src + dt sum_s b[s] k_s (src: y itself, or the last SDC node with
+// nterms = 0), ghost frame from the images, CFL partials into part; the buffers are NOT exchanged here
+int fv4_final(pyrohip_state *y, const pyrohip_state *src, const pyrohip_state *k, const double *b, int nterms,
+              const pyrohip_comp_params *p, const StepScalars *S, double *part)
+{
+    const Geom &g = y->g;
+    Fv4Coef lc;
+    lc.n = nterms;
+    for (int s = 0; s < 4; s++) lc.c[s] = s < nterms ? b[s] : 0.0;
+    const dim3 grid((g.qy + 255) / 256, g.qx < 512 ? g.qx : 512);
+    PYRO_LAUNCH(y->ctx, "k_fv4_final", k_fv4_final, grid, dim3(256), 0, y->alt_base + geom_lead(g),
+                (const double *)src->d, (const double *)k->d, g, fv4_maps(y), lc, S, (const int *)y->d_flag,
+                p->gamma, p->dx, p->dy, part);
+    PYRO_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int fv4_sdc_node(pyrohip_state *dst, const pyrohip_state *src, const pyrohip_state *k, int slot_new,
+                 int slot_old, const int *slots_q, const double *cq, const StepScalars *S, const int *flag)
+{
+    const Geom &g = dst->g;
+    const size_t blk = (size_t)4 * g.plane;
+    SdcArgs A;
+    A.an = k->d + slot_new * blk;
+    A.ao = k->d + slot_old * blk;
+    A.q0 = k->d + slots_q[0] * blk;
+    A.q1 = k->d + slots_q[1] * blk;
+    A.q2 = k->d + slots_q[2] * blk;
+    A.c0 = cq[0]; A.c1 = cq[1]; A.c2 = cq[2];
+    A.hdt = 0.0; A.idt = 0.0;      // (formed by the kernel from the run's dt)
+    PYRO_LAUNCH(dst->ctx, "k_fv4_sdc_node", k_fv4_sdc_node, dim3((g.qy + 255) / 256, g.qx, 4), dim3(256), 0,
+                dst->d, (const double *)src->d, g, fv4_maps(dst), A, S, flag);
+    PYRO_CHECK_HIP(hipGetLastError());
+    dst->next_cfl_min = -1.0;
+    dst->ghost_by_rules = false;
+    return 0;
+}
+
+int fv4_copy_frame(pyrohip_state *dst, const double *src)
+{
+    const Geom &g = dst->g;
+    PYRO_LAUNCH(dst->ctx, "k_fv4_copy_frame", k_fv4_copy_frame, dim3((g.qy + 255) / 256, g.qx, 4), dim3(256), 0,
+                dst->d, src, g);
     PYRO_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -305,6 +305,21 @@ class DeviceState:
             check(self._l.pyrohip_comp_sdc_update(self.h, src.h, kstate.h, int(slot_new), int(slot_old),
                                                   sq, dptr(c), float(dt)))
 
+    def comp_fv4_evolve(self, params, stage, kstate, a, b, cfl, policy, max_steps, particles=None):
+        """up to max_steps compressible_fv4 steps with the driver's dt policy on the device
+        (pyrohip_comp_fv4_evolve; as comp_rk_evolve); stage / kstate: RKIntegrator.set_start's"""
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        return self._evolve(policy, max_steps, "pyrohip_comp_fv4_evolve",
+                            (self.h, C.byref(params), stage.h, kstate.h, len(b), dptr(a), dptr(b), float(cfl)),
+                            particles)
+
+    def comp_sdc_evolve(self, params, node1, node2, kstate, cfl, policy, max_steps, particles=None):
+        """... and compressible_sdc steps (pyrohip_comp_sdc_evolve); node1 / node2 / kstate:
+        compressible_sdc.Simulation._scratch's"""
+        return self._evolve(policy, max_steps, "pyrohip_comp_sdc_evolve",
+                            (self.h, C.byref(params), node1.h, node2.h, kstate.h, float(cfl)), particles)
+
     def lincomb(self, src, kstate, coefs):
         """self <- src (whole array); interior += coefs[s] * k_s in order"""
         c = np.ascontiguousarray(coefs, dtype=np.float64)
