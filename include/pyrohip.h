@@ -332,7 +332,11 @@ typedef struct {
        supports pyrohip_comp_stage_dump); 1 = one fused kernel on 2-d LDS
        tiles (best below ~1024^2); 2 = one fused kernel of autonomous
        wavefronts marching along the rows (x windows in registers, y exchange
-       by DPP lane rotation; the fastest on large grids)                     */
+       by DPP lane rotation; the fastest on large grids).
+       compressible_rk (pyrohip_comp_rk_step / _evolve): 1 = one launch of the stage tile
+       kernel per Runge-Kutta stage (comp_rk_tile.hip) at any size, 2 = the row-marching
+       kernel, -1 = the tile kernel below 1024^2 cells (fast_math 0: below 3072^2) and the
+       row-marching kernel from there on, 0 = stage by stage on the staged kernels */
     int kernel_set;
     /* compressible.riemann: 0 = HLLC (riemann.py:681-860), 1 = CGF (:8-310),
        2 = HLLC_lm (riemann_hllc_lowspeed, :863-1020).
@@ -419,6 +423,10 @@ int pyrohip_comp_wave_geometry(int nx, int ny, int ng, int num_cus, int march_ro
    value of the priority turns (0: more wavefronts than two rounds of resident ones; no priority
    board is taken) }.  The code the step itself goes by.                                    */
 int pyrohip_sph_wave_geometry(int nx, int ny, int ng, int num_cus, int march_rows, int *out7);
+/* the tiles of the compressible_rk stage kernel (kernel_set 1) on an nx x ny grid, without
+   launching anything: cells per tile along x and along y, number of tiles (= workgroups per
+   stage).  The code the step itself goes by.                                               */
+int pyrohip_comp_rk_tile_geometry(int nx, int ny, int *tx, int *ty, int *ntiles);
 /* the driver's time-step policy, NullSimulation.compute_timestep
    (simulation_null.py:222-244): dt = cfl * min, scaled by init_tstep_factor on
    the first step (n == 0), growth capped by max_dt_change * dt_old, fix_dt > 0
@@ -634,12 +642,14 @@ int pyrohip_comp_rk_dt(pyrohip_state *s, const pyrohip_comp_params *p,
    58-104) with the RKIntegrator of pyro/mesh/integration.py:76-129 in nstages launches:
    stage 0 = pyrohip_comp_rk_rhs of the ghost-filled state; every later stage builds its start
    y_0 + dt sum_j a[s][j] k_j (interior; ghost cells = the images the boundary rules give) as
-   the rows enter the kernel, the last one stores y_0 + dt sum_s b[s] k_s as the new state and
-   leaves the CFL minimum pyrohip_comp_rk_dt then answers from.  a: nstages x nstages row-major
+   its cells enter the kernel, the last one stores y_0 + dt sum_s b[s] k_s as the new state and
+   leaves the CFL minimum pyrohip_comp_rk_dt then answers from.  The kernel is the row-marching
+   one (kernel_set 2, or -1 from 1024^2 cells on -- 3072^2 with fast_math 0) or the stage tile
+   kernel (kernel_set 1, or -1 below that size; needs nx, ny >= 4).  a: nstages x nstages row-major
    (strictly lower triangular), b: nstages, 2 <= nstages <= 4; k: a state with >= 4 nstages
    planes (scratch).  Needs pyrohip_comp_rk_can_fuse (single Cartesian domain, outflow /
-   reflect / periodic sides, no sponge / heating / host source, kernel_set 2 or >= 2048^2
-   cells); everything else goes stage by stage (pyrohip_comp_rk_rhs + pyrohip_state_lincomb).
+   reflect / periodic sides, no sponge / heating / host source / well_balanced, kernel_set
+   -1, 1 or 2); everything else goes stage by stage (pyrohip_comp_rk_rhs + pyrohip_state_lincomb).
    PYROHIP_ERR_STATE: an invalid stage state; y is left as it was (floored).                */
 int pyrohip_comp_rk_can_fuse(pyrohip_state *y, const pyrohip_comp_params *p,
                              pyrohip_state *k, int nstages, int *flag);

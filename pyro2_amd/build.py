@@ -59,6 +59,9 @@ UNITS = [
     # the 4th-order method-of-lines right-hand side (compressible_fv4 / compressible_sdc)
     ("comp_fv4.hip", "fv4_exact", ["-ffp-contract=off", "-DPYRO_FAST=0"]),
     ("comp_fv4.hip", "fv4_fast", ["-ffp-contract=fast", "-DPYRO_FAST=1"]),
+    # compressible_rk: one tile-kernel launch per Runge-Kutta stage (small grids, kernel_set 1)
+    ("comp_rk_tile.hip", "rktile_exact", ["-ffp-contract=off", "-DPYRO_FAST=0"]),
+    ("comp_rk_tile.hip", "rktile_fast", ["-ffp-contract=fast", "-DPYRO_FAST=1"]),
     ("comp_api.hip", "comp_api", ["-ffp-contract=off"]),
     # the device-side run protocol: the small kernels between two steps and their host side
     ("evolve.hip", "evolve", ["-ffp-contract=off"]),

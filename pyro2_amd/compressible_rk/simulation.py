@@ -5,7 +5,11 @@ pyrohip_comp_rk_rhs (density floor, primitives, flattening, limited slopes,
 face states -- with compressible.well_balanced the y pressure slope and face pressures
 of fluxes.py:100-108, :139-148 --, Riemann fluxes, artificial viscosity, flux divergence,
 gravity and sponge sources); stage starts and the final update are
-pyrohip_state_lincomb launches (pyro2_amd/mesh/integration.py)."""
+pyrohip_state_lincomb launches (pyro2_amd/mesh/integration.py).  Where the library
+carries the whole step (pyrohip_comp_rk_can_fuse: standard boundaries, no sponge /
+heating / well_balanced) it is one launch per stage instead -- the stage tile kernel
+on small grids, the row-marching kernel from 1024^2 cells on (3072^2 without
+gpu.fast_math) -- and batches of steps run on the device (pyrohip_comp_rk_evolve)."""
 from ..compressible.simulation import Simulation as CompressibleSimulation
 from ..mesh import integration
 from ..util import msg
@@ -47,9 +51,11 @@ class Simulation(CompressibleSimulation):
         self.dt = st.comp_rk_dt(self._params(), float(cfl))
 
     def _rk_fusable(self, start, method):
-        """the whole Runge-Kutta step as nstages launches of the row-marching kernel
-        (pyrohip_comp_rk_step): standard boundary types filled by the device, no sponge, no
-        heating profile, no host-side source, a grid the kernel pays on (the library decides)"""
+        """the whole Runge-Kutta step as nstages launches of one kernel (pyrohip_comp_rk_step: the
+        stage tile kernel on small grids and with gpu.kernel_set 1, the row-marching kernel on large
+        ones and with gpu.kernel_set 2): standard boundary types filled by the device, no sponge, no
+        heating profile, no host-side source, not gpu.kernel_set 0, at least 4 cells each way (the
+        library decides: pyrohip_comp_rk_can_fuse)"""
         cc = self.cc_data
         if self._host_source() or self._heating() is not None or type(self).substep is not Simulation.substep:
             return False
@@ -103,8 +109,9 @@ class Simulation(CompressibleSimulation):
         tm.end()
 
     def can_evolve_many(self):
-        """batches of steps on the device (pyrohip_comp_rk_evolve): where the one-call step runs,
-        nothing watches the data, tracer particles only where the device advances them"""
+        """batches of steps on the device (pyrohip_comp_rk_evolve): where the one-call step runs
+        (_rk_fusable: at every grid size the library carries), nothing watches the data, tracer
+        particles only where the device advances them"""
         if self.cc_data._views_alive():
             return False
         if self.particles is not None and self._device_particle_source() is None:

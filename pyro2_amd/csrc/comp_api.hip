@@ -37,6 +37,9 @@ int comp_fv4_rhs(pyrohip_state *, const pyrohip_comp_params *, pyrohip_state *, 
 int comp_rk_rhs_wave(pyrohip_state *, const pyrohip_comp_params *, pyrohip_state *, int);
 int comp_rk_step_wave(pyrohip_state *, const pyrohip_comp_params *, pyrohip_state *, int, const double *,
                       const double *, double, const StepScalars *, const double **);
+int comp_rk_step_tile(pyrohip_state *, const pyrohip_comp_params *, pyrohip_state *, int, const double *,
+                      const double *, double, const StepScalars *, const double **);
+void rk_tile_geometry(int, int, int *, int *, int *);
 int comp_rk_cfl_min_device(pyrohip_state *, const pyrohip_comp_params *, const double **);
 int comp_wave_geometry(int, int, int, int, int, int *);
 int sph_wave_geometry(int, int, int, int, int, int *);
@@ -59,6 +62,8 @@ int comp_fv4_rhs(pyrohip_state *, const pyrohip_comp_params *, pyrohip_state *, 
 int comp_fv4_rhs_run(pyrohip_state *, const pyrohip_comp_params *, pyrohip_state *, int, const StepScalars *, int *);
 int comp_rk_rhs_wave(pyrohip_state *, const pyrohip_comp_params *, pyrohip_state *, int);
 int comp_rk_step_wave(pyrohip_state *, const pyrohip_comp_params *, pyrohip_state *, int, const double *,
+                      const double *, double, const StepScalars *, const double **);
+int comp_rk_step_tile(pyrohip_state *, const pyrohip_comp_params *, pyrohip_state *, int, const double *,
                       const double *, double, const StepScalars *, const double **);
 int comp_dt(pyrohip_state *, const pyrohip_comp_params *, double, double *);
 int comp_step_staged(pyrohip_state *, const pyrohip_comp_params *, double);
@@ -90,8 +95,8 @@ using namespace pyro;
 // "This call takes the row-marching wavefront kernel": kernel_set 2, or the library's choice
 // (kernel_set -1) where that kernel fills the chip -- it needs >= ~2 wavefronts per SIMD of 56
 // columns x >= 32 rows; measured crossover with the tile kernel at 2048^2 cells
-// (profiles/r02_kernel_sets_by_size.txt).  SphericalPolar steps, the Runge-Kutta stages and the
-// Runge-Kutta step:
+// (profiles/r02_kernel_sets_by_size.txt).  SphericalPolar steps and the Runge-Kutta stages taken
+// singly (pyrohip_comp_rk_rhs):
 static bool takes_wave_kernel(const Geom &g, const pyrohip_comp_params *p)
 {
     return p->kernel_set == 2 || (p->kernel_set == -1 && (double)g.nx * (double)g.ny >= 2048.0 * 2048.0);
@@ -555,18 +560,49 @@ int pyrohip_comp_rk_dt(pyrohip_state *s, const pyrohip_comp_params *p, double cf
     return exact::comp_rk_dt(s, p, cfl, dt_out);
 }
 
-// The whole Runge-Kutta step in nstages launches of the row-marching kernel (comp_wave.hip:
-// comp_rk_step_wave)?  Single Cartesian domain, outflow / reflect / periodic sides (the same kind
-// for the four variables: the stage states' ghost cells are read through index maps), no sponge,
-// no heating profile, no host-evaluated source, no well-balanced reconstruction (the row-marching
-// kernel does not carry it); where the call takes that kernel (takes_wave_kernel).
+// ... the whole Runge-Kutta step (pyrohip_comp_rk_step / _evolve): kernel_set 2, or the library's
+// choice from the size on at which the row-marching kernel passes the stage tile kernel.  Measured,
+// the RK4 step alone on Sedov (profiles/comprk_tile_time.txt; row-marching / tile): contracted build
+// 512^2 1.43, 768^2 1.17, 896^2 1.03 (a tie), 1024^2 0.87, 1536^2 0.79, 2048^2 0.74, 4096^2 0.68;
+// bit-faithful build 512^2 1.84, 1024^2 1.14, 1536^2 1.08, 2048^2 1.03, 3072^2 1.01 (a tie: the
+// row-marching kernel keeps it), 4096^2 0.96.
+static bool takes_wave_kernel_rk(const Geom &g, const pyrohip_comp_params *p)
+{
+    const double side = p->fast_math ? 1024.0 : 3072.0;
+    return p->kernel_set == 2 || (p->kernel_set == -1 && (double)g.nx * (double)g.ny >= side * side);
+}
+// "This Runge-Kutta step takes the stage tile kernel" (comp_rk_tile.hip): where the row-marching
+// kernel does not take the call, with kernel_set 1 or the library's choice, on a grid whose ghost
+// images are interior cells (4 cells each way).  kernel_set 0 stays staged (stage dumps).
+static bool takes_rk_tile(const Geom &g, const pyrohip_comp_params *p)
+{
+    return !takes_wave_kernel_rk(g, p) && (p->kernel_set == -1 || p->kernel_set == 1) && g.nx >= 4 && g.ny >= 4;
+}
+
+// The whole Runge-Kutta step in nstages launches of ONE kernel -- the row-marching kernel
+// (comp_wave.hip: comp_rk_step_wave) where the call takes it (takes_wave_kernel_rk), the stage tile
+// kernel (comp_rk_tile.hip: comp_rk_step_tile) below that size and with kernel_set 1?  Single
+// Cartesian domain, outflow / reflect / periodic sides (the same kind for the four variables: the
+// stage states' ghost cells are read through index maps), no sponge, no heating profile, no
+// host-evaluated source, no well-balanced reconstruction (neither kernel carries them).
 static bool comp_rk_can_fuse(const pyrohip_state *y, const pyrohip_comp_params *p, const pyrohip_state *k,
                              int nstages)
 {
     if (y->nvar != 4 || y->sph || y->nb_set || y->user_bc || y->ramp_bc || y->heat || y->ext_old ||
         p->do_sponge || p->well_balanced || y->g.ng < 4 || nstages < 2 || nstages > 4 || !k || k->nvar < 4 * nstages)
         return false;
-    return takes_wave_kernel(y->g, p) && same_index_map_kinds(y, false);
+    return (takes_wave_kernel_rk(y->g, p) || takes_rk_tile(y->g, p)) && same_index_map_kinds(y, false);
+}
+
+// the step itself, by the same predicate
+static int comp_rk_step_any(pyrohip_state *y, const pyrohip_comp_params *p, pyrohip_state *k, int nstages,
+                            const double *a, const double *b, double dt, const StepScalars *S, const double **dmin)
+{
+    if (takes_wave_kernel_rk(y->g, p))
+        return p->fast_math ? fastm::comp_rk_step_wave(y, p, k, nstages, a, b, dt, S, dmin)
+                            : exact::comp_rk_step_wave(y, p, k, nstages, a, b, dt, S, dmin);
+    return p->fast_math ? fastm::comp_rk_step_tile(y, p, k, nstages, a, b, dt, S, dmin)
+                        : exact::comp_rk_step_tile(y, p, k, nstages, a, b, dt, S, dmin);
 }
 
 static int check_rk(pyrohip_state *y, const pyrohip_comp_params *p, pyrohip_state *k, int nstages,
@@ -601,10 +637,9 @@ int pyrohip_comp_rk_step(pyrohip_state *y, const pyrohip_comp_params *p, pyrohip
                                     "stage by stage on the staged kernels)");
     PYRO_REQUIRE(comp_rk_can_fuse(y, p, k, nstages),
                  "pyrohip_comp_rk_step: single Cartesian domain, outflow / reflect / periodic sides, no sponge / "
-                 "heating / host source, kernel_set 2 or a grid of >= 2048^2 cells (pyrohip_comp_rk_can_fuse; "
-                 "otherwise stage by stage: pyrohip_comp_rk_rhs + pyrohip_state_lincomb)");
-    const int rc = p->fast_math ? fastm::comp_rk_step_wave(y, p, k, nstages, a, b, dt, nullptr, nullptr)
-                                : exact::comp_rk_step_wave(y, p, k, nstages, a, b, dt, nullptr, nullptr);
+                 "heating / host source, kernel_set -1, 1 or 2 and at least 4 cells each way "
+                 "(pyrohip_comp_rk_can_fuse; otherwise stage by stage: pyrohip_comp_rk_rhs + pyrohip_state_lincomb)");
+    const int rc = comp_rk_step_any(y, p, k, nstages, a, b, dt, nullptr, nullptr);
     y->ghost_by_rules = false;
     return rc;
 }
@@ -649,8 +684,7 @@ int pyrohip_comp_rk_evolve_p(pyrohip_state *y, const pyrohip_comp_params *p, pyr
         }
         if (rc) break;
         s->frame_prefilled = frame_done;
-        rc = p->fast_math ? fastm::comp_rk_step_wave(s, p, k, nstages, a, b, 0.0, s->d_scal, &r.dmin)
-                          : exact::comp_rk_step_wave(s, p, k, nstages, a, b, 0.0, s->d_scal, &r.dmin);
+        rc = comp_rk_step_any(s, p, k, nstages, a, b, 0.0, s->d_scal, &r.dmin);
         r.take_pending();
         if (rc == 0) rc = evolve_particles(r);
     }
@@ -944,6 +978,16 @@ int pyrohip_comp_stage_dump(pyrohip_state *s, int stage_id, double *out)
 }
 
 }  // extern "C"
+
+// the tiles of the Runge-Kutta stage kernel on an nx x ny grid (comp_rk_tile.hip; no kernel runs):
+// cells per tile along x and y, number of tiles -- tests place their shapes on the kernel's seams
+extern "C" int pyrohip_comp_rk_tile_geometry(int nx, int ny, int *tx, int *ty, int *ntiles)
+{
+    PYRO_REQUIRE(tx && ty && ntiles, "NULL argument");
+    PYRO_REQUIRE(nx >= 1 && ny >= 1, "nx, ny must be positive");
+    pyro::exact::rk_tile_geometry(nx, ny, tx, ty, ntiles);
+    return 0;
+}
 
 extern "C" int pyrohip_sph_wave_geometry(int nx, int ny, int ng, int num_cus, int march_rows, int *out7)
 {

@@ -49,6 +49,15 @@ def sph_wave_geometry(nx, ny, ng=4, num_cus=0, march_rows=0):
                      "prio_duty"), (int(v) for v in out)))
 
 
+def comp_rk_tile_geometry(nx, ny):
+    """tiles of the compressible_rk stage kernel (k_rk_tile, gpu.kernel_set 1) on an nx x ny grid
+    (pyrohip_comp_rk_tile_geometry, no kernel runs): dict of the cells per tile along x and y and
+    the number of tiles (workgroups per stage)"""
+    tx, ty, nt = C.c_int(), C.c_int(), C.c_int()
+    check(_lib.lib().pyrohip_comp_rk_tile_geometry(int(nx), int(ny), C.byref(tx), C.byref(ty), C.byref(nt)))
+    return {"tx": tx.value, "ty": ty.value, "ntiles": nt.value}
+
+
 def _check_run(rc, dts):
     """check() for a device-side run: the error carries what the run did before it stopped
     (steps_done, dts: the steps that advanced the state, which is the one before the failing step)"""
