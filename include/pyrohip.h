@@ -414,6 +414,17 @@ int pyrohip_comp_step(pyrohip_state *s, const pyrohip_comp_params *p,
    wavefronts per launch, wavefronts resident at once }.  For callers that decompose a grid
    (decomp.py; bench.py's scaling line records it per rank).                            */
 int pyrohip_comp_wave_geometry(int nx, int ny, int ng, int num_cus, int march_rows, int *out6);
+/* the whole plan of that launch, by the function the step itself goes by, without launching anything:
+   neighbours != 0: a slab with neighbours (pyrohip_state_set_neighbours: no cut strips, no short tail).
+   out11 = { column strips (56 updated columns each), rows per strip, row strips of that length (a last
+   strip of fewer than ng rows joins its predecessor), overlap as above, n_extra (the column strips
+   [0, n_extra) are cut into row strips + 1 equal parts: a launch of one round fills the slots), n_short
+   (many-round launches: so many SHORT row strips end the grid, behind the long ones; 0: none), Ls (their
+   length), long row strips (in front of the short ones; = row strips without a short tail), the duty value
+   of the priority turns (0: more wavefronts than two rounds of resident ones), wavefronts per launch
+   (column strips x (long + short row strips) + n_extra), wavefronts resident at once }.  A step that is
+   the only launch of a step of pyrohip_comp_evolve (step_launches 1) takes no short tail.          */
+int pyrohip_comp_wave_plan(int nx, int ny, int ng, int num_cus, int march_rows, int neighbours, int *out11);
 /* the launch geometry of the row-marching SphericalPolar step (k_sph_wave: kernel_set 2 on a state
    with a geometry) on an nx x ny grid on a device of num_cus compute units (<= 0: 256) with the
    caller's march_rows (0: the library's strips), without launching anything: out7 = { column

@@ -42,6 +42,7 @@ int comp_rk_step_tile(pyrohip_state *, const pyrohip_comp_params *, pyrohip_stat
 void rk_tile_geometry(int, int, int *, int *, int *);
 int comp_rk_cfl_min_device(pyrohip_state *, const pyrohip_comp_params *, const double **);
 int comp_wave_geometry(int, int, int, int, int, int *);
+int comp_wave_plan(int, int, int, int, int, int, int *);
 int sph_wave_geometry(int, int, int, int, int, int *);
 int comp_fv4_rhs_run(pyrohip_state *, const pyrohip_comp_params *, pyrohip_state *, int, const StepScalars *, int *);
 int fv4_stage_start(pyrohip_state *, const pyrohip_state *, const pyrohip_state *, const double *, int,
@@ -999,4 +1000,10 @@ extern "C" int pyrohip_comp_wave_geometry(int nx, int ny, int ng, int num_cus, i
 {
     PYRO_REQUIRE(out6 && nx > 0 && ny > 0 && ng >= 0, "bad argument");
     return pyro::exact::comp_wave_geometry(nx, ny, ng, num_cus, march_rows, out6);
+}
+
+extern "C" int pyrohip_comp_wave_plan(int nx, int ny, int ng, int num_cus, int march_rows, int neighbours, int *out11)
+{
+    PYRO_REQUIRE(out11 && nx > 0 && ny > 0 && ng >= 0 && march_rows >= 0, "bad argument");
+    return pyro::exact::comp_wave_plan(nx, ny, ng, num_cus, march_rows, neighbours, out11);
 }

@@ -367,6 +367,7 @@ __global__ __launch_bounds__(FNT, (NA > 0 ? 2 : FUSED_MINW)) void k_ctu_fused(co
             Cons Ug{Uin[kc], 0.0, 0.0, Uin[3 * pl + kc]};
             if (i >= g.ilo && i <= g.ihi && js >= g.jlo && js <= g.jhi)
                 Ug.d = fmax(Ug.d, P.small_dens);
+            else Ug.d = ghost_src_dens(Ug.d, P.small_dens);
             const double sgn =
                 ((j < g.jlo && P.refl_ylo) || (j > g.jhi && P.refl_yhi)) ? -1.0 : 1.0;
             const double hp = P.heat ? P.heat[(size_t)(ina ? i : g.qx - 1) * p + (ina ? j : g.qy - 1)]

@@ -735,6 +735,7 @@ __global__ __launch_bounds__(64, WAVE_MINW) void k_ctu_wave(const double *__rest
                 Ug.d = Uin[kc]; Ug.my = Uin[3 * pl + kc];
                 if (i >= g.ilo && i <= g.ihi && js >= g.jlo && js <= g.jhi)
                     Ug.d = fmax(Ug.d, US(SMALLD, P.small_dens));
+                else Ug.d = ghost_src_dens(Ug.d, US(SMALLD, P.small_dens));
                 sgn = ((j < g.jlo && P.refl_ylo) || (j > g.jhi && P.refl_yhi)) ? -1.0 : 1.0;
                 hp = P.heat ? P.heat[(size_t)(ina ? i : g.qx - 1) * p + (ina ? j : g.qy - 1)] : 0.0;
             }
@@ -1075,7 +1076,41 @@ static int wave_short_tail(const WaveGeom &w, int nx, int slots, int march_rows,
     *Ls = ls; *nsb_long = nl;
     return ns;
 }
+// The plan of a step's launch: everything comp_step_wave_ex decides before it launches, for a single domain
+// or for a slab with neighbours (no cut strips, no short tail: a slab's strips are its protocol; what the halo
+// communicator adds on top -- the boundary launch and its own short strips -- stays with the step), `one_launch`:
+// the step kernel is the whole step of pyrohip_comp_evolve (no short tail: the last wavefront runs the dt policy).
+// The step and pyrohip_comp_wave_plan go by this one function.
+struct WavePlan {
+    WaveGeom w;
+    int n_extra, n_short, Ls, nsb;     // nsb: row strips of the launch (the long ones + the short tail)
+    int nsb_long, prio_duty, nwg, slots;
+};
+static WavePlan wave_plan(int nx, int ny, int ng, int cus, int march_rows, bool neighbours, bool one_launch)
+{
+    WavePlan q;
+    q.w = wave_geometry(nx, ny, ng, cus, march_rows);
+    q.slots = 4 * WAVE_MINW * cus;
+    q.n_extra = neighbours ? 0 : wave_extra_units(q.w, nx, q.slots, march_rows);
+    q.n_short = 0; q.Ls = 0; q.nsb_long = q.w.nsb;
+    if (!neighbours && !one_launch)
+        q.n_short = wave_short_tail(q.w, nx, q.slots, march_rows, &q.Ls, &q.nsb_long);
+    q.nsb = q.n_short > 0 ? q.nsb_long + q.n_short : q.w.nsb;
+    q.nwg = q.w.ncb * q.nsb + q.n_extra;
+    q.prio_duty = wave_prio_duty(q.nwg, q.slots, q.w.L);
+    return q;
+}
 #if !PYRO_FAST
+// out: column strips, rows per strip, row strips (without a short tail), overlap, n_extra, n_short, Ls, long row
+// strips, prio_duty, wavefronts, slots
+int comp_wave_plan(int nx, int ny, int ng, int cus, int march_rows, int neighbours, int *out)
+{
+    const WavePlan q = wave_plan(nx, ny, ng, cus > 0 ? cus : 256, march_rows, neighbours != 0, false);
+    out[0] = q.w.ncb; out[1] = q.w.L; out[2] = q.w.nsb; out[3] = q.w.overlap;
+    out[4] = q.n_extra; out[5] = q.n_short; out[6] = q.Ls; out[7] = q.nsb_long;
+    out[8] = q.prio_duty; out[9] = q.nwg; out[10] = q.slots;
+    return 0;
+}
 // (for callers that want to know before they launch: bench.py's scaling line, the tests of
 // the decomposed runs)  out: ncb, L, nsb, overlap, wavefronts, resident slots
 int comp_wave_geometry(int nx, int ny, int ng, int cus, int march_rows, int *out)
@@ -1096,20 +1131,19 @@ int comp_step_wave_ex(pyrohip_state *s, const pyrohip_comp_params *p, double dt,
     double *Uin, *Uout;
     PYRO_TRY(fused_prepare(s, p, dt, P, Uin, Uout, S == nullptr));
     const int cus = c->num_cus > 0 ? c->num_cus : 256;
-    const WaveGeom wg = wave_geometry(g.nx, g.ny, g.ng, cus, p->march_rows);
-    P.ncb = wg.ncb;
-    P.L = wg.L;
-    const int nsb = wg.nsb;
-    P.nsb = nsb;
     // slab of a decomposed run with the halo communicator: EVERY step posts the
     // exchange of its new boundary rows (overlapped when the strips allow it), so the
     // protocol does not depend on this rank's geometry
     const bool post = s->nb_set && comm_can_overlap(s);
-    P.n_extra = (s->nb_set || post) ? 0 : wave_extra_units(wg, g.nx, 4 * WAVE_MINW * cus, p->march_rows);
-    int nsb_long = nsb;
-    if (!s->nb_set && !post && !(S && s->pol_next))
-        P.n_short = wave_short_tail(wg, g.nx, 4 * WAVE_MINW * cus, p->march_rows, &P.Ls, &nsb_long);
-    if (P.n_short > 0) { P.nsb = nsb_long + P.n_short; P.units_short = P.ncb * P.n_short; }
+    // strips, cut strips, short tail, priority turns, unit count: wave_plan (pyrohip_comp_wave_plan reads the same)
+    const WavePlan plan = wave_plan(g.nx, g.ny, g.ng, cus, p->march_rows, s->nb_set, S && s->pol_next);
+    const WaveGeom &wg = plan.w;
+    P.ncb = wg.ncb;
+    P.L = wg.L;
+    const int nsb = wg.nsb;
+    P.nsb = plan.nsb;
+    P.n_extra = plan.n_extra;
+    if (plan.n_short > 0) { P.n_short = plan.n_short; P.Ls = plan.Ls; P.units_short = P.ncb * P.n_short; }
     // (a slab with the boundary strips on the halo stream: the interior launch ends with short strips too -- the
     // row strips in front of the last boundary strip, which keeps its rows; strip lengths that divide only)
     int slab_short = 0;
@@ -1200,8 +1234,8 @@ int comp_step_wave_ex(pyrohip_state *s, const pyrohip_comp_params *p, double dt,
         s->halo_pending = (rc == 0);
         return rc;
     }
-    P.nunits = nwg;
-    P.prio_duty = wave_prio_duty(nwg, 4 * WAVE_MINW * cus, P.L);
+    P.nunits = nwg;               // (no boundary launch: the plan's units)
+    P.prio_duty = plan.prio_duty;
     PYRO_TRY(wave_prio_feedback(c, P));
     if (S && s->pol_next && !post) {
         // this launch is the whole step (pyrohip_comp_evolve): ghost cells read through the

@@ -187,7 +187,8 @@ __global__ __launch_bounds__(256) void k_states(const double *__restrict__ U,
     if (P.have_src) {   // apply_source_terms, unsplit_fluxes.py:247-330
         // "ambient" upper boundary: the source ghosts are copies of row jhi
         // (BC.py:159-160), not the sources of the ambient ghost state
-        const Cons Uc = load_cons(U, pl, (P.amb_yhi && j > g.jhi) ? k - (j - g.jhi) : k);
+        Cons Uc = load_cons(U, pl, (P.amb_yhi && j > g.jhi) ? k - (j - g.jhi) : k);
+        if (i < g.ilo || i > g.ihi || j < g.jlo || j > g.jhi) Uc.d = ghost_src_dens(Uc.d, P.small_dens);
         const double sgn = ((j < g.jlo && P.refl_ylo) || (j > g.jhi && P.refl_yhi)) ? -1.0 : 1.0;
         const double hp = P.heat ? P.heat[k] : 0.0;
         add_grav_to_state(XM, Uc, P.grav, P.dt, sgn, P.heat_rate, hp);
@@ -199,7 +200,8 @@ __global__ __launch_bounds__(256) void k_states(const double *__restrict__ U,
                    // aux data (unsplit_fluxes.py:298-306); gravity alone when have_src
         const Cons X = load_cons(P.ext, pl, k);
         Cons *F[4] = {&XM, &XP, &YM, &YP};
-        const Cons Uc = load_cons(U, pl, (P.amb_yhi && j > g.jhi) ? k - (j - g.jhi) : k);
+        Cons Uc = load_cons(U, pl, (P.amb_yhi && j > g.jhi) ? k - (j - g.jhi) : k);
+        if (i < g.ilo || i > g.ihi || j < g.jlo || j > g.jhi) Uc.d = ghost_src_dens(Uc.d, P.small_dens);
         const double sgn = ((j < g.jlo && P.refl_ylo) || (j > g.jhi && P.refl_yhi)) ? -1.0 : 1.0;
         const double Sy = sgn * (Uc.d * P.grav) + X.my;
         const double SE = sgn * (Uc.my * P.grav) + X.E;

@@ -1175,6 +1175,25 @@ __device__ __forceinline__ void add_grav_to_state(Cons &S, const Cons &Ucell, do
     S.E += 0.5 * dt * SE;
 }
 
+// The density that source takes in a GHOST cell.  The reference floors the interior in place
+// (clean_state) and leaves the ghost cells as the fill left them, but the source's own ghost cells are
+// filled from its interior (unsplit_fluxes.py:295-306): the source of a ghost cell is that of the FLOORED
+// cell it mirrors.  The ghost state holds the unfloored density, as it is (outflow, reflect, periodic,
+// hse) or negated (a side where every variable is odd): floor its magnitude.  A NaN stays one; with the
+// floor off (small_dens = -1e200) nothing changes.  (The odd image of a positive density and the even image
+// of a negative one cannot be told apart here: a negative interior density that only the floor makes
+// valid keeps its own ghost source.  And the rule is exact only for ghost cells that ARE images: the
+// density of an `hse` ghost cell is a copy of the boundary row's (BC.py:56-63), an image as well, but a
+// boundary that integrates or prescribes its ghost densities needs the source read from the image cell,
+// as the SphericalPolar kernels do -- `ambient`, the one that prescribes them today, has its callers read
+// row jhi, an interior row that is floored as such.)
+__device__ __forceinline__ double ghost_src_dens(double d, double small)
+{
+    if (d >= 0.0 && d < small) return small;
+    if (d < 0.0 && -d < small) return -small;
+    return d;
+}
+
 // Source predictor-corrector after the conservative update
 // (compressible/simulation.py:406-423 with get_external_sources :105-161):
 // U* = U + dt S(U_old); S_new uses the time-centred momentum; U = U* + dt/2 (S_new - S_old)

@@ -25,6 +25,21 @@ def comp_wave_geometry(nx, ny, ng=4, num_cus=0, march_rows=0):
                     (int(v) for v in out)))
 
 
+def comp_wave_plan(nx, ny, ng=4, num_cus=0, march_rows=0, neighbours=False):
+    """the whole launch plan of the row-marching compressible kernel on an nx x ny grid, or on a slab
+    with neighbours (pyrohip_comp_wave_plan: the function the step goes by, no kernel runs): dict of
+    column strips, rows per strip, row strips of that length, overlap eligibility, n_extra (the first
+    n_extra column strips are cut into row_strips + 1 equal parts), n_short and short_rows (so many
+    short row strips of that length end the grid behind long_row_strips long ones; 0: none), the duty
+    value of the priority turns (0: none), wavefronts per launch, resident wavefront slots"""
+    out = (C.c_int * 11)()
+    check(_lib.lib().pyrohip_comp_wave_plan(int(nx), int(ny), int(ng), int(num_cus), int(march_rows),
+                                              int(bool(neighbours)), out))
+    return dict(zip(("col_strips", "rows_per_strip", "row_strips", "overlap", "n_extra", "n_short",
+                     "short_rows", "long_row_strips", "prio_duty", "wavefronts", "slots"),
+                    (int(v) for v in out)))
+
+
 def swe_wave_geometry(nx, ny, ng=4, num_cus=0):
     """launch geometry of the one-launch shallow-water step on an nx x ny grid
     (pyrohip_swe_wave_geometry, no kernel runs): dict of column strips, rows per regular row
