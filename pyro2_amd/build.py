@@ -145,7 +145,9 @@ def build(force=False, verbose=False):
 
     with ThreadPoolExecutor(max_workers=min(8, len(us))) as ex:
         objs = list(ex.map(compile_one, us))
-    cmd = [hipcc, f"--offload-arch={ARCH}", "-shared", "-o", LIB] + objs
+    # --no-undefined: a function that csrc/comp_units.h (or any unit) declares and calls but no unit
+    # defines fails the build here, by name, instead of the load of the library on the GPU machine
+    cmd = [hipcc, f"--offload-arch={ARCH}", "-shared", "-Wl,--no-undefined", "-o", LIB] + objs
     if any(u[1] == "comm" for u in us):
         cmd += ["-L/opt/rocm/lib", "-lrccl", "-Wl,-rpath,/opt/rocm/lib"]
     if verbose:

@@ -35,19 +35,11 @@
 // order: results identical to NumPy) and contracted (-ffp-contract=fast: north_star's
 // tolerance for advection is 1e-12, the multiply-add pairs of the slope / state / flux
 // expressions fuse); pyrohip_adv_params.fast_math selects.
+#include "builds.h"
 #include "common.h"
 #include "stencil.h"
 #include "wave_march.h"
 #include <type_traits>
-
-#ifndef PYRO_FAST
-#define PYRO_FAST 0
-#endif
-#if PYRO_FAST
-#define PYRO_NS fastm
-#else
-#define PYRO_NS exact
-#endif
 
 namespace pyro {
 namespace PYRO_NS {
@@ -748,8 +740,7 @@ extern "C" int pyrohip_adv_step_p(pyrohip_state *s, int n, const pyrohip_adv_par
     PYRO_TRY(state_work(s, WorkOwner::ADV, 1));
     double *cur = s->d + (size_t)n * g.plane;
     double *nxt = s->work + geom_lead(g);
-    PYRO_TRY(ap->fast_math ? fastm::adv_step_launch(s, n, ap, dt, cur, nxt)
-                           : exact::adv_step_launch(s, n, ap, dt, cur, nxt));
+    PYRO_TRY(PYRO_BUILD(ap->fast_math, adv_step_launch(s, n, ap, dt, cur, nxt)));
     return state_take_work(s, n);
 }
 
@@ -791,11 +782,9 @@ extern "C" int pyrohip_adv_evolve(pyrohip_state *s, int n, const pyrohip_adv_par
         double *cur = s->d + (size_t)n * g.plane;
         double *nxt = s->work + geom_lead(g);
         if (K == 1 && !(ap->multi_k == 1 && periodic && ap->u != 0.0 && ap->v != 0.0 && !s->nb_set)) {
-            PYRO_TRY(ap->fast_math ? fastm::adv_step_launch(s, n, &one, dts[done], cur, nxt)
-                                   : exact::adv_step_launch(s, n, &one, dts[done], cur, nxt));
+            PYRO_TRY(PYRO_BUILD(ap->fast_math, adv_step_launch(s, n, &one, dts[done], cur, nxt)));
         } else {
-            PYRO_TRY(ap->fast_math ? fastm::adv_multi_launch(s, &one, dts + done, K, cur, nxt)
-                                   : exact::adv_multi_launch(s, &one, dts + done, K, cur, nxt));
+            PYRO_TRY(PYRO_BUILD(ap->fast_math, adv_multi_launch(s, &one, dts + done, K, cur, nxt)));
         }
         PYRO_TRY(state_take_work(s, n));
         done += K;

@@ -42,17 +42,9 @@
 // Compiled twice (build.py): bit-faithful (-ffp-contract=off, the reference's operation order,
 // cx = u*dt/dx as a product and a true division per cell: results identical to NumPy) and
 // contracted (-ffp-contract=fast, cx = u*(dt/dx)); pyrohip_advnu_params.fast_math selects.
+#include "builds.h"
 #include "common.h"
 #include "stencil.h"
-
-#ifndef PYRO_FAST
-#define PYRO_FAST 0
-#endif
-#if PYRO_FAST
-#define PYRO_NS fastm
-#else
-#define PYRO_NS exact
-#endif
 
 namespace pyro {
 namespace PYRO_NS {
@@ -296,8 +288,7 @@ extern "C" int pyrohip_advnu_evolve(pyrohip_state *s, int ia, int iu, int iv, co
     PYRO_REQUIRE(dts || nsteps == 0, "NULL argument");
     PYRO_REQUIRE(nsteps >= 0, "negative step count");
     auto step = [&](int k, const double *cur, double *nxt) {
-        return ap->fast_math ? fastm::advnu_step_launch(s, ia, iu, iv, ap, dts[k], cur, nxt, nullptr)
-                             : exact::advnu_step_launch(s, ia, iu, iv, ap, dts[k], cur, nxt, nullptr);
+        return PYRO_BUILD(ap->fast_math, advnu_step_launch(s, ia, iu, iv, ap, dts[k], cur, nxt, nullptr));
     };
     return evolve_pingpong(s, ia, WorkOwner::ADVNU, 1, nsteps, step);
 }
@@ -323,10 +314,8 @@ extern "C" int pyrohip_advnu_stage_dump(pyrohip_state *s, int ia, int iu, int iv
     DevBuf tmp;
     PYRO_TRY(tmp.ensure(4 * g.plane * sizeof(double)));
     double *dump = (double *)tmp.p;
-    const int rc = ap->fast_math ? fastm::advnu_step_launch(s, ia, iu, iv, ap, dt, s->d + (size_t)ia * g.plane,
-                                                            s->work + geom_lead(g), dump)
-                                 : exact::advnu_step_launch(s, ia, iu, iv, ap, dt, s->d + (size_t)ia * g.plane,
-                                                            s->work + geom_lead(g), dump);
+    const int rc = PYRO_BUILD(ap->fast_math, advnu_step_launch(s, ia, iu, iv, ap, dt, s->d + (size_t)ia * g.plane,
+                                                               s->work + geom_lead(g), dump));
     return dump_planes_to_host(s, tmp, 4, rc, hipSuccess, host);
 }
 

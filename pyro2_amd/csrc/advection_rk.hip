@@ -57,19 +57,11 @@
 // there --, and beta**2 is the C library's pow(), which is not always the product (libm_pow2.h).
 #include <cmath>
 
+#include "builds.h"
 #include "common.h"
 #include "stencil.h"
 #include "fv4_limit.h"
 #include "libm_pow2.h"
-
-#ifndef PYRO_FAST
-#define PYRO_FAST 0
-#endif
-#if PYRO_FAST
-#define PYRO_NS fastm
-#else
-#define PYRO_NS exact
-#endif
 
 namespace pyro {
 
@@ -477,9 +469,8 @@ int advrk_stages(pyrohip_state *s, int var, const pyrohip_advrk_params *ap, cons
             for (int k = 0; k < tb.ns; k++) cb[k] = dt * tb.b[k];           // integration.py:125
         double *kout = last ? nullptr : kpl + (size_t)st * g.plane;
         double *d = st == upto ? dump : nullptr;
-        PYRO_TRY(ap->fast_math
-                     ? fastm::advrk_stage_launch(s, var, ap, cur, kpl, g.plane, st, last, ca, cb, kout, nxt, d)
-                     : exact::advrk_stage_launch(s, var, ap, cur, kpl, g.plane, st, last, ca, cb, kout, nxt, d));
+        PYRO_TRY(PYRO_BUILD(ap->fast_math,
+                            advrk_stage_launch(s, var, ap, cur, kpl, g.plane, st, last, ca, cb, kout, nxt, d)));
     }
     return 0;
 }
@@ -500,11 +491,8 @@ extern "C" int pyrohip_advrk_rhs(pyrohip_state *y, int var, const pyrohip_advrk_
     PYRO_TRY(comm_wait_halo(y));
     const double *cur = y->d + (size_t)var * y->g.plane;
     double *kout = kstate->d + (size_t)slot * y->g.plane;
-    return ap->fast_math
-               ? fastm::advrk_stage_launch(y, var, ap, cur, nullptr, 0, 0, false, nullptr, nullptr, kout, nullptr,
-                                           nullptr)
-               : exact::advrk_stage_launch(y, var, ap, cur, nullptr, 0, 0, false, nullptr, nullptr, kout, nullptr,
-                                           nullptr);
+    return PYRO_BUILD(ap->fast_math, advrk_stage_launch(y, var, ap, cur, nullptr, 0, 0, false, nullptr, nullptr,
+                                                        kout, nullptr, nullptr));
 }
 
 // nsteps Runge-Kutta steps, nstages launches each, alternating between the variable's plane of

@@ -1,93 +1,18 @@
 // extern "C" entry points of the compressible solver: argument checking and
-// dispatch between the bit-faithful (exact) and contracted (fastm) builds of
-// compressible.hip / comp_fused.hip.
+// dispatch (PYRO_BUILD, builds.h) between the bit-faithful (exact) and contracted (fastm) builds
+// of the compressible units.  What the units export is declared in comp_units.h: all of it in the
+// bit-faithful build, in the contracted one the functions both builds define and no other.
+#include "builds.h"
 #include "common.h"
 #include "stencil.h"
 
 namespace pyro {
 namespace exact {
-int comp_dt(pyrohip_state *, const pyrohip_comp_params *, double, double *);
-int comp_step_staged(pyrohip_state *, const pyrohip_comp_params *, double);
-int comp_step_fused(pyrohip_state *, const pyrohip_comp_params *, double);
-int comp_step_wave(pyrohip_state *, const pyrohip_comp_params *, double);
-int comp_step_fused_ex(pyrohip_state *, const pyrohip_comp_params *, double, const StepScalars *,
-                       const double **);
-int comp_step_wave_ex(pyrohip_state *, const pyrohip_comp_params *, double, const StepScalars *,
-                      const double **);
-int comp_cfl_min_device(pyrohip_state *, const pyrohip_comp_params *, const double **);
-int comp_fill_frame_user(pyrohip_state *, const pyrohip_comp_params *, const StepScalars *, double *);
-int comp_fill_frame_user_parts(const pyrohip_state *);
-int comp_sponge_run(pyrohip_state *, const pyrohip_comp_params *, const StepScalars *, double *);
-int comp_sponge_run_parts(const pyrohip_state *);
-int comp_step_sph(pyrohip_state *, const pyrohip_comp_params *, double);
-int comp_step_wave_sph(pyrohip_state *, const pyrohip_comp_params *, double);
-int comp_step_wave_sph_ex(pyrohip_state *, const pyrohip_comp_params *, double, const StepScalars *,
-                          const double **);
-int comp_step_fused_sph(pyrohip_state *, const pyrohip_comp_params *, double);
-int comp_step_fused_sph_ex(pyrohip_state *, const pyrohip_comp_params *, double, const StepScalars *,
-                           const double **);
-int comp_cfl_min_device_sph(pyrohip_state *, const pyrohip_comp_params *, const double **);
-int comp_dt_sph(pyrohip_state *, const pyrohip_comp_params *, double, double *);
-int comp_stage_dump(pyrohip_state *, int, double *);
-int comp_sponge(pyrohip_state *, const pyrohip_comp_params *, double);
-int comp_source_correct(pyrohip_state *, const pyrohip_comp_params *, double);
-int comp_rk_dt(pyrohip_state *, const pyrohip_comp_params *, double, double *);
-int comp_rk_rhs(pyrohip_state *, const pyrohip_comp_params *, pyrohip_state *, int);
-int comp_fv4_rhs(pyrohip_state *, const pyrohip_comp_params *, pyrohip_state *, int);
-int comp_rk_rhs_wave(pyrohip_state *, const pyrohip_comp_params *, pyrohip_state *, int);
-int comp_rk_step_wave(pyrohip_state *, const pyrohip_comp_params *, pyrohip_state *, int, const double *,
-                      const double *, double, const StepScalars *, const double **);
-int comp_rk_step_tile(pyrohip_state *, const pyrohip_comp_params *, pyrohip_state *, int, const double *,
-                      const double *, double, const StepScalars *, const double **);
-void rk_tile_geometry(int, int, int *, int *, int *);
-int comp_rk_cfl_min_device(pyrohip_state *, const pyrohip_comp_params *, const double **);
-int comp_wave_geometry(int, int, int, int, int, int *);
-int comp_wave_plan(int, int, int, int, int, int, int *);
-int sph_wave_geometry(int, int, int, int, int, int *);
-int comp_fv4_rhs_run(pyrohip_state *, const pyrohip_comp_params *, pyrohip_state *, int, const StepScalars *, int *);
-int fv4_stage_start(pyrohip_state *, const pyrohip_state *, const pyrohip_state *, const double *, int,
-                    const StepScalars *);
-int fv4_final_parts(const Geom &);
-int fv4_final(pyrohip_state *, const pyrohip_state *, const pyrohip_state *, const double *, int,
-              const pyrohip_comp_params *, const StepScalars *, double *);
-int fv4_sdc_node(pyrohip_state *, const pyrohip_state *, const pyrohip_state *, int, int, const int *,
-                 const double *, const StepScalars *, const int *);
-int fv4_copy_frame(pyrohip_state *, const double *);
-int state_from_centers(pyrohip_state *, int, double, double, double *);
-int comp_sdc_update(pyrohip_state *, const pyrohip_state *, const pyrohip_state *, int, int, const int *,
-                    const double *, double);
+#include "comp_units.h"
 }
 namespace fastm {
-int comp_rk_rhs(pyrohip_state *, const pyrohip_comp_params *, pyrohip_state *, int);
-int comp_fv4_rhs(pyrohip_state *, const pyrohip_comp_params *, pyrohip_state *, int);
-int comp_fv4_rhs_run(pyrohip_state *, const pyrohip_comp_params *, pyrohip_state *, int, const StepScalars *, int *);
-int comp_rk_rhs_wave(pyrohip_state *, const pyrohip_comp_params *, pyrohip_state *, int);
-int comp_rk_step_wave(pyrohip_state *, const pyrohip_comp_params *, pyrohip_state *, int, const double *,
-                      const double *, double, const StepScalars *, const double **);
-int comp_rk_step_tile(pyrohip_state *, const pyrohip_comp_params *, pyrohip_state *, int, const double *,
-                      const double *, double, const StepScalars *, const double **);
-int comp_dt(pyrohip_state *, const pyrohip_comp_params *, double, double *);
-int comp_step_staged(pyrohip_state *, const pyrohip_comp_params *, double);
-int comp_step_fused(pyrohip_state *, const pyrohip_comp_params *, double);
-int comp_step_wave(pyrohip_state *, const pyrohip_comp_params *, double);
-int comp_step_fused_ex(pyrohip_state *, const pyrohip_comp_params *, double, const StepScalars *,
-                       const double **);
-int comp_step_wave_ex(pyrohip_state *, const pyrohip_comp_params *, double, const StepScalars *,
-                      const double **);
-int comp_cfl_min_device(pyrohip_state *, const pyrohip_comp_params *, const double **);
-int comp_fill_frame_user(pyrohip_state *, const pyrohip_comp_params *, const StepScalars *, double *);
-int comp_fill_frame_user_parts(const pyrohip_state *);
-int comp_sponge_run(pyrohip_state *, const pyrohip_comp_params *, const StepScalars *, double *);
-int comp_sponge_run_parts(const pyrohip_state *);
-int comp_step_sph(pyrohip_state *, const pyrohip_comp_params *, double);
-int comp_step_wave_sph(pyrohip_state *, const pyrohip_comp_params *, double);
-int comp_step_wave_sph_ex(pyrohip_state *, const pyrohip_comp_params *, double, const StepScalars *,
-                          const double **);
-int comp_step_fused_sph(pyrohip_state *, const pyrohip_comp_params *, double);
-int comp_step_fused_sph_ex(pyrohip_state *, const pyrohip_comp_params *, double, const StepScalars *,
-                           const double **);
-int comp_cfl_min_device_sph(pyrohip_state *, const pyrohip_comp_params *, const double **);
-int comp_dt_sph(pyrohip_state *, const pyrohip_comp_params *, double, double *);
+#define PYRO_UNITS_FAST 1
+#include "comp_units.h"
 }
 }  // namespace pyro
 
@@ -193,6 +118,30 @@ static int check_comp(pyrohip_state *s, const pyrohip_comp_params *p, int max_sc
     return 0;
 }
 
+// The checks several entry points share.  fn: the caller's __func__ -- it opens the message, as in
+// PYRO_REQUIRE, so the text that reaches Python names the entry point.  (check_sponge asks nothing
+// where the sponge is off.)
+static int require_in(const char *fn, bool cond, const char *msg)
+{
+    if (cond) return 0;
+    set_error(std::string(fn) + ": " + msg);
+    return PYROHIP_ERR_ARG;
+}
+static int check_riemann(const pyrohip_comp_params *p, const char *fn)
+{
+    return require_in(fn, p->riemann >= 0 && p->riemann <= 2, "riemann must be 0 (HLLC), 1 (CGF) or 2 (HLLC_lm)");
+}
+static int check_not_well_balanced(const pyrohip_comp_params *p, const char *fn)
+{
+    return require_in(fn, !p->well_balanced, "well_balanced is carried by pyrohip_comp_rk_rhs only (compressible_rk, "
+                                             "stage by stage on the staged kernels)");
+}
+static int check_sponge(const pyrohip_comp_params *p, const char *fn)
+{
+    return require_in(fn, !p->do_sponge || p->sponge_rho_begin > p->sponge_rho_full,
+                      "sponge_rho_begin must exceed sponge_rho_full (simulation.py:172)");
+}
+
 // What a state with passive scalars (planes 4, 5: partial densities rho X) excludes: they are carried
 // by the tile kernel alone, with the upwinding of the HLLC solvers (the reference's CGF path cannot
 // run with species: consFlux on an array of states does not broadcast, riemann.py:1163, 1177)
@@ -227,10 +176,9 @@ int pyrohip_comp_evolve_p(pyrohip_state *s, const pyrohip_comp_params *p, double
     PYRO_TRY(check_comp(s, p));
     PYRO_REQUIRE(pol && steps_done, "NULL argument");
     PYRO_REQUIRE(max_steps >= 1, "max_steps must be positive");
-    PYRO_REQUIRE(!p->well_balanced, "well_balanced is carried by pyrohip_comp_rk_rhs only (compressible_rk, "
-                                    "stage by stage on the staged kernels)");
+    PYRO_TRY(check_not_well_balanced(p, __func__));
     PYRO_REQUIRE(p->kernel_set != 0, "the staged kernel set steps from the host (kernel_set 0)");
-    PYRO_REQUIRE(p->riemann >= 0 && p->riemann <= 2, "riemann must be 0 (HLLC), 1 (CGF) or 2 (HLLC_lm)");
+    PYRO_TRY(check_riemann(p, __func__));
     // (a SphericalPolar grid steps on the device where its step is one launch: comp_can_fuse_sph)
     const bool sphf = s->sph != nullptr && comp_can_fuse_sph(s, p);
     PYRO_REQUIRE((!s->sph || sphf) && !s->ramp_bc && !s->ext_old,
@@ -248,8 +196,7 @@ int pyrohip_comp_evolve_p(pyrohip_state *s, const pyrohip_comp_params *p, double
                      "ambient on the upper y side only, at least ng cells each way "
                      "(use pyrohip_comp_dt / pyrohip_comp_step)");
         PYRO_REQUIRE(!s->user_bc || s->user_bc_set, "hse / ambient boundary: call pyrohip_state_set_user_bc first");
-        PYRO_REQUIRE(!p->do_sponge || p->sponge_rho_begin > p->sponge_rho_full,
-                     "sponge_rho_begin must exceed sponge_rho_full (simulation.py:172)");
+        PYRO_TRY(check_sponge(p, __func__));
     }
     const bool wave = !sphf && takes_wave_kernel_ctu(s->g, p);
     // SphericalPolar grid on the row-marching kernel (comp_sph_wave.hip: reads a filled frame)
@@ -268,8 +215,8 @@ int pyrohip_comp_evolve_p(pyrohip_state *s, const pyrohip_comp_params *p, double
         r.min_cached = false;
         r.own_frames = true;
         PYRO_TRY(state_alt(s));
-        nfpart = p->fast_math ? fastm::comp_fill_frame_user_parts(s) : exact::comp_fill_frame_user_parts(s);
-        nspart = p->do_sponge ? (p->fast_math ? fastm::comp_sponge_run_parts(s) : exact::comp_sponge_run_parts(s)) : 0;
+        nfpart = PYRO_BUILD(p->fast_math, comp_fill_frame_user_parts(s));
+        nspart = p->do_sponge ? PYRO_BUILD(p->fast_math, comp_sponge_run_parts(s)) : 0;
         PYRO_TRY(c->strat.ensure((size_t)(nfpart + nspart) * sizeof(double)));
         fpart = (double *)c->strat.p;
         spart = fpart + nfpart;
@@ -320,8 +267,7 @@ int pyrohip_comp_evolve_p(pyrohip_state *s, const pyrohip_comp_params *p, double
         if (one_launch && m > 0) {
             s->pol_next = d_pol;
             s->pol_m = m;
-            rc = p->fast_math ? fastm::comp_step_wave_ex(s, p, 0.0, r.d_scal, &r.dmin)
-                              : exact::comp_step_wave_ex(s, p, 0.0, r.d_scal, &r.dmin);
+            rc = PYRO_BUILD(p->fast_math, comp_step_wave_ex(s, p, 0.0, r.d_scal, &r.dmin));
             continue;
         }
         // ghost cells: halos of a slab first, then the boundary fill (pyro_sim.py:250-256)
@@ -332,13 +278,11 @@ int pyrohip_comp_evolve_p(pyrohip_state *s, const pyrohip_comp_params *p, double
         if (strat) {
             // one launch: the frames of both buffers by the hse / ambient rules and the CFL partials
             // of the cells written; nothing on an iteration that will not advance
-            rc = p->fast_math ? fastm::comp_fill_frame_user(s, p, r.d_scal, fpart)
-                              : exact::comp_fill_frame_user(s, p, r.d_scal, fpart);
+            rc = PYRO_BUILD(p->fast_math, comp_fill_frame_user(s, p, r.d_scal, fpart));
             if (rc) break;
             frame_done = true;
             if (m == 0) {   // CFL minimum of the state as handed over: the full reduction
-                rc = p->fast_math ? fastm::comp_cfl_min_device(s, p, &r.dmin)
-                                  : exact::comp_cfl_min_device(s, p, &r.dmin);
+                rc = PYRO_BUILD(p->fast_math, comp_cfl_min_device(s, p, &r.dmin));
                 if (rc) break;
             } else {        // min(interior: the last step's or the sponge's partials, frame: the fill's)
                 r.fpart = fpart;
@@ -351,11 +295,9 @@ int pyrohip_comp_evolve_p(pyrohip_state *s, const pyrohip_comp_params *p, double
             if (r.min_cached)
                 r.dmin = &r.d_scal->min0;      // (... the one the previous call's last step left)
             else if (sphf)
-                rc = p->fast_math ? fastm::comp_cfl_min_device_sph(s, p, &r.dmin)
-                                  : exact::comp_cfl_min_device_sph(s, p, &r.dmin);
+                rc = PYRO_BUILD(p->fast_math, comp_cfl_min_device_sph(s, p, &r.dmin));
             else
-                rc = p->fast_math ? fastm::comp_cfl_min_device(s, p, &r.dmin)
-                                  : exact::comp_cfl_min_device(s, p, &r.dmin);
+                rc = PYRO_BUILD(p->fast_math, comp_cfl_min_device(s, p, &r.dmin));
             if (rc) break;
             // decomposed run: every rank steps with the minimum over ALL slabs -- also in the
             // first step of a call (found by running four ranks on one GPU: the slabs far from
@@ -377,23 +319,18 @@ int pyrohip_comp_evolve_p(pyrohip_state *s, const pyrohip_comp_params *p, double
         s->pol_next = d_pol;    // (one launch per step: this is step 0, its dt is in S[0])
         s->pol_m = 0;
         if (sphw)
-            rc = p->fast_math ? fastm::comp_step_wave_sph_ex(s, &pf, 0.0, r.d_scal, &r.dmin)
-                              : exact::comp_step_wave_sph_ex(s, &pf, 0.0, r.d_scal, &r.dmin);
+            rc = PYRO_BUILD(p->fast_math, comp_step_wave_sph_ex(s, &pf, 0.0, r.d_scal, &r.dmin));
         else if (sphf)
-            rc = p->fast_math ? fastm::comp_step_fused_sph_ex(s, &pf, 0.0, r.d_scal, &r.dmin)
-                              : exact::comp_step_fused_sph_ex(s, &pf, 0.0, r.d_scal, &r.dmin);
+            rc = PYRO_BUILD(p->fast_math, comp_step_fused_sph_ex(s, &pf, 0.0, r.d_scal, &r.dmin));
         else if (wave)
-            rc = p->fast_math ? fastm::comp_step_wave_ex(s, p, 0.0, r.d_scal, &r.dmin)
-                              : exact::comp_step_wave_ex(s, p, 0.0, r.d_scal, &r.dmin);
+            rc = PYRO_BUILD(p->fast_math, comp_step_wave_ex(s, p, 0.0, r.d_scal, &r.dmin));
         else
-            rc = p->fast_math ? fastm::comp_step_fused_ex(s, &pf, 0.0, r.d_scal, &r.dmin)
-                              : exact::comp_step_fused_ex(s, &pf, 0.0, r.d_scal, &r.dmin);
+            rc = PYRO_BUILD(p->fast_math, comp_step_fused_ex(s, &pf, 0.0, r.d_scal, &r.dmin));
         r.take_pending();       // (the minimum of a tile-kernel launch is taken by the next policy call)
         if (rc == 0 && p->do_sponge) {
             // the sponge on the new buffer, ghost frame included; the next policy call takes the
             // partials of the interior behind it, not the step's
-            rc = p->fast_math ? fastm::comp_sponge_run(s, p, r.d_scal, spart)
-                              : exact::comp_sponge_run(s, p, r.d_scal, spart);
+            rc = PYRO_BUILD(p->fast_math, comp_sponge_run(s, p, r.d_scal, spart));
             r.pend = spart;
             r.npend = nspart;
         }
@@ -429,10 +366,9 @@ int pyrohip_comp_dt(pyrohip_state *s, const pyrohip_comp_params *p, double cfl, 
         // (cached by the one-launch spherical step: whole-array minimum of the new state; every
         // other path that touches the state, the staged spherical set included, resets it)
         if (s->next_cfl_min > 0.0 && s->cfl_kind == 0) { *dt_out = cfl * s->next_cfl_min; return 0; }
-        return p->fast_math ? fastm::comp_dt_sph(s, p, cfl, dt_out)
-                            : exact::comp_dt_sph(s, p, cfl, dt_out);
+        return PYRO_BUILD(p->fast_math, comp_dt_sph(s, p, cfl, dt_out));
     }
-    return p->fast_math ? fastm::comp_dt(s, p, cfl, dt_out) : exact::comp_dt(s, p, cfl, dt_out);
+    return PYRO_BUILD(p->fast_math, comp_dt(s, p, cfl, dt_out));
 }
 
 int pyrohip_comp_dt_is_cached(pyrohip_state *s, int *flag)
@@ -460,10 +396,9 @@ int pyrohip_comp_step(pyrohip_state *s, const pyrohip_comp_params *p, double dt)
 {
     PYRO_TRY(check_comp(s, p, 2));
     PYRO_REQUIRE(dt > 0.0, "dt must be positive");
-    PYRO_REQUIRE(!p->well_balanced, "well_balanced is carried by pyrohip_comp_rk_rhs only (compressible_rk, "
-                                    "stage by stage on the staged kernels)");
+    PYRO_TRY(check_not_well_balanced(p, __func__));
     PYRO_REQUIRE(p->kernel_set >= -1 && p->kernel_set <= 2, "kernel_set must be -1 (automatic), 0, 1 or 2");
-    PYRO_REQUIRE(p->riemann >= 0 && p->riemann <= 2, "riemann must be 0 (HLLC), 1 (CGF) or 2 (HLLC_lm)");
+    PYRO_TRY(check_riemann(p, __func__));
     int rc;
     PYRO_REQUIRE(!s->ext_pending, "the corrector of the host-evaluated source has not run "
                                   "(pyrohip_comp_source_correct)");
@@ -494,27 +429,26 @@ int pyrohip_comp_step(pyrohip_state *s, const pyrohip_comp_params *p, double dt)
             // the row-marching kernel reads the state's ghost cells from memory: filled here if
             // the caller left the fill to the step
             if (p->fuse_fill) PYRO_TRY(pyrohip_fill_bc(s, -1));
-            rc = p->fast_math ? fastm::comp_step_wave_sph(s, p, dt) : exact::comp_step_wave_sph(s, p, dt);
+            rc = PYRO_BUILD(p->fast_math, comp_step_wave_sph(s, p, dt));
         } else if (fuse_sph)
-            rc = p->fast_math ? fastm::comp_step_fused_sph(s, p, dt) : exact::comp_step_fused_sph(s, p, dt);
+            rc = PYRO_BUILD(p->fast_math, comp_step_fused_sph(s, p, dt));
         else
-            rc = p->fast_math ? fastm::comp_step_sph(s, p, dt) : exact::comp_step_sph(s, p, dt);
+            rc = PYRO_BUILD(p->fast_math, comp_step_sph(s, p, dt));
     } else if (s->ext_old) {
         // host-evaluated source: staged kernels up to the predictor U* = U + dt S(U^n);
         // the caller evaluates S_h(U*) and finishes with pyrohip_comp_source_correct
         PYRO_REQUIRE(!s->heat && !s->ramp_bc, "a host-evaluated source excludes the heating "
                      "profile and the ramp boundary (which zeroes the source arrays, BC.py:198-200)");
-        return p->fast_math ? fastm::comp_step_staged(s, p, dt) : exact::comp_step_staged(s, p, dt);
+        return PYRO_BUILD(p->fast_math, comp_step_staged(s, p, dt));
     } else if (takes_wave_kernel_ctu(s->g, p, s->nvar))
-        rc = p->fast_math ? fastm::comp_step_wave(s, p, dt) : exact::comp_step_wave(s, p, dt);
+        rc = PYRO_BUILD(p->fast_math, comp_step_wave(s, p, dt));
     else if (p->kernel_set == 1 || p->kernel_set == -1)
-        rc = p->fast_math ? fastm::comp_step_fused(s, p, dt) : exact::comp_step_fused(s, p, dt);
+        rc = PYRO_BUILD(p->fast_math, comp_step_fused(s, p, dt));
     else
-        rc = p->fast_math ? fastm::comp_step_staged(s, p, dt) : exact::comp_step_staged(s, p, dt);
+        rc = PYRO_BUILD(p->fast_math, comp_step_staged(s, p, dt));
     s->ghost_by_rules = false;      // a new time level: its ghost cells are stale until the next fill
     if (rc == 0 && p->do_sponge) {
-        PYRO_REQUIRE(p->sponge_rho_begin > p->sponge_rho_full,
-                     "sponge_rho_begin must exceed sponge_rho_full (simulation.py:172)");
+        PYRO_TRY(check_sponge(p, __func__));
         rc = exact::comp_sponge(s, p, dt);
     }
     return rc;
@@ -544,8 +478,7 @@ int pyrohip_comp_source_correct(pyrohip_state *s, const pyrohip_comp_params *p, 
                  "needs a predictor step (pyrohip_comp_step with a source set) and S_h(U*)");
     int rc = exact::comp_source_correct(s, p, dt);
     if (rc == 0 && p->do_sponge) {
-        PYRO_REQUIRE(p->sponge_rho_begin > p->sponge_rho_full,
-                     "sponge_rho_begin must exceed sponge_rho_full (simulation.py:172)");
+        PYRO_TRY(check_sponge(p, __func__));
         rc = exact::comp_sponge(s, p, dt);
     }
     return rc;
@@ -600,10 +533,20 @@ static int comp_rk_step_any(pyrohip_state *y, const pyrohip_comp_params *p, pyro
                             const double *a, const double *b, double dt, const StepScalars *S, const double **dmin)
 {
     if (takes_wave_kernel_rk(y->g, p))
-        return p->fast_math ? fastm::comp_rk_step_wave(y, p, k, nstages, a, b, dt, S, dmin)
-                            : exact::comp_rk_step_wave(y, p, k, nstages, a, b, dt, S, dmin);
-    return p->fast_math ? fastm::comp_rk_step_tile(y, p, k, nstages, a, b, dt, S, dmin)
-                        : exact::comp_rk_step_tile(y, p, k, nstages, a, b, dt, S, dmin);
+        return PYRO_BUILD(p->fast_math, comp_rk_step_wave(y, p, k, nstages, a, b, dt, S, dmin));
+    return PYRO_BUILD(p->fast_math, comp_rk_step_tile(y, p, k, nstages, a, b, dt, S, dmin));
+}
+
+// The first iteration of a method-of-lines run (pyrohip_comp_rk_evolve_p, fv4_run): the CFL minimum of
+// the state as handed over -- whole array, ghost cells filled -- or the one the previous call's last
+// stage left, then the dt policy
+static int rk_first_iteration(EvolveRun &r, pyrohip_state *s, const pyrohip_comp_params *p, bool *frame_done)
+{
+    int rc = evolve_fill(r, false, frame_done);
+    if (r.min_cached) r.dmin = &s->d_scal->min0;
+    else if (rc == 0) rc = exact::comp_rk_cfl_min_device(s, p, &r.dmin);
+    if (rc == 0) rc = evolve_policy(r, 0);
+    return rc;
 }
 
 static int check_rk(pyrohip_state *y, const pyrohip_comp_params *p, pyrohip_state *k, int nstages,
@@ -614,7 +557,7 @@ static int check_rk(pyrohip_state *y, const pyrohip_comp_params *p, pyrohip_stat
     PYRO_REQUIRE(nstages >= 2 && nstages <= 4, "2 to 4 stages (RK2, TVD2, TVD3, RK4)");
     PYRO_REQUIRE(k->g.nx == y->g.nx && k->g.ny == y->g.ny && k->g.ng == y->g.ng && k->nvar >= 4 * nstages,
                  "the k state must have the geometry of the state and 4 planes per stage");
-    PYRO_REQUIRE(p->riemann >= 0 && p->riemann <= 2, "riemann must be 0 (HLLC), 1 (CGF) or 2 (HLLC_lm)");
+    PYRO_TRY(check_riemann(p, __func__));
     for (int s = 0; s < nstages; s++)
         for (int j = s; j < nstages; j++)
             PYRO_REQUIRE(a[s * nstages + j] == 0.0, "explicit methods only (strictly lower triangular a)");
@@ -634,8 +577,7 @@ int pyrohip_comp_rk_step(pyrohip_state *y, const pyrohip_comp_params *p, pyrohip
 {
     PYRO_TRY(check_rk(y, p, k, nstages, a, b));
     PYRO_REQUIRE(dt > 0.0, "dt must be positive");
-    PYRO_REQUIRE(!p->well_balanced, "well_balanced is carried by pyrohip_comp_rk_rhs only (compressible_rk, "
-                                    "stage by stage on the staged kernels)");
+    PYRO_TRY(check_not_well_balanced(p, __func__));
     PYRO_REQUIRE(comp_rk_can_fuse(y, p, k, nstages),
                  "pyrohip_comp_rk_step: single Cartesian domain, outflow / reflect / periodic sides, no sponge / "
                  "heating / host source, kernel_set -1, 1 or 2 and at least 4 cells each way "
@@ -655,8 +597,7 @@ int pyrohip_comp_rk_evolve_p(pyrohip_state *y, const pyrohip_comp_params *p, pyr
 {
     PYRO_TRY(check_rk(y, p, k, nstages, a, b));
     PYRO_REQUIRE(pol && steps_done && max_steps >= 1, "NULL argument / max_steps must be positive");
-    PYRO_REQUIRE(!p->well_balanced, "well_balanced is carried by pyrohip_comp_rk_rhs only (compressible_rk, "
-                                    "stage by stage on the staged kernels)");
+    PYRO_TRY(check_not_well_balanced(p, __func__));
     PYRO_REQUIRE(comp_rk_can_fuse(y, p, k, nstages),
                  "device-side stepping: compressible_rk needs the conditions of pyrohip_comp_rk_step "
                  "(pyrohip_comp_rk_can_fuse)");
@@ -669,20 +610,11 @@ int pyrohip_comp_rk_evolve_p(pyrohip_state *y, const pyrohip_comp_params *p, pyr
     int rc = 0;
     for (int m = 0; m < max_steps && rc == 0; m++) {
         bool frame_done = false;
-        if (m == 0) {
-            // the CFL minimum of the state as handed over: whole array, ghost cells filled
-            // (or the one the previous call's last stage left)
-            rc = evolve_fill(r, false, &frame_done);
-            if (r.min_cached) r.dmin = &s->d_scal->min0;
-            else if (rc == 0) rc = exact::comp_rk_cfl_min_device(s, p, &r.dmin);
-            if (rc == 0) rc = evolve_policy(r, 0);
-        } else {
-            // steps after the first: the ghost frames of both buffers, the minimum of the last stage's
-            // CFL partials and the dt policy in ONE launch (k_fill_frame2_policy, round 6) -- they were
-            // k_fill_x + k_fill_y inside the step, k_copy_frame4, k_min_one and k_dt_policy: five
-            // launches, 30 us of a 0.64 ms step at 2048^2; the policy alone where the step has to fill
-            rc = evolve_between(r, m, true, false, &frame_done);
-        }
+        // steps after the first: the ghost frames of both buffers, the minimum of the last stage's
+        // CFL partials and the dt policy in ONE launch (k_fill_frame2_policy, round 6) -- they were
+        // k_fill_x + k_fill_y inside the step, k_copy_frame4, k_min_one and k_dt_policy: five
+        // launches, 30 us of a 0.64 ms step at 2048^2; the policy alone where the step has to fill
+        rc = m == 0 ? rk_first_iteration(r, s, p, &frame_done) : evolve_between(r, m, true, false, &frame_done);
         if (rc) break;
         s->frame_prefilled = frame_done;
         rc = comp_rk_step_any(s, p, k, nstages, a, b, 0.0, s->d_scal, &r.dmin);
@@ -711,10 +643,8 @@ int pyrohip_comp_rk_rhs(pyrohip_state *y, const pyrohip_comp_params *p, pyrohip_
     PYRO_REQUIRE(k->g.nx == y->g.nx && k->g.ny == y->g.ny && k->g.ng == y->g.ng,
                  "k state must have the geometry of the stage state");
     PYRO_REQUIRE(slot >= 0 && 4 * (slot + 1) <= k->nvar, "slot outside the k state");
-    PYRO_REQUIRE(p->riemann >= 0 && p->riemann <= 2, "riemann must be 0 (HLLC), 1 (CGF) or 2 (HLLC_lm)");
-    if (p->do_sponge)
-        PYRO_REQUIRE(p->sponge_rho_begin > p->sponge_rho_full,
-                     "sponge_rho_begin must exceed sponge_rho_full (simulation.py:172)");
+    PYRO_TRY(check_riemann(p, __func__));
+    PYRO_TRY(check_sponge(p, __func__));
     if (p->well_balanced) {
         // reconstruction.py:24-25; no geometry terms in compressible_rk/fluxes.py anyway
         PYRO_REQUIRE(p->limiter == 1, "well_balanced only works for limiter == 1");
@@ -725,8 +655,8 @@ int pyrohip_comp_rk_rhs(pyrohip_state *y, const pyrohip_comp_params *p, pyrohip_
     // reconstruction)
     const bool wave = !p->do_sponge && !p->well_balanced && y->nvar == 4 && takes_wave_kernel(y->g, p);
     if (wave)
-        return p->fast_math ? fastm::comp_rk_rhs_wave(y, p, k, slot) : exact::comp_rk_rhs_wave(y, p, k, slot);
-    return p->fast_math ? fastm::comp_rk_rhs(y, p, k, slot) : exact::comp_rk_rhs(y, p, k, slot);
+        return PYRO_BUILD(p->fast_math, comp_rk_rhs_wave(y, p, k, slot));
+    return PYRO_BUILD(p->fast_math, comp_rk_rhs(y, p, k, slot));
 }
 
 // compressible_fv4 (csrc/comp_fv4.hip): the 4th-order right-hand side of a ghost-filled state
@@ -734,8 +664,7 @@ int pyrohip_comp_fv4_rhs(pyrohip_state *y, const pyrohip_comp_params *p, pyrohip
 {
     PYRO_TRY(check_comp(y, p));
     PYRO_REQUIRE(y->g.ng == 4, "compressible_fv4 needs ng = 4 (the reference's grid)");
-    PYRO_REQUIRE(!p->well_balanced, "well_balanced is carried by pyrohip_comp_rk_rhs only (compressible_rk, "
-                                    "stage by stage on the staged kernels)");
+    PYRO_TRY(check_not_well_balanced(p, __func__));
     PYRO_REQUIRE(!y->sph, "compressible_fv4 has no SphericalPolar geometry terms");
     PYRO_REQUIRE(k && k->ctx == y->ctx, "k state missing or on another context");
     PYRO_REQUIRE(k != y && k->d != y->d,
@@ -744,10 +673,8 @@ int pyrohip_comp_fv4_rhs(pyrohip_state *y, const pyrohip_comp_params *p, pyrohip
     PYRO_REQUIRE(k->g.nx == y->g.nx && k->g.ny == y->g.ny && k->g.ng == y->g.ng,
                  "k state must have the geometry of the stage state");
     PYRO_REQUIRE(slot >= 0 && 4 * (slot + 1) <= k->nvar, "slot outside the k state");
-    if (p->do_sponge)
-        PYRO_REQUIRE(p->sponge_rho_begin > p->sponge_rho_full,
-                     "sponge_rho_begin must exceed sponge_rho_full (simulation.py:172)");
-    return p->fast_math ? fastm::comp_fv4_rhs(y, p, k, slot) : exact::comp_fv4_rhs(y, p, k, slot);
+    PYRO_TRY(check_sponge(p, __func__));
+    return PYRO_BUILD(p->fast_math, comp_fv4_rhs(y, p, k, slot));
 }
 
 // fv.py:31-39 for variable `var` (-1: every variable, in order): fill its ghost cells, then
@@ -801,9 +728,7 @@ static int check_fv4_run(pyrohip_state *y, const pyrohip_comp_params *p, const c
     PYRO_TRY(check_comp(y, p));
     PYRO_REQUIRE(y->g.ng == 4, "compressible_fv4 needs ng = 4 (the reference's grid)");
     PYRO_REQUIRE(!y->sph, "compressible_fv4 has no SphericalPolar geometry terms");
-    if (p->do_sponge)
-        PYRO_REQUIRE(p->sponge_rho_begin > p->sponge_rho_full,
-                     "sponge_rho_begin must exceed sponge_rho_full (simulation.py:172)");
+    PYRO_TRY(check_sponge(p, __func__));
     const char *why = nullptr;
     if (p->well_balanced) why = "compressible.well_balanced is not carried";
     else if (y->user_bc || y->ramp_bc) why = "hse / ambient / ramp sides are not carried";
@@ -851,16 +776,7 @@ static int fv4_run(pyrohip_state *s, const pyrohip_comp_params *p, double cfl, p
     int rc = 0;
     for (int m = 0; m < max_steps && rc == 0; m++) {
         bool frame_done = false;
-        if (m == 0) {
-            // the CFL minimum of the state as handed over: whole array, ghost cells filled (or the one
-            // the previous call's last step left)
-            rc = evolve_fill(r, false, &frame_done);
-            if (r.min_cached) r.dmin = &s->d_scal->min0;
-            else if (rc == 0) rc = exact::comp_rk_cfl_min_device(s, p, &r.dmin);
-            if (rc == 0) rc = evolve_policy(r, 0);
-        } else {
-            rc = evolve_between(r, m, false, false, &frame_done);
-        }
+        rc = m == 0 ? rk_first_iteration(r, s, p, &frame_done) : evolve_between(r, m, false, false, &frame_done);
         if (rc) break;
         rc = step(r.d_scal, part);
         // the next policy call takes the minimum of the partials itself and keeps it in the step scalars
@@ -878,12 +794,6 @@ static int fv4_run(pyrohip_state *s, const pyrohip_comp_params *p, double cfl, p
     // the minimum of the last launch belongs to the state only if that launch advanced it
     if (rc == 0 && *steps_done == max_steps) s->next_cfl_min = r.H.min0;
     return rc;
-}
-static int fv4_rhs_run(pyrohip_state *st, const pyrohip_comp_params *p, pyrohip_state *k, int slot,
-                       const StepScalars *S, int *flag)
-{
-    return p->fast_math ? fastm::comp_fv4_rhs_run(st, p, k, slot, S, flag)
-                        : exact::comp_fv4_rhs_run(st, p, k, slot, S, flag);
 }
 
 extern "C" {
@@ -905,10 +815,10 @@ int pyrohip_comp_fv4_evolve_p(pyrohip_state *y, const pyrohip_comp_params *p, py
     PYRO_TRY(check_fv4_run(y, p, __func__));
     return fv4_run(y, p, cfl, pol, max_steps, steps_done, dts_out, nullptr,
                    [&](const StepScalars *S, double *part) -> int {
-                       PYRO_TRY(fv4_rhs_run(y, p, k, 0, S, y->d_flag));
+                       PYRO_TRY(PYRO_BUILD(p->fast_math, comp_fv4_rhs_run(y, p, k, 0, S, y->d_flag)));
                        for (int st = 1; st < nstages; st++) {
                            PYRO_TRY(exact::fv4_stage_start(stage, y, k, a + st * nstages, st, S));
-                           PYRO_TRY(fv4_rhs_run(stage, p, k, st, S, y->d_flag));
+                           PYRO_TRY(PYRO_BUILD(p->fast_math, comp_fv4_rhs_run(stage, p, k, st, S, y->d_flag)));
                        }
                        return exact::fv4_final(y, y, k, b, nstages, p, S, part);
                    });
@@ -943,7 +853,7 @@ int pyrohip_comp_sdc_evolve_p(pyrohip_state *y, const pyrohip_comp_params *p, py
     return fv4_run(y, p, cfl, pol, max_steps, steps_done, dts_out, (const double *)node2->d,
                    [&](const StepScalars *S, double *part) -> int {
                        pyrohip_state *U[3] = {y, node1, node2};
-                       PYRO_TRY(fv4_rhs_run(y, p, k, 0, S, y->d_flag));
+                       PYRO_TRY(PYRO_BUILD(p->fast_math, comp_fv4_rhs_run(y, p, k, 0, S, y->d_flag)));
                        int old[3] = {0, 0, 0};          // A_kold[m] -> slot
                        for (int it = 0; it < 4; it++) {
                            int nw[3] = {0, 0, 0}, next_free = 1;
@@ -951,7 +861,8 @@ int pyrohip_comp_sdc_evolve_p(pyrohip_state *y, const pyrohip_comp_params *p, py
                                if (m > 0) {
                                    while (next_free == old[1] || next_free == old[2]) next_free++;
                                    nw[m] = next_free++;
-                                   PYRO_TRY(fv4_rhs_run(U[m], p, k, nw[m], S, y->d_flag));
+                                   PYRO_TRY(PYRO_BUILD(p->fast_math,
+                                                       comp_fv4_rhs_run(U[m], p, k, nw[m], S, y->d_flag)));
                                }
                                if (m < 2)
                                    PYRO_TRY(exact::fv4_sdc_node(U[m + 1], U[m], k, nw[m], old[m], old, C[m], S,

@@ -23,22 +23,15 @@
 // LDS: max(Q, fluxes) + upper states + div(U); for 16x32 threads
 // 32 + 32 + 4 KiB = 68 KiB, two workgroups (16 waves, 4 per SIMD) per CU.
 //
-// Compiled twice like compressible.hip (PYRO_FAST = 0 / 1).
+// Compiled twice like compressible.hip (PYRO_FAST = 0 / 1, builds.h; exports: comp_units.h).
+#include "builds.h"
 #include "common.h"
 #include "hydro.h"
 #include "reduce.h"
 
-#ifndef PYRO_FAST
-#define PYRO_FAST 0
-#endif
-#if PYRO_FAST
-#define PYRO_NS fastm
-#else
-#define PYRO_NS exact
-#endif
-
 namespace pyro {
 namespace PYRO_NS {
+#include "comp_units.h"
 
 constexpr int FBI = 16;                 // threads along i (rows)
 constexpr int FBJ = 32;                 // threads along j (fast axis)

@@ -27,24 +27,18 @@
 // with dt from the run's step scalars (the bit-faithful part at the end of the file: one instance
 // serves both builds).
 //
-// This file is compiled twice: PYRO_FAST=0 (-ffp-contract=off, the bit-faithful build) and
-// PYRO_FAST=1 (-ffp-contract=fast); pyrohip_comp_fv4_rhs dispatches on fast_math.
+// This file is compiled twice (builds.h): PYRO_FAST=0 (-ffp-contract=off, the bit-faithful build) and
+// PYRO_FAST=1 (-ffp-contract=fast); the entry points (comp_api.hip) dispatch on fast_math.  Exports:
+// comp_units.h.
+#include "builds.h"
 #include "common.h"
 #include "hydro.h"
 #include "fv4_limit.h"
 #include "reduce.h"
 
-#ifndef PYRO_FAST
-#define PYRO_FAST 0
-#endif
-#if PYRO_FAST
-#define PYRO_NS fastm
-#else
-#define PYRO_NS exact
-#endif
-
 namespace pyro {
 namespace PYRO_NS {
+#include "comp_units.h"
 
 namespace {
 

@@ -28,22 +28,15 @@
 // RKIntegrator; a zero weight adds nothing and is not read), a ghost cell from the interior cell its
 // boundary rule copies from, with the sign of an odd reflection.
 //
-// Compiled twice like compressible.hip (PYRO_FAST = 0 / 1).
+// Compiled twice like compressible.hip (PYRO_FAST = 0 / 1, builds.h; exports: comp_units.h).
+#include "builds.h"
 #include "common.h"
 #include "hydro.h"
 #include "reduce.h"
 
-#ifndef PYRO_FAST
-#define PYRO_FAST 0
-#endif
-#if PYRO_FAST
-#define PYRO_NS fastm
-#else
-#define PYRO_NS exact
-#endif
-
 namespace pyro {
 namespace PYRO_NS {
+#include "comp_units.h"
 
 constexpr int RBI = 16;                 // threads along i (rows)
 constexpr int RBJ = 32;                 // threads along j (fast axis)

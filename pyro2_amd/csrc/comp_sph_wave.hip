@@ -25,23 +25,16 @@
 // frame (the caller's fill / k_fill_frame2 of a device-side run); the source terms and the CFL
 // minimum of the new state's ghost cells go through the boundary rules' index maps like the tile
 // kernel's.  Boundaries: outflow / reflect / periodic sides.
-// Compiled twice like the other compressible units (PYRO_FAST = 0 / 1).
+// Compiled twice like the other compressible units (PYRO_FAST = 0 / 1, builds.h; exports: comp_units.h).
+#include "builds.h"
 #include "common.h"
 #include "hydro.h"
 #include "reduce.h"
 #include "wave_march.h"
 
-#ifndef PYRO_FAST
-#define PYRO_FAST 0
-#endif
-#if PYRO_FAST
-#define PYRO_NS fastm
-#else
-#define PYRO_NS exact
-#endif
-
 namespace pyro {
 namespace PYRO_NS {
+#include "comp_units.h"
 
 #include "fused_common.h"
 #include "sph_common.h"

@@ -33,23 +33,16 @@
 // read of a row three iterations later (old state for the update and the
 // viscosity terms) is an L1/L2 hit.
 //
-// Compiled twice like the other compressible units (PYRO_FAST = 0 / 1).
+// Compiled twice like the other compressible units (PYRO_FAST = 0 / 1, builds.h; exports: comp_units.h).
+#include "builds.h"
 #include "common.h"
 #include "hydro.h"
 #include "reduce.h"
 #include "wave_march.h"
 
-#ifndef PYRO_FAST
-#define PYRO_FAST 0
-#endif
-#if PYRO_FAST
-#define PYRO_NS fastm
-#else
-#define PYRO_NS exact
-#endif
-
 namespace pyro {
 namespace PYRO_NS {
+#include "comp_units.h"
 
 #include "fused_common.h"
 

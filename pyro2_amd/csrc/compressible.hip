@@ -13,24 +13,18 @@
 // compared with the oracle.  Only the cells/faces inside the interior's
 // domain of dependence are computed (SURVEY.md 7 "stencil radius 4").
 //
-// This file is compiled twice: PYRO_FAST=0 (-ffp-contract=off, the
+// This file is compiled twice (builds.h): PYRO_FAST=0 (-ffp-contract=off, the
 // bit-faithful build) and PYRO_FAST=1 (-ffp-contract=fast); the entry points
-// dispatch on pyrohip_comp_params.fast_math.
+// (comp_api.hip) dispatch on pyrohip_comp_params.fast_math.  What the unit
+// exports to them is declared in comp_units.h.
+#include "builds.h"
 #include "common.h"
 #include "hydro.h"
 #include "reduce.h"
 
-#ifndef PYRO_FAST
-#define PYRO_FAST 0
-#endif
-#if PYRO_FAST
-#define PYRO_NS fastm
-#else
-#define PYRO_NS exact
-#endif
-
 namespace pyro {
 namespace PYRO_NS {
+#include "comp_units.h"
 
 // work-space plane indices
 enum {

@@ -5,11 +5,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "builds.h"
 #include "stencil.h"
-
-#ifndef PYRO_FAST
-#define PYRO_FAST 0
-#endif
 
 namespace pyro {
 // The functions below differ between the bit-faithful and the fast build of a unit.  They

@@ -5,9 +5,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#ifndef PYRO_FAST
-#define PYRO_FAST 0
-#endif
+#include "builds.h"
 
 namespace pyro {
 
