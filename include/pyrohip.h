@@ -468,6 +468,33 @@ typedef struct {
 int pyrohip_comp_evolve(pyrohip_state *s, const pyrohip_comp_params *p, double cfl,
                         pyrohip_dt_policy *policy, int max_steps, int *steps_done,
                         double *dts_out);
+/* An ENSEMBLE: nmembers >= 1 independent compressible runs with the same grid, boundary codes and
+   solver parameters, stepped together.  Members are ordinary states of one context
+   (pyrohip_state_create): every other entry point works on them before and after.  The call
+   advances every member by up to max_steps iterations of the driver's loop with its own policy
+   pols[m] (advanced in place) -- its own dt sequence, t, n and last step -- in TWO launches per
+   iteration for the whole ensemble (dt policy, then the tile kernel with one member per
+   blockIdx.y) and one read-back at the end; only each member's first iteration (ghost fill, CFL
+   minimum of the filled array unless the member's last call left it) takes launches of its own.
+   A member comes out exactly as from pyrohip_comp_evolve on it alone: bit for bit with
+   fast_math = 0; with fast_math = 1 the batch kernel is another compilation and may contract
+   differently: held to 1e-10 element-wise by tests/test_ensemble.py (DESIGN.md 3.6.3 records what
+   was seen, and on which backend).  steps_done[m]; dts_out (may be NULL):
+   nmembers x max_steps doubles, row m the dt of each iteration of member m (-1 where none was
+   taken); status[m]: 0, or PYROHIP_ERR_STATE where a step of member m found an invalid state --
+   that member is left at the state before that step with its ghost cells filled, the others are
+   not disturbed, and the call returns 0.
+   The tile kernel steps the ensemble at every grid size; it is meant for small grids (a 64^2 grid
+   is 15 workgroups of the 512 an MI355X keeps resident): above about 1024^2 a single run on the
+   row-marching kernel is the better tool.
+   PYROHIP_ERR_ARG with a message that starts "batch:" and names the reason: members of different
+   contexts, shapes, ng or boundary codes; the same state twice; nvar != 4; gravity, a heating
+   profile, host-evaluated sources, hse / ambient / ramp sides, SphericalPolar grids; slabs and a
+   global CFL minimum; kernel_set 0 and 2; the sponge; well_balanced; fewer than 4 cells in a
+   direction. */
+int pyrohip_comp_evolve_batch(pyrohip_state *const *members, int nmembers,
+                              const pyrohip_comp_params *p, double cfl, pyrohip_dt_policy *pols,
+                              int max_steps, int *steps_done, double *dts_out, int *status);
 /* debug: copy an intermediate of the LAST staged step to the host.
    stage ids: 0 q(4) 1 xi(1) 2 XM(4) 3 XP(4) 4 YM(4) 5 YP(4) 6 FxT(4)
    7 FyT(4) 8 Fx(4) 9 Fy(4).  out: (qx,qy,ncomp) reference layout.

@@ -221,6 +221,8 @@ _PROTOS = {
     "pyrohip_comp_dt": [_VP, C.POINTER(CompParams), C.c_double, _DP],
     "pyrohip_comp_evolve": [_VP, C.POINTER(CompParams), C.c_double, C.POINTER(DtPolicyC), C.c_int,
                             _IP, _DP],
+    "pyrohip_comp_evolve_batch": [C.POINTER(_VP), C.c_int, C.POINTER(CompParams), C.c_double,
+                                  C.POINTER(DtPolicyC), C.c_int, _IP, _DP, _IP],
     "pyrohip_comp_step": [_VP, C.POINTER(CompParams), C.c_double],
     "pyrohip_comp_stage_dump": [_VP, C.c_int, _DP],
     "pyrohip_mg_create": [_VP, C.c_int, C.c_double, C.c_double, C.c_double,

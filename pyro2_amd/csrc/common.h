@@ -106,6 +106,9 @@ struct pyrohip_ctx {
     // device-side stepping of a stratified run (hse / ambient sides, the sponge): the CFL partials of
     // the frame fill, then those of the sponge (comp_api.hip)
     pyro::DevBuf strat;
+    // an ensemble's call (pyrohip_comp_evolve_batch): the member table, the members' step scalars, flags,
+    // minima and dt sequences (one read-back), their tiles' CFL partials
+    pyro::DevBuf batch;
     // tracer particle sets alive on this context (ctx.hip: particles_alloc / particles_release;
     // pyrohip_shutdown releases the device memory of those still here)
     std::vector<pyrohip_particles *> psets;
@@ -303,6 +306,33 @@ struct StepPolicy {
     double *dts;                 // dt sequence of the call
 };
 
+// One member of an ensemble that steps together (pyrohip_comp_evolve_batch): what a
+// single run hands its step and policy kernels as arguments, as a row of a table in device memory
+// (context scratch, uploaded once per call).  Iteration m of the call reads buf[m & 1] and writes
+// buf[(m & 1) ^ 1]: the kernels take the parity as an argument, the table is never rewritten.
+// (A pointer a kernel reads from memory is a generic one to the compiler -- flat_ loads and stores with
+// a 64-bit address in vector registers each, where a kernel argument gives global_ ones off a scalar
+// base -- unless its type says otherwise: the table holds global memory only, and says so to the
+// device compiler.  member_ptr() hands a field to code that takes plain pointers.)
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(PYRO_EMU)
+#define PYRO_GLOBAL_MEM __attribute__((address_space(1)))
+#else
+#define PYRO_GLOBAL_MEM
+#endif
+struct BatchMember {
+    PYRO_GLOBAL_MEM double *buf[2];       // the state's buffer at the start of the call, its second buffer
+    PYRO_GLOBAL_MEM int *flag;            // positivity flag (bit 0)
+    PYRO_GLOBAL_MEM StepScalars *S;
+    PYRO_GLOBAL_MEM double *part;         // CFL partials of the member's tiles
+    PYRO_GLOBAL_MEM double *minout;       // ... their minimum, left by the policy kernel
+    PYRO_GLOBAL_MEM double *dts;          // dt of every iteration of the call (max_steps + 1 slots)
+};
+static_assert(sizeof(BatchMember) == 7 * 8, "seven 8-byte pointers, in the host and in the device compilation");
+template <class T>
+__host__ __device__ inline T *member_ptr(PYRO_GLOBAL_MEM T *q) { return (T *)q; }
+template <class T>
+inline void set_member_ptr(PYRO_GLOBAL_MEM T *&field, T *q) { field = (PYRO_GLOBAL_MEM T *)q; }
+
 // which solver's planes a state's work area holds (pyrohip_state::work_owner, state_work)
 struct WorkOwner { enum { NONE, ADV, ADVNU, ADVRK, COMP, SWE, INC, LM }; };
 }  // namespace pyro
@@ -425,6 +455,9 @@ void state_swap_alt(pyrohip_state *s);
 // uploads H.
 int evolve_begin(pyrohip_state *s, const pyrohip_dt_policy *pol, double cfl, double dx, double dy,
                  int max_steps, StepScalars *H);
+// ... the second half alone: *H zeroed and filled from the policy (an ensemble's members keep their
+// scalars in the context's scratch, pyrohip_comp_evolve_batch)
+void evolve_scalars(const pyrohip_dt_policy *pol, double cfl, double dx, double dy, StepScalars *H);
 
 // ---- the device-side run protocol (evolve.hip) ----
 // 256-thread pieces of a state's ghost frame: the 2 ng full ghost rows in pieces of 256 columns,
@@ -492,6 +525,11 @@ int evolve_between(EvolveRun &r, int m, bool frame, bool fill, bool *frame_done)
 // frames; one_launch: they wrote none), the cached minimum, pol, the verdict
 int evolve_close(EvolveRun &r, pyrohip_dt_policy *pol, int *steps_done, double *dts_out, bool framed,
                  bool one_launch);
+// an ensemble's call (pyrohip_comp_evolve_batch): k_dt_policy on ONE member's scalars with the CFL
+// minimum at dmin (its first iteration; M: the member's row, host copy), and k_dt_policy_batch -- one
+// workgroup per member, each on the nparts partials its last step left (d_tab: the table on the device)
+int evolve_batch_policy0(pyrohip_ctx *c, const BatchMember &M, const double *dmin);
+int evolve_batch_policy(pyrohip_ctx *c, const BatchMember *d_tab, int nmembers, int nparts, int slot, int final_call);
 // enqueue the copy of one plane (laid out like the state's) into a (qx, qy) host array; the
 // caller synchronises
 int plane_to_host(pyrohip_state *s, const double *dev_plane, double *host);

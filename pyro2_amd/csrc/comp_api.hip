@@ -358,6 +358,159 @@ int pyrohip_comp_evolve(pyrohip_state *s, const pyrohip_comp_params *p, double c
     return pyrohip_comp_evolve_p(s, p, cfl, pol, max_steps, steps_done, dts_out, nullptr, nullptr);
 }
 
+// An ensemble of independent runs on one grid, stepped together: per iteration ONE
+// policy launch (a workgroup per member) and ONE launch of the tile kernel (blockIdx.y = member) for
+// all of them.  What pyrohip_comp_evolve does for a single run on the tile kernel, member by member:
+// the same first iteration with the existing launches, the same close.
+int pyrohip_comp_evolve_batch(pyrohip_state *const *members, int nmembers, const pyrohip_comp_params *p, double cfl,
+                              pyrohip_dt_policy *pols, int max_steps, int *steps_done, double *dts_out, int *status)
+{
+    const char *fn = "batch";
+    PYRO_TRY(require_in(fn, members && p && pols && steps_done && status, "NULL argument"));
+    PYRO_TRY(require_in(fn, nmembers >= 1 && nmembers <= 65535, "1 to 65535 members"));
+    PYRO_TRY(require_in(fn, max_steps >= 1, "max_steps must be positive"));
+    for (int m = 0; m < nmembers; m++) PYRO_TRY(require_in(fn, members[m] != nullptr, "a member is NULL"));
+    pyrohip_state *s0 = members[0];
+    pyrohip_ctx *c = s0->ctx;
+    for (int m = 0; m < nmembers; m++) {
+        const pyrohip_state *s = members[m];
+        const std::string who = "member " + std::to_string(m) + ": ";
+        PYRO_TRY(require_in(fn, s->ctx == c, (who + "another context than member 0's").c_str()));
+        PYRO_TRY(require_in(fn, s->nvar == 4, (who + "nvar must be 4 (density, energy, x-momentum, y-momentum; "
+                                                     "passive scalars are not carried)").c_str()));
+        PYRO_TRY(require_in(fn, s->g.nx == s0->g.nx && s->g.ny == s0->g.ny,
+                            (who + "another shape (nx, ny) than member 0's").c_str()));
+        PYRO_TRY(require_in(fn, s->g.ng == s0->g.ng, (who + "another ng than member 0's").c_str()));
+        PYRO_TRY(require_in(fn, s->bc == s0->bc, (who + "other boundary codes than member 0's").c_str()));
+        for (int k = 0; k < m; k++)
+            PYRO_TRY(require_in(fn, members[k] != s, (who + "the same state is listed twice").c_str()));
+        // what the tile kernel with the ghost fill folded in does not carry (comp_can_fuse_fill), by name
+        PYRO_TRY(require_in(fn, !s->sph, (who + "SphericalPolar grids are not carried").c_str()));
+        PYRO_TRY(require_in(fn, !s->user_bc && !s->ramp_bc,
+                            (who + "hse / ambient / ramp sides are not carried").c_str()));
+        PYRO_TRY(require_in(fn, !s->heat, (who + "a heating profile is not carried").c_str()));
+        PYRO_TRY(require_in(fn, !s->ext_old && !s->ext_new, (who + "host-evaluated sources are not carried").c_str()));
+        PYRO_TRY(require_in(fn, !s->nb_set, (who + "slabs of a decomposed run are not carried").c_str()));
+    }
+    PYRO_TRY(require_in(fn, !c->global_cfl, "a global CFL minimum (decomposed runs) is not carried"));
+    PYRO_TRY(require_in(fn, s0->g.nx >= 4 && s0->g.ny >= 4, "the tile kernel needs at least 4 cells in each direction"));
+    PYRO_TRY(require_in(fn, s0->g.ng >= 4, "compressible needs ng >= 4 (compressible/simulation.py:194)"));
+    PYRO_TRY(require_in(fn, same_index_map_kinds(s0, false),
+                        "outflow / reflect / periodic sides only, the same kind for the four variables"));
+    PYRO_TRY(require_in(fn, p->limiter >= 0 && p->limiter <= 2, "limiter must be 0, 1 or 2"));
+    PYRO_TRY(require_in(fn, p->dx > 0 && p->dy > 0 && p->gamma > 1.0, "bad dx/dy/gamma"));
+    PYRO_TRY(check_riemann(p, fn));
+    PYRO_TRY(require_in(fn, p->grav == 0.0, "gravity (grav != 0) is not carried"));
+    PYRO_TRY(require_in(fn, !p->do_sponge, "the sponge (do_sponge) is not carried"));
+    PYRO_TRY(require_in(fn, !p->well_balanced, "well_balanced is not carried"));
+    PYRO_TRY(require_in(fn, p->kernel_set == -1 || p->kernel_set == 1,
+                        "kernel_set 0 and 2 are not carried (the tile kernel, kernel_set 1 or -1, steps an ensemble)"));
+
+    // context scratch: the table | scalars, minima, flags, dt sequences (ONE read-back) | CFL partials
+    const int N = nmembers, nt = PYRO_BUILD(p->fast_math, comp_fused_tiles(s0));
+    const size_t o_scal = (size_t)N * sizeof(BatchMember), o_min = o_scal + (size_t)N * sizeof(StepScalars),
+                 o_flag = o_min + (size_t)N * 8, o_dts = o_flag + (((size_t)N * 4 + 7) & ~(size_t)7),
+                 o_part = o_dts + (size_t)N * (max_steps + 1) * 8, total = o_part + (size_t)N * nt * 8;
+    static_assert(sizeof(BatchMember) % 8 == 0 && sizeof(StepScalars) % 8 == 0, "8-byte fields");
+    PYRO_TRY(c->batch.ensure(total));
+    char *db = (char *)c->batch.p;
+    std::vector<char> hb(o_part, 0);
+    BatchMember *tab = (BatchMember *)hb.data();
+    StepScalars *H = (StepScalars *)(hb.data() + o_scal);
+    std::vector<char> cached(N, 0);
+    for (int m = 0; m < N; m++) {
+        pyrohip_state *s = members[m];
+        PYRO_TRY(comm_wait_halo(s));
+        PYRO_TRY(state_alt(s));
+        BatchMember &M = tab[m];
+        memset(&M, 0, sizeof(M));
+        set_member_ptr(M.buf[0], s->d);
+        set_member_ptr(M.buf[1], s->alt_base + geom_lead(s->g));
+        set_member_ptr(M.S, (StepScalars *)(db + o_scal) + m);
+        set_member_ptr(M.minout, (double *)(db + o_min) + m);
+        set_member_ptr(M.flag, (int *)(db + o_flag) + m);
+        set_member_ptr(M.dts, (double *)(db + o_dts) + (size_t)m * (max_steps + 1));
+        set_member_ptr(M.part, (double *)(db + o_part) + (size_t)m * nt);
+        evolve_scalars(&pols[m], cfl, p->dx, p->dy, &H[m]);
+        // the minimum the member's last call left still describes it (evolve_open)
+        cached[m] = cfl_min_cached(s, 0, p->gamma, p->dx, p->dy) ? 1 : 0;
+        H[m].min0 = cached[m] ? s->next_cfl_min : 0.0;
+        H[m].keep0 = cached[m] ? 1.0 : 0.0;
+        s->pend_part = nullptr;
+    }
+    PYRO_CHECK_HIP(hipMemcpyAsync(db, hb.data(), o_part, hipMemcpyHostToDevice, c->stream));
+    PYRO_CHECK_HIP(hipStreamSynchronize(c->stream));      // (pageable host memory: the copy has left hb)
+    const BatchMember *d_tab = (const BatchMember *)db;
+    // A launch or copy that fails from here on leaves work enqueued on members whose buffers may have changed
+    // places an unknown number of times: the error is collected, and before it is returned every member is
+    // put into a state the other entry points can work on (contents undefined, nothing cached, ghost cells stale)
+    const auto abandon = [&](int rc) {
+        (void)hipStreamSynchronize(c->stream);
+        for (int m = 0; m < N; m++) {
+            pyrohip_state *s = members[m];
+            s->halo_pending = false;
+            s->frame_prefilled = false;
+            s->ghost_by_rules = false;
+            s->next_cfl_min = -1.0;
+            s->cfl_is_global = false;
+            steps_done[m] = 0;
+            status[m] = 0;
+        }
+        return rc;
+    };
+    int rc = 0;
+    // first iteration, member by member with the launches of a single run: ghost fill, the CFL minimum
+    // of the filled array (or the kept one), the policy
+    for (int m = 0; m < N && rc == 0; m++) {
+        pyrohip_state *s = members[m];
+        rc = pyrohip_fill_bc(s, -1);
+        const double *dmin = &member_ptr(tab[m].S)->min0;
+        if (rc == 0 && !cached[m]) rc = PYRO_BUILD(p->fast_math, comp_cfl_min_device(s, p, &dmin));
+        if (rc == 0) rc = evolve_batch_policy0(c, tab[m], dmin);
+    }
+    for (int it = 0; it < max_steps && rc == 0; it++) {
+        if (it > 0) rc = evolve_batch_policy(c, d_tab, N, nt, it, 0);
+        if (rc == 0) rc = PYRO_BUILD(p->fast_math, comp_step_fused_batch(s0, p, d_tab, N, it & 1));
+    }
+    if (rc == 0) rc = evolve_batch_policy(c, d_tab, N, nt, max_steps, 1);
+    // the one round trip of the call
+    if (rc == 0)
+        rc = (int)hipMemcpyAsync(hb.data() + o_scal, db + o_scal, o_part - o_scal, hipMemcpyDeviceToHost, c->stream);
+    if (rc == 0) {
+        rc = (int)hipStreamSynchronize(c->stream);
+        if (rc != 0) set_error(std::string("batch: the read-back failed: ") + hipGetErrorString((hipError_t)rc));
+    }
+    if (rc != 0) return abandon(rc);
+    // the close, member by member as evolve_close does it for a run on the tile kernel
+    const double *mins = (const double *)(hb.data() + o_min);
+    const int *flags = (const int *)(hb.data() + o_flag);
+    const double *dts = (const double *)(hb.data() + o_dts);
+    for (int m = 0; m < N; m++) {
+        pyrohip_state *s = members[m];
+        const StepScalars &R = H[m];
+        const bool invalid = (flags[m] & 1) || R.dead;
+        // every iteration exchanged the member's buffers, the first R.steps of them advanced it: the
+        // last state that advanced (after an invalid step: the one before it) sits R.steps exchanges on
+        if (R.steps % 2) state_swap_alt(s);
+        s->halo_pending = false;
+        s->frame_prefilled = false;
+        s->ghost_by_rules = false;      // a new time level: its ghost cells are stale until the next fill
+        // after an invalid step the state carries its own filled ghost cells (evolve_close)
+        if (invalid) PYRO_TRY(pyrohip_fill_bc(s, -1));
+        // the minimum of the last launch belongs to the state only if that launch advanced it
+        s->next_cfl_min = (R.steps == max_steps && !invalid) ? mins[m] : -1.0;
+        s->cfl_is_global = false;
+        s->cfl_kind = 0;
+        s->cfl_par[0] = p->gamma; s->cfl_par[1] = p->dx; s->cfl_par[2] = p->dy;
+        pols[m].t = R.t; pols[m].dt_old = R.dt_old; pols[m].n = R.n;
+        steps_done[m] = R.steps;
+        status[m] = invalid ? PYROHIP_ERR_STATE : 0;
+        if (dts_out)
+            memcpy(dts_out + (size_t)m * max_steps, dts + (size_t)m * (max_steps + 1), (size_t)max_steps * sizeof(double));
+    }
+    return 0;
+}
+
 int pyrohip_comp_dt(pyrohip_state *s, const pyrohip_comp_params *p, double cfl, double *dt_out)
 {
     PYRO_TRY(check_comp(s, p, 2));      // (the CFL minimum reads the four hydro planes)

@@ -19,6 +19,8 @@ int comp_rk_rhs(pyrohip_state *, const pyrohip_comp_params *, pyrohip_state *, i
 int comp_step_fused(pyrohip_state *, const pyrohip_comp_params *, double);                      // comp_fused.hip
 int comp_step_fused_ex(pyrohip_state *, const pyrohip_comp_params *, double, const StepScalars *,
                        const double **);                                                        // comp_fused.hip
+int comp_fused_tiles(const pyrohip_state *);                                                    // comp_fused.hip
+int comp_step_fused_batch(pyrohip_state *, const pyrohip_comp_params *, const BatchMember *, int, int);   // comp_fused.hip
 int comp_step_fused_sph(pyrohip_state *, const pyrohip_comp_params *, double);                  // comp_fused.hip
 int comp_step_fused_sph_ex(pyrohip_state *, const pyrohip_comp_params *, double, const StepScalars *,
                            const double **);                                                    // comp_fused.hip

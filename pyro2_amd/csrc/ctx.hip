@@ -341,11 +341,16 @@ int evolve_begin(pyrohip_state *s, const pyrohip_dt_policy *pol, double cfl, dou
         PYRO_CHECK_HIP(hipMalloc((void **)&s->d_dts, (size_t)cap * sizeof(double)));
         s->dts_cap = cap;
     }
+    evolve_scalars(pol, cfl, dx, dy, H);
+    return 0;
+}
+
+void evolve_scalars(const pyrohip_dt_policy *pol, double cfl, double dx, double dy, StepScalars *H)
+{
     memset(H, 0, sizeof(*H));
     H->t = pol->t; H->dt_old = pol->dt_old; H->n = pol->n;
     H->tmax = pol->tmax; H->f0 = pol->init_tstep_factor; H->mx = pol->max_dt_change;
     H->fix_dt = pol->fix_dt; H->cfl = cfl; H->dx = dx; H->dy = dy;
-    return 0;
 }
 
 int plane_to_host(pyrohip_state *s, const double *dev_plane, double *host)
@@ -477,6 +482,7 @@ int pyrohip_shutdown(pyrohip_ctx *c)
     c->reduce.release();
     c->prio_board.release();
     c->strat.release();
+    c->batch.release();
     c->mg_trace.release();
     if (c->reduce_host) (void)hipHostFree(c->reduce_host);
     (void)hipEventDestroy(c->ev0);

@@ -172,7 +172,36 @@ __global__ __launch_bounds__(kPolicyThreads) void k_fill_frame2_policy(
     if (piece < npieces) fill_frame2_piece<NV>(src, cur, alt, g, bc, piece, (int)threadIdx.x % 256);
 }
 
+// The policy between two steps of an ensemble (pyrohip_comp_evolve_batch): one
+// workgroup per member does what k_dt_policy does for a single run -- the minimum of the member's CFL
+// partials (kept in its minout), then dt_policy_apply on its own scalars, flag and dt slots.
+__global__ __launch_bounds__(kPolicyThreads) void k_dt_policy_batch(const BatchMember *__restrict__ tab, int nparts,
+                                                                    int slot, int final_call)
+{
+    const BatchMember M = tab[blockIdx.x];
+    dt_policy_block(member_ptr(M.S), member_ptr(M.minout), member_ptr(M.flag), member_ptr(M.dts), slot, final_call,
+                    member_ptr(M.part), nparts, member_ptr(M.minout), 1, nullptr, 0);
+}
+
 namespace pyro {
+
+int evolve_batch_policy(pyrohip_ctx *c, const BatchMember *d_tab, int nmembers, int nparts, int slot, int final_call)
+{
+    PYRO_LAUNCH(c, "k_dt_policy_batch", k_dt_policy_batch, dim3(nmembers), dim3(kPolicyThreads), 0, d_tab, nparts,
+                slot, final_call);
+    PYRO_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// the first policy call of a member: k_dt_policy on the CFL minimum of the state as handed over
+int evolve_batch_policy0(pyrohip_ctx *c, const BatchMember &M, const double *dmin)
+{
+    PYRO_LAUNCH(c, "k_dt_policy", k_dt_policy, dim3(1), dim3(kPolicyThreads), 0, member_ptr(M.S), dmin,
+                (const int *)member_ptr(M.flag), member_ptr(M.dts), 0, 0, (const double *)nullptr, 0,
+                member_ptr(M.minout), 1, (const double *)nullptr, 0);
+    PYRO_CHECK_HIP(hipGetLastError());
+    return 0;
+}
 
 // (x sides of a slab that are cuts -- PYROHIP_BC_HALO -- are identity maps: the halo rows are data
 // that arrived with the exchange, the y rule runs along them like along an interior row and the

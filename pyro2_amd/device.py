@@ -783,6 +783,45 @@ class DeviceState:
         return self._evolve(policy, max_steps, "pyrohip_comp_evolve", (self.h, C.byref(params), float(cfl)),
                             particles)
 
+    @staticmethod
+    def comp_evolve_batch(states, params, cfl, policies, max_steps):
+        """an ENSEMBLE of independent runs on one grid stepped together: up to
+        max_steps iterations of every member of `states` (DeviceStates of one context with the
+        same shape and boundary types) with its own policy of `policies` (as comp_evolve's,
+        advanced in place), two launches per iteration for all of them.  Returns (dts, status):
+        per member the dt of the steps it took, and 0 or ERR_STATE.  A member that met an
+        invalid state raises what comp_evolve raises for it -- after every policy has been
+        advanced -- with the member's index (e.member), e.steps_done and e.dts as there, and
+        e.all_dts / e.status for the others, whose states and results stay usable."""
+        states, policies = list(states), list(policies)
+        n, max_steps = len(states), int(max_steps)
+        if n < 1 or len(policies) != n:
+            raise ValueError("comp_evolve_batch: one policy per state, at least one state")
+        ctx, l = states[0].ctx, states[0]._l
+        handles = (C.c_void_p * n)(*[s.h.value for s in states])
+        pcs = (_lib.DtPolicyC * n)(*[_lib.DtPolicyC(p.tmax, p.f0, p.mx, p.fix, p.t, p.dt_old, p.n)
+                                     for p in policies])
+        done = np.zeros(n, dtype=np.int32)
+        status = np.zeros(n, dtype=np.int32)
+        dts = np.empty((n, max_steps))
+        with ctx.lock:
+            rc = l.pyrohip_comp_evolve_batch(handles, n, C.byref(params), float(cfl), pcs, max_steps,
+                                             _lib.iptr(done), dptr(dts), _lib.iptr(status))
+        check(rc)           # (a refusal: nothing ran, the policies are as they were)
+        for p, pc in zip(policies, pcs):
+            p.t, p.dt_old, p.n = pc.t, pc.dt_old, int(pc.n)
+        out = [dts[m, :done[m]].copy() for m in range(n)]
+        status = [int(v) for v in status]
+        for m, st in enumerate(status):
+            if st != 0:
+                e = _lib.PyroHipError(st, f"member {m} of the ensemble after {len(out[m])} steps: invalid state: "
+                                          "min(rho) <= 0 or min(e) <= 0 on the interior "
+                                          "(compressible/simulation.py:68-71); the state is the one before that step")
+                e.member, e.steps_done, e.dts = m, len(out[m]), out[m]
+                e.all_dts, e.status = out, status
+                raise e
+        return out, status
+
     STAGES = {"q": 0, "xi": 1, "XM": 2, "XP": 3, "YM": 4, "YP": 5, "FxT": 6,
               "FyT": 7, "Fx": 8, "Fy": 9}
 
